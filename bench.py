@@ -5,14 +5,23 @@
 A step = one RD::TraceRays frame (RayTraceProperties{totalSamples 0, batchSize 4, depth 8}) of the
 workload, scene and accumulators already resident in HBM.  Default workload = the Sponza-class scene (BASELINE.json
 configs[2], the configuration the north star's 1-GPU target is stated on); the sample1 scene (configs[1]) and the
-10.4 M-triangle scene (configs[4] geometry) are always timed as well and reported under `also` (N = 1).
+10.4 M-triangle scene (configs[4] geometry) are timed as well with --full and reported under `also` (N = 1).
 N > 1: one process per GPU (torch.distributed / RCCL), the frame is sharded by interleaved 64x64 image tiles, no
 collective while rendering, one RGBA8 gather to rank 0 at frame end -- inside the timed region.  The headline at every N is
 the metric's own frame (1920x1080, 4 spp, depth 8) split N ways: STRONG scaling, what the north star's ">= 6x at 8 GPUs" is
 about.  The weak-scaling figure (N x 4 samples per pixel, every GPU keeps the rays of the N = 1 frame: BASELINE configs 3 / 4
-are such frames) is timed as well and reported under `also.weak_scaling_n_x_spp`; --scaling weak makes it the headline.
+are such frames) is timed as well with --full and reported under `also.weak_scaling_n_x_spp`; --scaling weak makes it the headline.
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+A plain run does only what the headline needs: it builds the scene, warms up, times --steps frames, writes the last
+frame with --dump-outputs DIR, and prints the result line.  Everything else below (the visit-count pass, per-stage HIP
+events, PMC passes, the workloads under `also`, the reference's kernel, the CPU baseline) runs only with --full.
+
+--dump-outputs DIR writes what the last timed frame computed, as a caller of RD::TraceRays would read it back (rank 0):
+  radiance.npy  the frame's imageScratch, RGB channels (float32, H x W x 3; the path never writes channel 3); N = 1 only
+  image.npy     the RGBA8 frame (after the gather when N > 1) as float32, H x W x 4
+Frames larger than 1080p are written at a fixed, seeded sample of pixels (pixel_index.npy), 64 MB in all at most.
+
+Prints ONE JSON line (rank 0).  Besides the contract fields, a --full run carries
   roofline      dominant kernel (k_fused_pool = shadow rays of bounce d + closest-hit rays of bounce d+1 per launch).
                 `achieved` = fabric bytes per launch (rocprofv3 PMC passes FETCH_SIZE / WRITE_SIZE of this same workload,
                 collected by this run in child processes after the timed region; units as
@@ -340,6 +349,25 @@ def cpu_baseline(scene, budget_s=20.0):
 
 STAGE_KEYS = ("ms_extend", "ms_shadow", "ms_shade", "ms_generate", "ms_accumulate", "ms_total", "ms_fused", "ms_path", "ms_sort")
 
+DUMP_CAP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """writes each (H, W, C) array as <out_dir>/<name>.npy in float32.  When they would exceed DUMP_CAP_BYTES in all, every
+    array is written at the same fixed, seeded sample of pixels ((K, C) rows), and the sample as pixel_index.npy (float64)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_CAP_BYTES:
+        n = next(iter(arrays.values())).shape[0] * next(iter(arrays.values())).shape[1]
+        flat = {k: a.reshape(n, -1) for k, a in arrays.items()}
+        row = sum(a.shape[1] * 4 for a in flat.values()) + 8
+        idx = np.sort(np.random.default_rng(seed).choice(n, min(n, (DUMP_CAP_BYTES - 4096) // row), replace=False))   # 4096: .npy headers
+        arrays = {k: a[idx] for k, a in flat.items()}
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -354,9 +382,14 @@ def main():
     ap.add_argument("--scaling", choices=("weak", "strong"), default="strong",
                     help="N > 1: strong (default) = the metric's own frame (1920x1080, --spp samples per pixel) is split N ways; weak = every "
                          "GPU keeps the rays of the N = 1 frame (the frame has N x --spp samples per pixel: BASELINE configs 3 / 4 are such frames)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC child passes (roofline.traffic / achieved become null)")
-    ap.add_argument("--no-reference", action="store_true", help="skip the informational run of the reference's own kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline (visit counts, per-stage HIP events, PMC passes), the workloads under 'also', "
+                         "the other scaling mode (N > 1), the reference's own kernel and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame (radiance.npy, image.npy; float32) into DIR")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 PMC child passes (roofline.traffic / achieved become null)")
+    ap.add_argument("--no-reference", action="store_true", help="--full: skip the informational run of the reference's own kernel")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--fuse", type=int, default=-1, help="-1 auto, 0/1: shadow(d)+extend(d+1) in one launch")
     ap.add_argument("--pipeline", type=int, default=-1, help="-1 library default, 0 staged wavefront, 1 whole paths in one persistent launch")
@@ -366,8 +399,10 @@ def main():
     ap.add_argument("--cull", type=int, default=-1, help="-1 library default (automatic); 0 = exhaustive walk, 1 = culled walk (pool engine)")
     ap.add_argument("--sort", type=int, default=-1, help="-1 library default (automatic); 0 / 1: per-bounce ray sort off / on")
     ap.add_argument("--opt", default=None, help="comma list name=value of library options (rdx_set_option) for experiments")
-    ap.add_argument("--also", default=None, help="comma list of extra workloads to time (reported under 'also'); default at N=1: the other two")
+    ap.add_argument("--also", default=None, help="--full: comma list of extra workloads to time (reported under 'also'); default at N=1: the others")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if args.pmc_child:          # (the parent has built everything; no compiler runs inside the profiled process)
         pmc_child(args)
@@ -375,9 +410,11 @@ def main():
 
     import numpy as np
     import torch
-    import __graft_entry__ as ge
-    ge.build()
     import rrt_amd
+    if not os.path.exists(rrt_amd._lib.LIB_PATH):
+        # a tree build() has not run in; a built tree is used as it is and never written to (it may be read-only)
+        import __graft_entry__ as ge
+        ge.build()
     from radiance_ray_tracing_amd import dist as rdist, rd, scenes
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -407,7 +444,7 @@ def main():
     # tiles are dealt to the ranks (what BASELINE configs 3 and 4 do: 64 / 256 spp over 8 GPUs); strong: the N = 1 frame split N ways
     spp_main = args.spp * world if (world > 1 and args.scaling == "weak") else args.spp
 
-    def run_workload(key, steps, warmup, want_roofline, spp=None):
+    def run_workload(key, steps, warmup, want_roofline, spp=None, stage_events=True):
         cfg, _ = WORKLOADS[key]
         scene = scenes.CONFIGS[cfg](args.width, args.height, spp_main if spp is None else spp, args.depth)
         dev = scenes.DeviceScene(scene, plt)
@@ -439,8 +476,9 @@ def main():
             frame()
         # per-stage HIP events (the roofline's kernel durations) ride along in the timed region at N = 1; with N > 1
         # a rank's frame is a few ms and the event records between its ~36 dispatches cost ~5 % of it, so there the
-        # timed region runs without them and the stage times come from extra, untimed frames of the same workload
-        prof_inline = world == 1
+        # timed region runs without them and the stage times come from extra, untimed frames of the same workload.
+        # A plain run (no --full) reports no stage times and records no events at all.
+        prof_inline = stage_events and world == 1
         rd.SetProfiling(prof_inline)
         acc = dict(primary=0, bounce=0, shadow=0, hits=0, ms_extend=0.0, ms_shadow=0.0, ms_shade=0.0, ms_generate=0.0,
                    ms_accumulate=0.0, ms_total=0.0, ms_fused=0.0, ms_path=0.0, ms_sort=0.0, launches_extend=0)
@@ -458,7 +496,7 @@ def main():
             acc["groups"] = int(st.groups)
         sync()
         dt = time.perf_counter() - t0
-        if not prof_inline:
+        if stage_events and not prof_inline:
             rd.SetProfiling(True)
             nprof = min(steps, 3)
             for _ in range(nprof):
@@ -470,7 +508,8 @@ def main():
         rd.SetProfiling(False)
         return scene, dev, acc, dt, visits
 
-    scene, dev, acc, dt, visits = run_workload(args.workload, args.steps, args.warmup, True)
+    full = args.full
+    scene, dev, acc, dt, visits = run_workload(args.workload, args.steps, args.warmup, full, stage_events=full)
 
     # aggregate over ranks: rays summed, time = max
     rays_local = acc["primary"] + acc["bounce"] + acc["shadow"]
@@ -484,13 +523,21 @@ def main():
     else:
         rays_total, rays_pb = float(rays_local), float(acc["primary"] + acc["bounce"])
 
+    if args.dump_outputs and rank == 0:
+        # the last timed frame, as a caller reads it back (every frame restarts at totalSamples 0: each is the same frame)
+        outs = {}
+        if world == 1:
+            outs["radiance"] = dev.read_scratch()[:, :, :3]
+        outs["image"] = rd.ReadBuffer(plt, dev.rdImage, args.width * args.height * 4).reshape(args.height, args.width, 4)
+        dump_outputs(args.dump_outputs, outs)
+
     tlas_blob = None
-    if rank == 0 and world == 1 and not args.no_reference and not under_profiler():
+    if full and rank == 0 and world == 1 and not args.no_reference and not under_profiler():
         tlas_blob = rd.ReadBuffer(dev.plt, dev.topAccelStruct, dev.topAccelStruct.size).tobytes()
     del dev                                                      # frees nothing on the device (the API has no release), drops the host side
 
     also = {}
-    if world > 1:
+    if full and world > 1:
         # the other scaling mode on the same ranks, for the record.  strong headline -> also the weak figure (N x spp samples per
         # pixel, every GPU keeps the rays of the N = 1 frame); weak headline -> also the metric's own frame split N ways
         import torch.distributed as tdist
@@ -507,7 +554,7 @@ def main():
             "workload": workload_label(args.workload, args, spp_o), "Mrays_per_s": round(float(t_s[0]) / float(tm_s[0]) / 1e6, 2),
             "ms_per_frame": round(1e3 * float(tm_s[0]) / st_s, 3), "steps": st_s}
     also_keys = [k for k in (args.also.split(",") if args.also is not None else
-                             ([w for w in ("sample1", "sponza", "sanmiguel", "sponza400") if w != args.workload] if world == 1 else [])) if k]
+                             ([w for w in ("sample1", "sponza", "sanmiguel", "sponza400") if w != args.workload] if world == 1 else [])) if k] if full else []
     for key in also_keys:
         sc2, _, a2, dt2, v2 = run_workload(key, max(2, args.steps // 2), 1, True)
         r2 = a2["primary"] + a2["bounce"] + a2["shadow"]
@@ -525,19 +572,6 @@ def main():
         return
     steps = args.steps
     ms_per_step = 1e3 * dt / steps
-    rays_extend_per_frame = (acc["primary"] + acc["bounce"]) / steps
-    bytes_extend_frame = algorithmic_bytes(visits["visit_top_nodes"][0], visits["visit_instances"][0],
-                                           visits["visit_bot_nodes"][0], visits["visit_triangles"][0], rays_extend_per_frame)
-    bytes_shadow_frame = algorithmic_bytes(visits["visit_top_nodes"][1], visits["visit_instances"][1],
-                                           visits["visit_bot_nodes"][1], visits["visit_triangles"][1], acc["shadow"] / steps)
-    kernel_name, roof_bytes, trav_s, launches = traversal_roofline(acc, visits, steps, args.depth)
-    ref_equiv = roof_bytes * steps / trav_s / 1e9 if trav_s > 0 else 0.0
-    pixels = args.width * args.height if world == 1 else None
-    frame_bytes = bytes_extend_frame + bytes_shadow_frame + 184 * acc["hits"] / steps + (20 * pixels if pixels else 0)
-    meas = {"traffic": None, "achieved": None, "issue": None}
-    if world == 1 and not args.no_pmc and not under_profiler():
-        meas = measured_roofline(kernel_name, trav_s, launches, option_args(args))
-    achieved = meas["achieved"]
     out = {
         "metric": "Mrays/sec (primary+secondary) and ms/frame at 1920x1080, 4 spp, depth 8",
         "value": round(rays_total / dt / 1e6, 3),
@@ -564,39 +598,55 @@ def main():
         "rays_per_frame": {"primary": acc["primary"] // steps, "bounce": acc["bounce"] // steps, "shadow": acc["shadow"] // steps,
                            "note": "rank 0 share" if world > 1 else "whole frame"},
         "Mrays_per_s_primary_plus_bounce": round(rays_pb / dt / 1e6, 3),
-        "roofline": {
-            "bound": "hbm", "kernel": (meas.get("kernel_profiled") or kernel_name).replace("rdx::", ""),
-            "achieved": round(achieved, 2) if achieved is not None else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved is not None else None,
-            "traffic": meas["traffic"],
-            "traffic_detail": meas.get("traffic_detail"),
-            "avg_launch_ms": round(1e3 * trav_s / launches, 4),
-            "launches": launches,
-            "issue": meas["issue"],
-            # SURVEY 8(d) byte model, kept as a normalisation: what the REFERENCE's exhaustive, cache-less walk would have
-            # to read for the same rays.  No peak, no fraction: the product neither makes those visits nor misses the caches.
-            "reference_walk_bytes_per_launch": int(roof_bytes * steps / launches),
-            "reference_walk_equiv_GBps": round(ref_equiv, 2),
-            "note": "achieved = fabric bytes per launch (FETCH_SIZE + WRITE_SIZE, KiB, PMC child passes of this run; FETCH_SIZE at face "
-                    "value as calibrated for this kernel's 64-B / 48-B record gathers, see traffic_detail) / average "
-                    "launch duration (HIP events in the timed region).  The scene (BVH 25 MB) lives in L2 + Infinity Cache, so "
-                    "the kernel is bound by instruction issue, not by HBM: see `issue` and DESIGN.md section 5",
-        },
-        "roofline_frame": {"reference_walk_equiv_GBps": round(frame_bytes / (ms_per_step * 1e-3) / 1e9, 2) if world == 1 else None,
-                           "bytes_per_frame": int(frame_bytes)},
-        "stage_timing": "HIP events inside the timed region" if world == 1 else
-                        "HIP events on 3 extra untimed frames per rank (the timed region runs without per-stage events)",
-        "stage_ms_per_frame": {k[3:]: round(acc[k] / steps, 4) for k in ("ms_generate", "ms_extend", "ms_shade", "ms_sort", "ms_shadow", "ms_fused", "ms_path", "ms_accumulate", "ms_total")},
         "device": rd.Platform.device_name(),
     }
-    if also:
-        out["also"] = also
-    if tlas_blob is not None:
-        r = reference_on_gpu(scene, tlas_blob, ms_per_step)
-        if r:
-            out["reference_on_gpu"] = r
-    if world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(scene)
+    if full:
+        rays_extend_per_frame = (acc["primary"] + acc["bounce"]) / steps
+        bytes_extend_frame = algorithmic_bytes(visits["visit_top_nodes"][0], visits["visit_instances"][0],
+                                               visits["visit_bot_nodes"][0], visits["visit_triangles"][0], rays_extend_per_frame)
+        bytes_shadow_frame = algorithmic_bytes(visits["visit_top_nodes"][1], visits["visit_instances"][1],
+                                               visits["visit_bot_nodes"][1], visits["visit_triangles"][1], acc["shadow"] / steps)
+        kernel_name, roof_bytes, trav_s, launches = traversal_roofline(acc, visits, steps, args.depth)
+        ref_equiv = roof_bytes * steps / trav_s / 1e9 if trav_s > 0 else 0.0
+        pixels = args.width * args.height if world == 1 else None
+        frame_bytes = bytes_extend_frame + bytes_shadow_frame + 184 * acc["hits"] / steps + (20 * pixels if pixels else 0)
+        meas = {"traffic": None, "achieved": None, "issue": None}
+        if world == 1 and not args.no_pmc and not under_profiler():
+            meas = measured_roofline(kernel_name, trav_s, launches, option_args(args))
+        achieved = meas["achieved"]
+        out.update({
+            "roofline": {
+                "bound": "hbm", "kernel": (meas.get("kernel_profiled") or kernel_name).replace("rdx::", ""),
+                "achieved": round(achieved, 2) if achieved is not None else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5) if achieved is not None else None,
+                "traffic": meas["traffic"],
+                "traffic_detail": meas.get("traffic_detail"),
+                "avg_launch_ms": round(1e3 * trav_s / launches, 4),
+                "launches": launches,
+                "issue": meas["issue"],
+                # SURVEY 8(d) byte model, kept as a normalisation: what the REFERENCE's exhaustive, cache-less walk would have
+                # to read for the same rays.  No peak, no fraction: the product neither makes those visits nor misses the caches.
+                "reference_walk_bytes_per_launch": int(roof_bytes * steps / launches),
+                "reference_walk_equiv_GBps": round(ref_equiv, 2),
+                "note": "achieved = fabric bytes per launch (FETCH_SIZE + WRITE_SIZE, KiB, PMC child passes of this run; FETCH_SIZE at face "
+                        "value as calibrated for this kernel's 64-B / 48-B record gathers, see traffic_detail) / average "
+                        "launch duration (HIP events in the timed region).  The scene (BVH 25 MB) lives in L2 + Infinity Cache, so "
+                        "the kernel is bound by instruction issue, not by HBM: see `issue` and DESIGN.md section 5",
+            },
+            "roofline_frame": {"reference_walk_equiv_GBps": round(frame_bytes / (ms_per_step * 1e-3) / 1e9, 2) if world == 1 else None,
+                               "bytes_per_frame": int(frame_bytes)},
+            "stage_timing": "HIP events inside the timed region" if world == 1 else
+                            "HIP events on 3 extra untimed frames per rank (the timed region runs without per-stage events)",
+            "stage_ms_per_frame": {k[3:]: round(acc[k] / steps, 4) for k in ("ms_generate", "ms_extend", "ms_shade", "ms_sort", "ms_shadow", "ms_fused", "ms_path", "ms_accumulate", "ms_total")},
+        })
+        if also:
+            out["also"] = also
+        if tlas_blob is not None:
+            r = reference_on_gpu(scene, tlas_blob, ms_per_step)
+            if r:
+                out["reference_on_gpu"] = r
+        if world == 1 and not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_baseline(scene)
     print(json.dumps(out), flush=True)
 
 

@@ -6,6 +6,10 @@ ref_kat.npz        inputs -> outputs of the REAL reference device functions that
                    builtin (random_pcg3d, InverseMat4x4, MultiplyMat4Vec4, MultiplyMat4Mat4, D_GGX),
                    executed from the reference's samples/shader.cl compiled for x86
                    (oracle/Makefile -> oracle/_ref, oracle/ref_harness.c).
+ref_live_kat.npz   the same functions on the seeded inputs of test_oracle_matches_live_reference_if_present
+                   (random_pcg3d, InverseMat4x4), so that test has the reference's answers where oracle/_ref is absent.
+ref_shader_hash.json  FNV-1a-64 of the non-blank characters of the reference's samples/shader.cl (the stock program
+                   the runtime recognises, test_stock_shader_hash_matches_the_reference_text).
 ref_gensbt.txt     stdout of the reference's own tools/genSBT.py run on its samples/sbt.json (only
                    its two hard-coded author paths are redirected; its ./tmp.cl lands in a temp dir).
 oracle_kat.npz     outputs of the CPU oracle (oracle/rt_oracle.c) on small seeded cases: blob hashes,
@@ -68,6 +72,34 @@ def make_ref_kat():
     print("ref_kat.npz written")
 
 
+def make_ref_live_kat():
+    import oracle_bind as ob
+    R = ob.ref()
+    assert R is not None, "oracle/_ref is not built (run `make -C oracle`)"
+    rng = np.random.default_rng(3)                    # the test's own inputs, drawn in the test's order
+    pcg_in = rng.integers(0, 2**32, size=(4096, 3), dtype=np.uint64).astype(np.uint32)
+    pcg_out = np.zeros((4096, 3), np.float32)
+    R.ref_pcg3d(pcg_in.ctypes.data, pcg_out.ctypes.data, pcg_in.shape[0])
+    mats = rng.normal(size=(256, 16)).astype(np.float32)
+    inv_out = np.zeros((256, 16), np.float32)
+    inv_ok = np.zeros(256, np.int32)
+    for k in range(256):
+        row = mats[k].copy()
+        inv_ok[k] = R.ref_inverse_mat4(row.ctypes.data, inv_out[k].ctypes.data)
+    np.savez_compressed(os.path.join(HERE, "ref_live_kat.npz"), pcg_in=pcg_in, pcg_out=pcg_out, mats=mats, inv_out=inv_out, inv_ok=inv_ok)
+
+
+def make_ref_shader_hash():
+    import json
+    import re
+    h = 0xcbf29ce484222325
+    for c in re.sub(rb"\s+", b"", open(os.path.join(REF, "samples", "shader.cl"), "rb").read()):
+        h = ((h ^ c) * 0x100000001b3) & 0xffffffffffffffff
+    with open(os.path.join(HERE, "ref_shader_hash.json"), "w") as f:
+        json.dump({"file": "samples/shader.cl", "fnv1a64_nonblank": "0x%016x" % h}, f)
+        f.write("\n")
+
+
 def make_ref_gensbt():
     src = open(os.path.join(REF, "tools", "genSBT.py")).read()
     src = src.replace("/home/zekailin00/Desktop/ray-tracing/framework/samples/sbt.json", os.path.join(REF, "samples", "sbt.json"))
@@ -120,5 +152,7 @@ def make_oracle_kat():
 
 if __name__ == "__main__":
     make_ref_kat()
+    make_ref_live_kat()
+    make_ref_shader_hash()
     make_ref_gensbt()
     make_oracle_kat()

@@ -30,8 +30,10 @@ def fixture_program():
 @pytest.mark.skipif(not os.path.exists(CLANG), reason="ROCm clang is not installed")
 def test_fixture_program_compiles_in_both_modes(lib):
     """tests/golden/user_stages.cl against the product's own device library: as the stage kernel (record / replay traceRay,
-    the stage-mode get_global_id) and as a plain megakernel program"""
-    t = fixture_program()
+    the stage-mode get_global_id) and as a plain megakernel program.  The extra #define makes the text one no other test
+    compiles: librdx keeps the programs it built in this process and hands such a program back without compiling it, which
+    rdx_debug_jit_compiles does not count as a compile (the GPU tests build this fixture when they share the process)"""
+    t = fixture_program() + b"\n#define RDX_TEST_COMPILE_ONLY_PROBE 1\n"
     for stages in (1, 0):
         assert lib.rdx_debug_jit_compiles(t, len(t), b"gfx950", stages) == 0, lib.rdx_last_error().decode()
     bad = t.replace(b"payload->hit = true;", b"payload->hit = this is not OpenCL C;")

@@ -9,7 +9,7 @@ pass a SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIV
 pass b SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU
 pass c SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_INSTS_SALU SQ_INST_CYCLES_SALU SQ_INST_CYCLES_SMEM SQ_IFETCH SQ_INSTS_VALU SQ_WAVE_CYCLES
 pass d SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES
-pass e SQ_INST_LEVEL_LDS SQ_INSTS_LDS SQ_INSTS_LDS_LOAD SQ_INSTS_LDS_STORE SQ_INSTS_LDS_ATOMIC SQ_WAVE_CYCLES
+pass e SQ_INST_LEVEL_LDS SQ_INSTS_LDS SQ_INSTS_LDS_{LOAD,STORE,ATOMIC} SQ_WAVE_CYCLES
 pass f SQ_INST_LEVEL_SMEM SQ_INSTS_SMEM SQ_WAVE_CYCLES
 cd $R
 python3 - <<PY
