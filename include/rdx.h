@@ -71,7 +71,13 @@ size_t      rdx_buffer_size(rdx_buffer b);
  *      bytes).  write / read move the (width, height) top-left region of one layer, host rows tightly packed, like the
  *      reference's clEnqueue{Write,Read}Image(origin (0,0,layer), region (width,height,1)).  addressingMode / filterMode take
  *      the CL_ADDRESS_* / CL_FILTER_* values the reference's RD_ADDRESS_* / RD_FILTER_* macros expand to.  Bound to descriptor
- *      slots 11 and 12; sampled by the stock closest-hit shader only when option "textures" is 1 (see rdx_set_option). */
+ *      slots 11 and 12; sampled by the stock closest-hit shader only when option "textures" is 1 (see rdx_set_option).  A user
+ *      shader program (rdx_shader_module_create) reads them whatever that option says, through read_imageui(image2d_array_t,
+ *      sampler_t, float4), read_imageui(image2d_array_t, int4) and get_image_width / height / array_size / dim, in the
+ *      megakernel and in stage mode, with the stock shader's sampler.  A NULL slot 11 reads as an empty image (reads 0,
+ *      queries 0), a NULL slot 12 as no sampler (sampled reads 0).  Other image builtins (write_image*, read_imagef /
+ *      read_imagei, inline `const sampler_t` constants) would need a hardware image descriptor: such a program is refused at
+ *      module creation, naming the builtin. */
 rdx_buffer  rdx_image_array_create(uint32_t width, uint32_t height, uint32_t layers);
 int         rdx_image_write(rdx_buffer imageArray, uint32_t width, uint32_t height, size_t layer, const void* rgba8);
 int         rdx_image_read(rdx_buffer imageArray, uint32_t width, uint32_t height, size_t layer, void* rgba8);
@@ -142,7 +148,8 @@ int         rdx_shader_include_path(const char* path);
 int         rdx_bind_pipeline(rdx_shader raygen_module);
 /* handles[i] binds to parameter i of the raygen kernel (samples/shader.cl:175-190):
  * 0 RTProp, 1 imageScratch, 2 image, 3 camData, 4 scene, 5 meshInfo, 6 vertex, 7 index, 8 uv,
- * 9 normal, 10 material, 11 textureArray (may be NULL), 12 sampler (may be NULL), 13 TLAS. */
+ * 9 normal, 10 material, 11 textureArray (may be NULL), 12 sampler (may be NULL), 13 TLAS.  A user program's image2d_array_t /
+ * sampler_t parameters receive the library's views of slots 11 / 12 (never a null descriptor; a NULL slot is an empty view). */
 int         rdx_bind_descriptor_set(void* const* handles, uint32_t n);
 /* the three SBT indices are accepted and ignored, exactly like radiance.cpp:242-259 */
 int         rdx_trace_rays(uint32_t raygenGroupIndex, uint32_t missGroupIndex, uint32_t hitGroupIndex,
@@ -200,7 +207,8 @@ int         rdx_set_profiling(int on);
  * path streams are not moved and no result depends on it), "textures" (0 (default) / 1.  The live reference shader has every texture read commented out (`uint4 tex =
  * 0.0f;//read_imageui(...)`, samples/shader.cl:379,411,421,445), so a material with a texture index renders with texel 0; that
  * is what 0 reproduces, bit for bit.  1 performs the commented-out read -- coord (uv.x, 1 - uv.y, texIdx), as the reference's
- * older shader2.cl:255-265 does live -- from the image array in slot 11 through the sampler in slot 12), "cull" (pool kernel: -1 (default) = automatic, 1 / 0 = on / off: closest-hit rays skip subtrees the ray enters
+ * older shader2.cl:255-265 does live -- from the image array in slot 11 through the sampler in slot 12.  The option concerns the
+ * stock shader only: a user program's own read_imageui calls always read slots 11 / 12), "cull" (pool kernel: -1 (default) = automatic, 1 / 0 = on / off: closest-hit rays skip subtrees the ray enters
  * beyond the best t found so far, every ray skips leaves whose box it misses -- only where a per-node normal cone proves the
  * reference's fp32 intersection test well conditioned for that ray, with margins that cover its error: the result is the
  * reference's exhaustive walk's, docs/CULLED_WALK.md has the proof; automatic = on for scenes with at least 1 M inner BVH

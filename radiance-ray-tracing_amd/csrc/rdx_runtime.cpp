@@ -173,6 +173,11 @@ struct Context {
     int cull = -1;                          // pool engine: culled walk (option "cull"): 1 on, 0 off, -1 = on for scenes of >= 1 M inner nodes
     int textures = 0;                       // option "textures": 1 = the stock shader samples the bound image array
     std::vector<std::unique_ptr<rdx_sampler_s>> samplers;
+    // user programs: the views their image2d_array_t / sampler_t parameters point to (texture.h TexImageView at 0, TexSamplerView
+    // at 32), made from slots 11 / 12 and rewritten when what they describe changes (user_tex_views)
+    void* texViews = nullptr;
+    uint8_t texViewsHost[48] = {};
+    bool texViewsValid = false;
     std::string shaderInclude;              // -I for user shader programs (rdx_shader_include_path; the reference's SHADER_LIB_PATH)
     int userLocalSize = 64;                 // option "user_shader_local_size": work-group size of a user program's launch (the reference uses 1)
     int sortRays = -1;                      // option "sort": per-bounce ray sort: 1 on, 0 off, -1 automatic
@@ -1000,6 +1005,50 @@ int camera_args(const PhysicalCamera& cam, CameraArgs& C)
     return 0;
 }
 
+// the sampler `h` (slot 12) as TexView::flags bits: addressing mode and filter (no TEX_ENABLED); false if `h` is not a sampler
+bool sampler_bits(const void* h, uint32_t& bits)
+{
+    for (auto& sm : g.samplers)
+        if (sm.get() == h) {
+            const uint32_t mode = sm->addressing == 0x1131 ? TEX_ADDR_CLAMP_TO_EDGE : sm->addressing == 0x1132 ? TEX_ADDR_CLAMP
+                                : sm->addressing == 0x1134 ? TEX_ADDR_MIRRORED : TEX_ADDR_REPEAT;
+            bits = (sm->filter == 0x1141 ? TEX_LINEAR : 0u) | (mode << TEX_ADDR_SHIFT);
+            return true;
+        }
+    return false;
+}
+
+// device addresses of the image and sampler views a user program's entry point passes for its image2d_array_t / sampler_t
+// parameters (csrc/user_texture.hip reads them).  Never null: a NULL slot 11 (or a buffer that is not an image array) is a zero
+// image view, a NULL slot 12 (or no sampler) a zero sampler view -- reads return (0, 0, 0, 0), queries 0.  Independent of option
+// "textures", which switches the stock shader's reads only.  The block is rewritten, in stream order, when its contents change:
+// another descriptor set, image or sampler.
+int user_tex_views(void*& image, void*& sampler)
+{
+    TexImageView iv{nullptr, 0, 0, 0, 0};
+    TexSamplerView sv{0, {0, 0, 0}};
+    if (g.slots[11] && known_buffer(g.slots[11])) {
+        const auto* img = static_cast<const rdx_buffer_s*>(g.slots[11]);
+        if (img->imgW && img->imgH && img->imgLayers) iv = TexImageView{static_cast<const uint8_t*>(dp(img)), img->imgW, img->imgH, img->imgLayers, 0};
+    }
+    uint32_t bits = 0;
+    if (g.slots[12] && sampler_bits(g.slots[12], bits)) sv.flags = TEX_ENABLED | bits;
+    uint8_t host[48] = {};
+    static_assert(sizeof(TexImageView) <= 32 && sizeof(TexSamplerView) <= 16, "view block layout");
+    std::memcpy(host, &iv, sizeof iv);
+    std::memcpy(host + 32, &sv, sizeof sv);
+    if (!g.texViews) { HIP_OK(hipMalloc(&g.texViews, sizeof host)); g.texViewsValid = false; }
+    if (!g.texViewsValid || std::memcmp(host, g.texViewsHost, sizeof host)) {
+        std::memcpy(g.texViewsHost, host, sizeof host);
+        HIP_OK(hipMemcpyAsync(g.texViews, g.texViewsHost, sizeof host, hipMemcpyHostToDevice, g.stream));
+        HIP_OK(hipStreamSynchronize(g.stream));          // (the host copy may change again before a later call)
+        g.texViewsValid = true;
+    }
+    image = g.texViews;
+    sampler = static_cast<uint8_t*>(g.texViews) + 32;
+    return 0;
+}
+
 int scene_args(SceneArgs& sc)
 {
     for (int i : {4, 5, 7, 8, 9, 10})
@@ -1018,14 +1067,9 @@ int scene_args(SceneArgs& sc)
     if (g.textures && g.slots[11] && known_buffer(g.slots[11])) {
         const auto* img = static_cast<const rdx_buffer_s*>(g.slots[11]);
         if (img->imgW && img->imgH && img->imgLayers) {
-            uint32_t mode = TEX_ADDR_REPEAT, linear = 0;           // no sampler bound: repeat + nearest
-            for (auto& sm : g.samplers)
-                if (sm.get() == g.slots[12]) {
-                    mode = sm->addressing == 0x1131 ? TEX_ADDR_CLAMP_TO_EDGE : sm->addressing == 0x1132 ? TEX_ADDR_CLAMP
-                         : sm->addressing == 0x1134 ? TEX_ADDR_MIRRORED : TEX_ADDR_REPEAT;
-                    linear = sm->filter == 0x1141 ? TEX_LINEAR : 0u;
-                }
-            sc.tex = TexView{static_cast<const uint8_t*>(dp(img)), img->imgW, img->imgH, img->imgLayers, TEX_ENABLED | linear | (mode << TEX_ADDR_SHIFT)};
+            uint32_t bits = TEX_ADDR_REPEAT << TEX_ADDR_SHIFT;     // no sampler bound: repeat + nearest
+            (void)sampler_bits(g.slots[12], bits);
+            sc.tex = TexView{static_cast<const uint8_t*>(dp(img)), img->imgW, img->imgH, img->imgLayers, TEX_ENABLED | bits};
         }
     }
     return 0;
@@ -1124,6 +1168,8 @@ static void release_device_state()
     }
     if (g.sampleColor) HIP_IGN(hipFree(g.sampleColor));
     if (g.ownedPixels) HIP_IGN(hipFree(g.ownedPixels));
+    if (g.texViews) HIP_IGN(hipFree(g.texViews));
+    g.texViews = nullptr; g.texViewsValid = false;
     for (void* p : g.gatherStage) if (p) HIP_IGN(hipFree(p));
     if (g.hStatus) HIP_IGN(hipHostFree(g.hStatus));
     g.hStatus = nullptr; g.dStatus = nullptr;
@@ -1786,6 +1832,30 @@ extern "C" int rdx_debug_jit_compiles(const char* code, uint32_t size, const cha
     return fail_str(err.empty() ? std::string("rdx_debug_jit_compiles: unexpected state") : err);
 }
 
+// The same, and the code object is written to `out_path` (an absolute path) for inspection -- its instructions, its kernels'
+// resources -- instead of being loaded.  Programs this process already built are compiled again.
+extern "C" int rdx_debug_jit_compile_to(const char* code, uint32_t size, const char* arch, int stages, const char* out_path)
+{
+    if (!code || !arch || !out_path || out_path[0] != '/') return fail("rdx_debug_jit_compile_to: null argument or a relative path");
+    std::string text(code, size), err;
+    if (stages) { text = strip_comments(text); blank_bodies(text, {"raygen", "generateRay"}); }
+    setenv("RDX_JIT_COMPILE_ONLY", out_path, 1);
+    UserProgram* p = compile_user_shader(text, g0.shaderInclude, arch, stages != 0, err);
+    unsetenv("RDX_JIT_COMPILE_ONLY");
+    (void)p;
+    if (err == "compiled") return 0;
+    return fail_str(err.empty() ? std::string("rdx_debug_jit_compile_to: unexpected state") : err);
+}
+
+// The run-time compiler's cache key of a program (megakernel or stage text as given): abi < 0 = this build's RDX_JIT_ABI,
+// bitcode null = the library's own texture bitcode, else that file.
+extern "C" unsigned long long rdx_debug_jit_key(const char* code, uint32_t size, const char* arch, int stages, int abi, const char* bitcode)
+{
+    if (!code || !arch) return 0;
+    return (unsigned long long)user_shader_key(std::string(code, size), g0.shaderInclude, arch, stages != 0, abi < 0 ? RDX_JIT_ABI : abi,
+                                               bitcode ? std::string(bitcode) : std::string());
+}
+
 extern "C" int rdx_shader_include_path(const char* path)
 {
     g0.shaderInclude = path ? path : "";
@@ -1988,15 +2058,16 @@ static int trace_rays_device(uint32_t width, uint32_t height)
     if (nPix == 0) return 0;
     if (g.pipeline->program && !g.pipeline->program->stages) {
         // a user's own raygen program: the megakernel, one work-item per pixel, bound by position like clSetKernelArg
-        // (radiance.cpp:231-259); slots 11 / 12 (texture array, sampler) are passed as null descriptors
+        // (radiance.cpp:231-259); slots 11 / 12 (texture array, sampler) are passed as the library's views of them (user_tex_views)
         if (nPix > 0xffffffffull) return fail("TraceRays: too many pixels");
-        void* ptrs[12];
+        void* ptrs[14];
         const int slotOf[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 13};
         for (int i = 0; i < 12; ++i) {
             void* h = g.slots[slotOf[i]];
             if (!h || !known_buffer(h)) return fail("descriptor slot %d is not a buffer", slotOf[i]);
             ptrs[i] = dp(static_cast<rdx_buffer_s*>(h));
         }
+        if (user_tex_views(ptrs[12], ptrs[13])) return -1;
         std::memset(&g.stats, 0, sizeof g.stats);
         g.stats.pixels = nPix;
         HIP_OK(hipEventRecord(g.evA, g.stream));
@@ -2111,15 +2182,17 @@ static int trace_rays_device(uint32_t width, uint32_t height)
             else launch_extend(g.stream, av, ps, G.dCounts, n0, tmin, tmax, nullptr, G.dCounts + 64);
             void* slotPtr[14];
             for (int i = 0; i < 14; ++i) slotPtr[i] = (g.slots[i] && known_buffer(g.slots[i])) ? dp(static_cast<rdx_buffer_s*>(g.slots[i])) : nullptr;
+            void *texImage = nullptr, *texSampler = nullptr;
+            if (user_tex_views(texImage, texSampler)) return -1;
             for (uint32_t d = 0; d < maxDepth; ++d) {
                 for (uint32_t pass = 0; pass < 2; ++pass) {
                     const uint32_t scalars[6] = {pass, d, maxDepth, P, sampleBase, rt.debug};
-                    void* ptrs[31] = {G.dCounts + d, G.dCounts + d + 1, G.dCounts + 200,
+                    void* ptrs[33] = {G.dCounts + d, G.dCounts + d + 1, G.dCounts + 200,
                                       slotPtr[3], slotPtr[4], slotPtr[5], slotPtr[6], slotPtr[7], slotPtr[8], slotPtr[9], slotPtr[10], slotPtr[13],
                                       const_cast<DInst*>(av.insts),
                                       ps.rayO, ps.rayD, ps.thr, ps.col, ps.hitA, ps.hitInst, ps.payC, ps.payF,
                                       ps.shO, ps.shD, ps.shHit,
-                                      ps.nRayO, ps.nRayD, ps.nThr, ps.nCol, ps.nPayC, ps.nPayF, ps.sampleColor};
+                                      ps.nRayO, ps.nRayD, ps.nThr, ps.nCol, ps.nPayC, ps.nPayF, ps.sampleColor, texImage, texSampler};
                     std::string err;
                     if (launch_user_stage(g.pipeline->program, g.stream, scalars, ptrs, n0, err)) return fail_str(err);
                     if (pass == 0) launch_shadow_user(g.stream, av, ps, G.dCounts + d, n0, tmin, tmax, G.dCounts + 128 + d);
