@@ -19,6 +19,16 @@ refgpu_kat.npz        intersectAABB, intersectTriangle, microfacetBRDF + sampleM
 refgpu_<scene>.npz    per small scene (tests/golden_cases.py): primary rays of generateRay, HitData of a 4096-ray batch
                       (closest hit: sbt 1; any hit: sbt 2), `material` payloads on captured hits, imageScratch + RGBA8
                       after TraceRays call 1 and 2 (progressive mean)
+
+Second entry point (leaves the files above alone):
+
+    python tests/golden/make_golden_gpu.py rayedges [DIR]     # on the MI355X; writes DIR/refgpu_rayedges.npz
+    cp DIR/refgpu_rayedges.npz tests/golden/                   # (DIR defaults to the folder the files above are written to, OUT)
+
+refgpu_rayedges.npz   the reference's intersectTop beyond the stock ray interval and unit directions: every cell of
+                      tests/ray_edge_cases.py (scene x family x interval), closest hit (sbt 1: full HitData) and any hit
+                      (sbt 2: flags), plus the inputs that depend on the reference's own answers.  Layout: ray_edge_cases.py
+                      "fixture layout".  The archive is written with fixed time stamps: a second run reproduces it byte for byte.
 """
 import os
 import sys
@@ -90,5 +100,49 @@ def main():
               (name, o.shape[0], int(h1["hit"].sum()), int(h2["hit"].sum()), int(mh["hit"].sum())), flush=True)
 
 
+def save_npz_reproducibly(path, arrays):
+    """np.savez_compressed with the archive's time stamps pinned (numpy stamps members with the wall clock)"""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[k]), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def rayedges(out_dir=OUT):
+    import ray_edge_cases as rec
+    os.makedirs(out_dir, exist_ok=True)
+    ref = rg.RefGpu("p")
+    out = {}
+    for name in rec.SCENES:
+        s = rec.scene(scenes, name)
+        blob = gc.scene_blob(rd, s)
+        rs = rg.RefScene(ref, s, blob)
+        base = None
+        if name in rec.GOLDEN:                  # the committed golden batch of the scene (itself the reference's output)
+            G = np.load(os.path.join(HERE, "refgpu_%s.npz" % name))
+            assert np.array_equal(G["blob_sha256"], gc.sha(blob))
+            base = (G["ray_o"], G["ray_d"])
+        cases = rec.Cases(scenes, name, base, None, rs.trace)
+        cells = cases.cells()
+        results = [(rs.trace(c.o, c.d, c.tmin, c.tmax, 1), rs.trace(c.o, c.d, c.tmin, c.tmax, 2)) for c in cells]
+        out.update(rec.pack_scene(name, gc.sha(blob), cases.params, results))
+        print("%s: %d cells, %d rays, %d closest hits, %d distinct records" % (name, len(cells), sum(c.n for c in cells),
+              sum(int((r["hit"] == 1).sum()) for r, _ in results), out[name + "/recs"].shape[1]), flush=True)
+    # rays of family F the live reference could not be run on: none -- every NaN comparison of its walk is false, it terminates
+    out["notes"] = np.array([], dtype="U1")
+    path = os.path.join(out_dir, "refgpu_rayedges.npz")
+    save_npz_reproducibly(path, out)
+    print("refgpu_rayedges.npz: %d bytes" % os.path.getsize(path), flush=True)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["rayedges"]:
+        rayedges(*[os.path.abspath(a) for a in sys.argv[2:3]])
+    else:
+        main()

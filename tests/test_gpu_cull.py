@@ -60,8 +60,9 @@ def _mismatches(want, got, closest):
     return bad
 
 
-def check_batches(rd, dev, ref, batches, tag):
-    """every batch x {closest, any hit} x {cull 1, cull 0} against the live reference (if built) and the reference-order kernel"""
+def check_batches(rd, dev, ref, batches, tag, tmin=0.001, tmax=1000.0):
+    """every batch x {closest, any hit} x {cull 1, cull 0} against the live reference (if built) and the reference-order kernel,
+    under the ray interval (tmin, tmax)"""
     tl = None
     if ref is not None:
         blob = rd.ReadBuffer(dev.plt, dev.topAccelStruct, dev.topAccelStruct.size).tobytes()
@@ -69,25 +70,27 @@ def check_batches(rd, dev, ref, batches, tag):
     total = 0
     for name, (o, d) in batches.items():
         o = np.ascontiguousarray(o, F); d = np.ascontiguousarray(d, F)
+        # (this filter stays: the generators below can overflow to inf / NaN or produce a zero direction by accident.  Non-finite and
+        # zero-direction rays are compared ON PURPOSE, under their own precautions, by tests/test_gpu_ray_edges.py family F.)
         ok = np.isfinite(o).all(1) & np.isfinite(d).all(1) & (np.abs(d).sum(1) > 0)
         o, d = o[ok], d[ok]
         for rec in (1, 2):
-            want = rd.TraceBatch(dev.topAccelStruct, o, d, 0.001, 1000.0, rec, reference_order=True)
+            want = rd.TraceBatch(dev.topAccelStruct, o, d, tmin, tmax, rec, reference_order=True)
             if tl is not None:
-                live = ref.trace(tl, o, d, 0.001, 1000.0, rec)
+                live = ref.trace(tl, o, d, tmin, tmax, rec)
                 bad = _mismatches(live, want, rec == 1)
                 assert not bad.any(), "%s / %s rec %d: reference-order kernel differs from the live reference on %d rays" % (tag, name, rec, int(bad.sum()))
             for cull in (1, 0):
                 rd.SetOption("kernel", 3); rd.SetOption("cull", cull)
                 try:
-                    got = rd.TraceBatch(dev.topAccelStruct, o, d, 0.001, 1000.0, rec)
+                    got = rd.TraceBatch(dev.topAccelStruct, o, d, tmin, tmax, rec)
                 finally:
                     rd.SetOption("cull", -1)
                 bad = _mismatches(want, got, rec == 1)
                 if bad.any():
                     i = int(np.flatnonzero(bad)[0])
-                    raise AssertionError("%s / %s rec %d cull %d: %d of %d rays differ; first: o=%r d=%r want t=%r prim=%d inst=%d hit=%d, got t=%r prim=%d inst=%d hit=%d"
-                                         % (tag, name, rec, cull, int(bad.sum()), o.shape[0], o[i].tolist(), d[i].tolist(),
+                    raise AssertionError("%s / %s rec %d cull %d tmin %r tmax %r: %d of %d rays differ; first: o=%r d=%r want t=%r prim=%d inst=%d hit=%d, got t=%r prim=%d inst=%d hit=%d"
+                                         % (tag, name, rec, cull, tmin, tmax, int(bad.sum()), o.shape[0], o[i].tolist(), d[i].tolist(),
                                             float(want["distance"][i]), int(want["primitiveIndex"][i]), int(want["instanceIndex"][i]), int(want["hit"][i]),
                                             float(got["distance"][i]), int(got["primitiveIndex"][i]), int(got["instanceIndex"][i]), int(got["hit"][i])))
             total += o.shape[0]
@@ -198,6 +201,9 @@ def test_slivers_identical_to_reference(mods, ref, seed):
     batches = {"aimed at slivers": (o, aimed), "along the long edge": (tgt, along), "far origin": (far, _unit(tgt - far)),
                "sliver to sliver": (a, _unit(tgt - a))}
     assert check_batches(rd, dev, ref, batches, "slivers seed %d" % seed) > 4 * n
+    if seed == 1:      # the same batches with nothing cut off, and with a tmax that cuts through the slivers (they span |x| < 7, origins |o| < 9)
+        assert check_batches(rd, dev, ref, batches, "slivers seed %d" % seed, 0.0, float(np.finfo(F).max)) > 4 * n
+        assert check_batches(rd, dev, ref, batches, "slivers seed %d" % seed, 0.001, 6.0) > 4 * n
 
 
 @pytest.mark.parametrize("seed,gap", [(1, 1e-5), (2, 1e-4), (3, 1e-3), (4, 0.0)])
@@ -227,6 +233,9 @@ def test_tilted_coplanar_stacks_identical_to_reference(mods, ref, seed, gap):
                "along edges from vertices": (vert, edge), "aimed": (o, _unit(b - o)), "far origin": (far, _unit(b - far)),
                "far origin, in plane": (grazing_far, inplane)}
     assert check_batches(rd, dev, ref, batches, "stack seed %d gap %g" % (seed, gap)) > 7 * n
+    if seed == 1:      # ... with nothing cut off, and with an interval that cuts the stack: its planes are 6 wide, in-plane rays cross them
+        assert check_batches(rd, dev, ref, batches, "stack seed %d gap %g" % (seed, gap), 0.0, float(np.finfo(F).max)) > 7 * n
+        assert check_batches(rd, dev, ref, batches, "stack seed %d gap %g" % (seed, gap), 1.5, 4.0) > 7 * n
 
 
 def test_cull_stress_families_on_the_sponza_class_scene(mods, ref):

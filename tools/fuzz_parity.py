@@ -82,27 +82,37 @@ def with_surface_rays(rng, o, d, hits):
         o = np.concatenate([o, hp.astype(F)]); d = np.concatenate([d, d2])
     return np.ascontiguousarray(o, F), np.ascontiguousarray(d, F)
 
-def run(nseeds, first_seed=0, verbose=True):
+def run(nseeds, first_seed=0, verbose=True, intervals=None, scales=None):
+    """intervals: [(tmin, tmax)] to trace under (default: the stock interval only); scales: factors the directions are multiplied
+    by, each run under every interval divided by the factor (t scales with 1 / |d|), in addition to the unscaled rays"""
     bad = 0
     fields = ("distance", "primitiveIndex", "instanceIndex", "instanceCustomIndex", "barycentric", "hitPoint", "transform")
+    ivs = [(0.001, 1000.0)] if intervals is None else list(intervals)
+    variants = [(F(a), F(b), F(1.0)) for a, b in ivs]
+    with np.errstate(over="ignore"):
+        variants += [(F(a) / F(sc), F(b) / F(sc), F(sc)) for sc in (scales or ()) for a, b in ivs]
     for seed in range(first_seed, first_seed + nseeds):
-        s, o, d, rng = random_case(seed)
+        s, o, d0, rng = random_case(seed)
         dev = scenes.DeviceScene(s)
-        ref = rd.TraceBatch(dev.topAccelStruct, o, d, reference_order=True)
-        o, d = with_surface_rays(rng, o, d, ref)
-        for rec in (1, 2):
-            ref = rd.TraceBatch(dev.topAccelStruct, o, d, 0.001, 1000.0, rec, reference_order=True)
-            h = ref["hit"] == 1
-            for kernel, cull, quad in ((3, 1, 1), (3, 0, 1), (3, 0, 0), (2, 0, 1), (1, 0, 1)):      # (3, 0, 1): the quad-record walk
-                rd.SetOption("kernel", kernel); rd.SetOption("cull", cull); rd.SetOption("quad", quad)
-                got = rd.TraceBatch(dev.topAccelStruct, o, d, 0.001, 1000.0, rec)
-                rd.SetOption("kernel", 3); rd.SetOption("cull", -1); rd.SetOption("quad", 1)
-                ok = np.array_equal(ref["hit"], got["hit"])
-                if ok and rec == 1:
-                    ok = all(np.array_equal(ref[f][h].view(np.uint8), got[f][h].view(np.uint8)) for f in fields)
-                if not ok:
-                    bad += 1
-                    print("MISMATCH seed %d rec %d kernel %d cull %d quad %d (%d instances, %d rays, %d hits)" % (seed, rec, kernel, cull, quad, len(s.instances), o.shape[0], int(h.sum())), flush=True)
+        ref = rd.TraceBatch(dev.topAccelStruct, o, d0, reference_order=True)
+        o, d0 = with_surface_rays(rng, o, d0, ref)
+        for tmin, tmax, sc in variants:
+            d = d0 if sc == 1.0 else np.ascontiguousarray(d0 * sc, F)
+            for rec in (1, 2):
+                ref = rd.TraceBatch(dev.topAccelStruct, o, d, float(tmin), float(tmax), rec, reference_order=True)
+                h = ref["hit"] == 1
+                for kernel, cull, quad in ((3, 1, 1), (3, 0, 1), (3, 0, 0), (2, 0, 1), (1, 0, 1)):      # (3, 0, 1): the quad-record walk
+                    rd.SetOption("kernel", kernel); rd.SetOption("cull", cull); rd.SetOption("quad", quad)
+                    try:
+                        got = rd.TraceBatch(dev.topAccelStruct, o, d, float(tmin), float(tmax), rec)
+                    finally:
+                        rd.SetOption("kernel", 3); rd.SetOption("cull", -1); rd.SetOption("quad", 1)
+                    ok = np.array_equal(ref["hit"], got["hit"])
+                    if ok and rec == 1:
+                        ok = all(np.array_equal(ref[f][h].view(np.uint8), got[f][h].view(np.uint8)) for f in fields)
+                    if not ok:
+                        bad += 1
+                        print("MISMATCH seed %d rec %d kernel %d cull %d quad %d tmin %r tmax %r scale %r (%d instances, %d rays, %d hits)" % (seed, rec, kernel, cull, quad, float(tmin), float(tmax), float(sc), len(s.instances), o.shape[0], int(h.sum())), flush=True)
         if verbose and seed % 10 == 9:
             print("seed %d done, %d instances, %d rays, %d hits, mismatches so far %d" % (seed, len(s.instances), o.shape[0], int(h.sum()), bad), flush=True)
     return bad
