@@ -261,6 +261,37 @@ int         rdx_generate_batch(const uint32_t* pixels, const uint32_t* rand_in3,
                                float* origins_xyz, float* dirs_xyz);
 int         rdx_pcg3d_batch(const uint32_t* in3, float* out3, uint32_t n);
 
+/* Scalars of the traversal layout derived from a TLAS blob (csrc/accel_layout.h): what the kernels' LDS is sized from and
+ * what picks the engine.  Flags are 0 / 1. */
+typedef struct rdx_accel_scalars {
+    uint32_t stackNeed;                  /* per-lane kernels (reference order: left child followed, right child pushed) */
+    uint32_t coopNeed;                   /* wave-cooperative kernel (leaf children are never pushed, smaller subtree first) */
+    uint32_t topNeed, blasNeed;          /* its two parts: top-level entries of one ray / entries inside one BLAS (pool engine) */
+    uint32_t blasNeedAny;                /* BLAS stack need of the pool engine when the push order depends on the ray (culled walk) */
+    uint32_t quadNeed, quadUnifiedNeed;  /* pool-stack need of the quad walk inside one BLAS / from the unified root */
+    uint32_t unifiedNeed, unifiedRoot;   /* pool engine: one tree over top level + instances + BLASes, root 0 = not built */
+    uint32_t topFlat, topFlatNeed;       /* pool engine: number of top-level nodes if they are few enough (<= 64) to be evaluated
+                                          * all at once per ray instead of walked, and the words per lane of the pending-instance bitmap */
+    uint32_t nWide;                      /* wide records: inner BLAS nodes of the scene plus the unified tree's (sizes the automatic
+                                          * choice of the culled walk) */
+    uint32_t nInst;
+    uint32_t groupCount;                 /* instances in the shared-transform group */
+    uint32_t leafRoots;                  /* flag: some instance's BLAS is a single leaf of <= 8 triangles */
+    uint32_t sbtOffsets;                 /* flag: reference-order kernel only (an instance's SBT offset needs the reference's visiting
+                                          * order, or a leaf has more triangles than a wide record counts) */
+    uint32_t groupIdentity;              /* flag: the group's transform is the identity: root tests in the flat top-level step */
+    uint32_t coopOK;                     /* flag: the scene fits the packed words of the cooperative engines (the runtime also
+                                          * requires that their LDS footprint fits) */
+    float    sceneLo[3], sceneHi[3];     /* box of the top-level root (per-bounce ray sort grid) */
+} rdx_accel_scalars;
+/* Test seam: derives the layout of `blob` on the host under options "quad" / "cull" (-1, 0, 1 as in rdx_set_option).  Needs no
+ * device and no initialised library.  The eight derived arrays are, in this order: top-level nodes, their copy ordered for the
+ * cooperative kernel, instances, BLAS nodes, triangles, wide records, quad records, group bitmap (csrc/rdx_types.h layouts).
+ * `bytes` (optional, 8 entries) receives their sizes in bytes.  `arrays` (optional, 8 entries, needs `bytes`): every non-null
+ * entry receives that array; the caller states its capacity in bytes[i], from a size query made before. */
+int         rdx_debug_accel_layout(const void* blob, size_t size, int quad, int cull, rdx_accel_scalars* scalars,
+                                   void* const* arrays, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

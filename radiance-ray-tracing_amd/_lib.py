@@ -56,6 +56,13 @@ class rdx_payload(C.Structure):
                 ("nextRayOrigin", C.c_float * 3), ("nextRayDirection", C.c_float * 3)]
 
 
+class rdx_accel_scalars(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in (
+        "stackNeed", "coopNeed", "topNeed", "blasNeed", "blasNeedAny", "quadNeed", "quadUnifiedNeed", "unifiedNeed", "unifiedRoot",
+        "topFlat", "topFlatNeed", "nWide", "nInst", "groupCount", "leafRoots", "sbtOffsets", "groupIdentity", "coopOK")] + [
+        ("sceneLo", C.c_float * 3), ("sceneHi", C.c_float * 3)]
+
+
 # name -> (restype, argtypes); must list every symbol of include/rdx.h (tests check this)
 SIGNATURES = {
     "rdx_init": (C.c_int, [C.c_int]),
@@ -104,6 +111,8 @@ SIGNATURES = {
     "rdx_material_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rdx_generate_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rdx_pcg3d_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rdx_debug_accel_layout": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(rdx_accel_scalars), C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_size_t)]),
     "rdx_obj_load": (C.c_int, [C.c_char_p, C.POINTER(rdx_obj_scene)]),
     "rdx_obj_free": (None, [C.POINTER(rdx_obj_scene)]),
 }

@@ -18,7 +18,7 @@ struct AccelView {                 // derived traversal layout (see rdx_types.h)
     const DTri*  tris;
     const DWide* wide;             // wide BLAS nodes (production kernels)
     uint32_t stackNeed;            // worst-case stack entries of an exhaustive DFS (per-lane kernels)
-    uint32_t coopNeed;             // the same for the wave-cooperative kernel (see derive_accel)
+    uint32_t coopNeed;             // the same for the wave-cooperative kernel (see accel_layout.cpp)
     uint32_t topNeed, blasNeed;    // its top-level / per-BLAS parts (pool engine: private top-level stacks + shared node pool)
     uint32_t leafRoots;            // pool engine: the scene has single-leaf BLASes handled in the flat top-level step (needs topFlat)
     uint32_t topFlat;              // pool engine: > 0 = number of top-level nodes, evaluated all at once per ray (<= 64 nodes)
@@ -26,18 +26,14 @@ struct AccelView {                 // derived traversal layout (see rdx_types.h)
     uint32_t* status;              // device-visible status word (pinned host memory): bit 0 = a traversal wave hit its iteration bound
     uint32_t cull;                 // pool engine: culled walk (best-t culling of closest-hit rays, leaf-box test; kernels.hip)
     uint32_t kernel;               // 2 = wave-cooperative (default), 3 = wave-cooperative with a shared node pool, 1 = per-lane wide, 0 = reference order
-    uint32_t groupCount;           // pool engine: instances in the shared-transform group (rdx_runtime.cpp derive_accel), 0 = none
+    uint32_t groupCount;           // pool engine: instances in the shared-transform group (accel_layout.cpp), 0 = none
     const uint32_t* groupBits;     // ... and their slots as a bitmap of 9 words in device memory (flat top level only: <= 256 instances)
-    uint32_t unifiedRoot;          // pool engine: > 0 = wide index of the super-root of the unified tree (derive_accel): rays start there
+    uint32_t unifiedRoot;          // pool engine: > 0 = wide index of the super-root of the unified tree (accel_layout.cpp): rays start there
     uint32_t quadWaves;            // ... its kernels' waves per SIMD: 6, or 7 for full-size frames (kernels.hip k_*_pool_q)
     const DQuad* quad;             // pool engine, exhaustive walk: two tree levels per record (rdx_types.h); null = walk the DWide records
 };
 
-// limits of the cooperative engines' packed words, shared by the kernels (traverse_coop.h) and the host's fallback rule
-constexpr uint32_t RDX_COOP_MAX_TRI_SLOTS = 1u << 25;    // queue entry: lane << 26 | parity << 25 | absolute triangle slot
-constexpr uint32_t RDX_COOP_MAX_WIDE = 1u << 26;         // pool item: lane << 26 | wide-node index
-constexpr uint32_t RDX_COOP_MAX_INSTANCES = 1u << 10;    // key: instance slot << 22 | BLAS-local triangle slot
-constexpr uint32_t RDX_COOP_MAX_BLAS_TRIS = 1u << 22;
+// (the limits of the cooperative engines' packed words, RDX_COOP_MAX_*, are in rdx_types.h)
 constexpr uint32_t RDX_LDS_WORDS_PER_WAVE_MAX = 16384u;  // 64 KB per workgroup of one wave
 
 struct SceneArgs {                 // descriptor slots 4-12 (samples/shader.cl:175-190)

@@ -198,7 +198,7 @@ __device__ __forceinline__ bool slab_fast(const RayInst& R, f3 bmin, f3 bmax)
 //   such rays: a margin alone, however wide, is wrong for them).
 //
 // Hence the gate: every child descriptor of a wide node carries the NORMAL CONE of the triangles of that leaf / below that inner
-// child (rdx_types.h, derive_accel), and the child may be skipped only by rays that provably have kappa >= 2^-7 against all of
+// child (rdx_types.h, accel_layout.cpp), and the child may be skipped only by rays that provably have kappa >= 2^-7 against all of
 // them (`safe`); then R <= 1.86e-4 * S with S >= |o - v| for every vertex in the child's box, and the skips keep a margin that covers R:
 //   leaf      skipped iff the slabs miss each other by more than max(2^-8 (|tFar| + n0), mabs),  mabs = 4e-4 * S1 * max|1/d_k|
 //   subtree   skipped iff it is entered beyond max(best_t (1 + 2^-8), best_t + mabs)              (S1 = L1 bound of S from the boxes)

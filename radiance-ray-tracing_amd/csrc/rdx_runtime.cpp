@@ -13,8 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <array>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -34,6 +32,7 @@
 #define RDX_STOCK_REDUCED_HASH 0xf95635133b09cb3full         // of samples/shader.cl; tools/stock_shader_hash.py prints it
 #endif
 #include RDX_SBT_HEADER
+#include "accel_layout.h"
 #include "bvh_build.h"
 #include "device_math.h"
 #include "kernels.h"
@@ -55,42 +54,18 @@ constexpr int RDX_MAX_DEVICES = 16;
 constexpr uint32_t RDX_SORT_AUTO_MIN_WIDE = 1u << 20;      // option "sort" -1: scenes with at least this many inner BVH nodes sort their rays per bounce ...
 constexpr uint32_t RDX_SORT_AUTO_MIN_WIDE_FULL = 1u << 15; // ... and so do scenes from this size on for chunks of more than sortMinPaths paths (the sort is four more dependent
                                                            // launches per bounce: small shards lose with it, and so does a scene that sits in L2 anyway)
-constexpr uint32_t RDX_CULL_AUTO_MIN_WIDE = 1u << 20;      // option "cull" -1: scenes with at least this many inner BVH nodes take the culled walk
-struct AccelCache {                // derived traversal layout of one TLAS buffer
+struct AccelCache {                // derived traversal layout of one TLAS buffer on one device (accel_layout.h)
     uint64_t version = ~0ull;
     DNode* tnodes = nullptr; DNode* ctnodes = nullptr; DInst* insts = nullptr; DNode* bnodes = nullptr; DTri* tris = nullptr;
     DWide* wide = nullptr;
-    uint32_t stackNeed = 1;            // per-lane kernels (reference order: left child followed, right child pushed)
-    uint32_t coopNeed = 1;             // wave-cooperative kernel (leaf children are never pushed, smaller subtree first)
-    uint32_t topNeed = 1, blasNeed = 0; // its two parts: top-level entries of one ray / entries inside one BLAS (pool engine)
-    bool leafRoots = false;             // some instance's BLAS is a single leaf of <= 8 triangles
-    float sceneLo[3] = {0, 0, 0}, sceneHi[3] = {1, 1, 1};   // box of the top-level root (per-bounce ray sort grid)
-    bool sbtOffsets = false;               // an instance has SBTOffset != 0: reference-order kernel only
-    uint32_t nWide = 0;                    // inner BLAS nodes of the scene (sizes the automatic choice of the culled walk)
-    uint32_t blasNeedAny = 0;              // BLAS stack need of the pool engine when the push order depends on the ray (culled walk)
-    uint32_t nInst = 0;
-    uint32_t topFlat = 0, topFlatNeed = 1; // pool engine: number of top-level nodes if they are few enough (<= 64) to be evaluated
-                                        // all at once per ray instead of walked, and the instance-mask entries that can then pile up
-    bool coopOK = true;                // scene fits the key packing of the wave-cooperative kernel
-    uint32_t* groupBits = nullptr;     // pool engine: instance slots of the shared-transform group (bitmap, 9 words on the device), see derive_accel
-    uint32_t groupCount = 0;
-    bool groupIdentity = false;        // ... and the group's transform is the identity: root tests in the flat top-level step
-    uint32_t unifiedRoot = 0, unifiedNeed = 0;   // pool engine: one tree over top level + instances + BLASes (derive_accel), 0 = not built
-    DQuad* quad = nullptr;                 // pool engine, exhaustive walk: quad records (rdx_types.h), index = DWide index
-    uint32_t quadNeed = 0, quadUnifiedNeed = 0;  // pool-stack need of the quad walk inside one BLAS / from the unified root
+    DQuad* quad = nullptr;             // null: the quad records were not built
+    uint32_t* groupBits = nullptr;     // 9 words
+    rdx_accel_scalars s{};             // coopOK: ... and the engines' LDS footprint fits (derive_accel)
     void release()
     {
-        if (groupBits) HIP_IGN(hipFree(groupBits));
-        groupBits = nullptr;
-        if (tnodes) HIP_IGN(hipFree(tnodes));
-        if (ctnodes) HIP_IGN(hipFree(ctnodes));
-        if (insts) HIP_IGN(hipFree(insts));
-        if (bnodes) HIP_IGN(hipFree(bnodes));
-        if (tris) HIP_IGN(hipFree(tris));
-        if (wide) HIP_IGN(hipFree(wide));
-        if (quad) HIP_IGN(hipFree(quad));
-        quad = nullptr;
-        tnodes = nullptr; ctnodes = nullptr; insts = nullptr; bnodes = nullptr; tris = nullptr; wide = nullptr;
+        for (void* p : {(void*)tnodes, (void*)ctnodes, (void*)insts, (void*)bnodes, (void*)tris, (void*)wide, (void*)quad, (void*)groupBits})
+            if (p) HIP_IGN(hipFree(p));
+        tnodes = nullptr; ctnodes = nullptr; insts = nullptr; bnodes = nullptr; tris = nullptr; wide = nullptr; quad = nullptr; groupBits = nullptr;
     }
 };
 
@@ -161,17 +136,36 @@ struct Context {
     size_t gatherCap[4] = {};
     uint32_t* hStatus = nullptr;            // pinned, device-mapped: bit 0 = a traversal wave hit its iteration bound
     uint32_t* dStatus = nullptr;            // its device address
-    int groupsOpt = 0;                      // sample groups in flight: 1..4, 0 = two for chunks small enough to be ramp + drain bound
-    int fuse = -1;                          // shadow(d) + extend(d+1) in one launch: 1 / -1 on, 0 off
-    int pathMode = 0;                       // 0 = staged wavefront (launch per stage per bounce), 1 = whole paths in one launch
     unsigned long long* dVisit = nullptr;   // 8 words
     unsigned long long* hVisit = nullptr;   // pinned
-    // options
-    int64_t chunkPaths = 16ll << 20;
-    bool countVisits = false, profiling = false;
-    int inlineLeafRoots = 1;                // pool engine: single-leaf BLASes handled in the flat top-level step (option "inline_leaf_roots")
-    int cull = -1;                          // pool engine: culled walk (option "cull"): 1 on, 0 off, -1 = on for scenes of >= 1 M inner nodes
-    int textures = 0;                       // option "textures": 1 = the stock shader samples the bound image array
+    // everything rdx_set_option / rdx_set_profiling write, except the builder's knobs below: handed to the other devices'
+    // contexts as a whole (rdx_trace_rays)
+    struct Options {
+        int64_t chunkPaths = 16ll << 20;
+        bool countVisits = false, profiling = false;
+        int groupsOpt = 0;                      // sample groups in flight: 1..4, 0 = two for chunks small enough to be ramp + drain bound
+        int fuse = -1;                          // shadow(d) + extend(d+1) in one launch: 1 / -1 on, 0 off
+        int pathMode = 0;                       // 0 = staged wavefront (launch per stage per bounce), 1 = whole paths in one launch
+        int inlineLeafRoots = 1;                // pool engine: single-leaf BLASes handled in the flat top-level step (option "inline_leaf_roots")
+        int cull = -1;                          // pool engine: culled walk (option "cull"): 1 on, 0 off, -1 = on for scenes of >= 1 M inner nodes
+        int textures = 0;                       // option "textures": 1 = the stock shader samples the bound image array
+        int userLocalSize = 64;                 // option "user_shader_local_size": work-group size of a user program's launch (the reference uses 1)
+        int sortRays = -1;                      // option "sort": per-bounce ray sort: 1 on, 0 off, -1 automatic
+        int topFlat = 1;                        // pool engine: evaluate small top-level trees all at once (option "top_flat")
+        int groupInstances = 1;                 // pool engine: instances with bit-identical inverse matrices share one ray slot (option "group_instances")
+        int userStages = 1;                     // user programs that differ from the stock one only inside stage functions run on the wavefront pipeline (option "user_stages")
+        int64_t sortMinPaths = 3ll << 19;       // chunks of more paths than this (1.5 M) sort the rays of mid-size scenes and use the 7-wave quad kernels (option
+                                                // "sort_min_paths"; 4.7 M / 3 M / 1.5 M: 1/2 frame 13.6 / 12.4 / 12.4 ms, 1/4 frame 7.57 / 7.57 / 7.35 ms, Sponza-class)
+        int64_t smallChunkPaths = 9ll << 19;    // chunks of at most this many paths (4.7 M) do not fill the chip: two sample groups, 6-wave quad kernels, no ray sort
+                                                // (option "small_chunk_paths")
+        int quad = 1;                           // pool engine, exhaustive walk: quad records -- two tree levels per fetch (option "quad"): 1 on (default), 0 off,
+                                                // -1 = only for chunks the chip is not filled by (<= RDX_QUAD_AUTO_MAX_PATHS paths)
+        int unifiedTree = 1;                    // pool engine: large top levels of identity instances are walked by the pool (option "unified_tree")
+        int kernel = 3;                         // traversal kernel: 3 cooperative + shared node pool, 2 cooperative, 1 per-lane wide, 0 reference order
+        int overlap = 0;                        // extend(d+1) || shadow(d) on two streams (experimental): 1 on, 0 off
+    } opt;
+    int gpuBuild = 1;                       // BVH builder: large nodes are binned on the GPU (option "gpu_build"); read on g0 only
+    int64_t gpuBuildMin = 32768;            // ... nodes (and meshes) of at least this many primitives (option "gpu_build_min")
     std::vector<std::unique_ptr<rdx_sampler_s>> samplers;
     // user programs: the views their image2d_array_t / sampler_t parameters point to (texture.h TexImageView at 0, TexSamplerView
     // at 32), made from slots 11 / 12 and rewritten when what they describe changes (user_tex_views)
@@ -179,22 +173,6 @@ struct Context {
     uint8_t texViewsHost[48] = {};
     bool texViewsValid = false;
     std::string shaderInclude;              // -I for user shader programs (rdx_shader_include_path; the reference's SHADER_LIB_PATH)
-    int userLocalSize = 64;                 // option "user_shader_local_size": work-group size of a user program's launch (the reference uses 1)
-    int sortRays = -1;                      // option "sort": per-bounce ray sort: 1 on, 0 off, -1 automatic
-    int topFlat = 1;                        // pool engine: evaluate small top-level trees all at once (option "top_flat")
-    int groupInstances = 1;                 // pool engine: instances with bit-identical inverse matrices share one ray slot (option "group_instances")
-    int userStages = 1;                     // user programs that differ from the stock one only inside stage functions run on the wavefront pipeline (option "user_stages")
-    int64_t sortMinPaths = 3ll << 19;       // chunks of more paths than this (1.5 M) sort the rays of mid-size scenes and use the 7-wave quad kernels (option
-                                            // "sort_min_paths"; 4.7 M / 3 M / 1.5 M: 1/2 frame 13.6 / 12.4 / 12.4 ms, 1/4 frame 7.57 / 7.57 / 7.35 ms, Sponza-class)
-    int64_t smallChunkPaths = 9ll << 19;    // chunks of at most this many paths (4.7 M) do not fill the chip: two sample groups, 6-wave quad kernels, no ray sort
-                                            // (option "small_chunk_paths")
-    int gpuBuild = 1;                       // BVH builder: large nodes are binned on the GPU (option "gpu_build")
-    int64_t gpuBuildMin = 32768;            // ... nodes (and meshes) of at least this many primitives (option "gpu_build_min")
-    int quad = 1;                           // pool engine, exhaustive walk: quad records -- two tree levels per fetch (option "quad"): 1 on (default), 0 off,
-                                            // -1 = only for chunks the chip is not filled by (<= RDX_QUAD_AUTO_MAX_PATHS paths)
-    int unifiedTree = 1;                    // pool engine: large top levels of identity instances are walked by the pool (option "unified_tree")
-    int kernel = 3;                         // traversal kernel: 3 cooperative + shared node pool, 2 cooperative, 1 per-lane wide, 0 reference order
-    int overlap = 0;                        // extend(d+1) || shadow(d) on two streams (experimental): 1 on, 0 off
     rdx_trace_stats stats{};
     float camAngles[3] = {0, 0, 0}, camTrig[6] = {1, 0, 1, 0, 1, 0};      // camera_args: cos / sin of the camera angles, evaluated on the device
     bool camCached = false;
@@ -239,129 +217,7 @@ bool known_buffer(const void* h)
 }
 
 // ---- derived traversal layout ------------------------------------------------------------------
-// worst-case stack occupancy of the left-first DFS in kernels.hip (right child pushed, left followed)
-uint32_t blas_need(const BlobNode* nodes, uint32_t idx)
-{
-    // iterative post-order to survive deep trees
-    struct Frame { uint32_t idx; uint32_t needL; int state; };
-    std::vector<Frame> st{{idx, 0, 0}};
-    uint32_t ret = 0;
-    while (!st.empty()) {
-        Frame& f = st.back();
-        const BlobNode& n = nodes[f.idx];
-        if (n.w0 & LEAF_BIT) { ret = 0; st.pop_back(); continue; }
-        if (f.state == 0) { f.state = 1; st.push_back({n.w0, 0, 0}); continue; }
-        if (f.state == 1) { f.needL = ret; f.state = 2; st.push_back({n.w1, 0, 0}); continue; }
-        ret = std::max(1u + f.needL, ret);
-        st.pop_back();
-    }
-    return ret;
-}
-
-// Cone of lines around the normals of a set of triangles + their worst shape; see DESIGN.md 4.1c for what the culled walk
-// proves from it.  kappa0 = 2^-7: the culled walk skips a subtree / a leaf only for rays that make at least asin(kappa0 / q)
-// with the plane of every triangle below the node.
-struct NormalCone {
-    double a[3] = {0, 0, 0};       // axis (unit) -- valid when n > 0
-    double alpha = 0;              // half-angle: every normal line is within alpha of the axis line
-    double q = 1;                  // min over the triangles of sin(angle(e1, e2))
-    bool never = false;            // degenerate triangle, or the normals do not fit a cone of < 90 degrees
-    uint32_t n = 0;
-    static double ang(const double* x, const double* y)      // angle between two LINES
-    {
-        const double c = std::fabs(x[0] * y[0] + x[1] * y[1] + x[2] * y[2]);
-        return std::acos(std::min(1.0, c));
-    }
-    void add_normal(const double* nn, double a1)
-    {
-        if (n == 0) { a[0] = nn[0]; a[1] = nn[1]; a[2] = nn[2]; alpha = a1; n = 1; return; }
-        NormalCone o; o.a[0] = nn[0]; o.a[1] = nn[1]; o.a[2] = nn[2]; o.alpha = a1; o.n = 1;
-        merge(o);
-    }
-    void add_triangle(const DTri& t)
-    {
-        const double e1[3] = {t.e1[0], t.e1[1], t.e1[2]}, e2[3] = {t.e2[0], t.e2[1], t.e2[2]};
-        const double c[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
-        const double lc = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
-        const double l1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), l2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
-        if (!(lc > 0) || !(l1 > 0) || !(l2 > 0) || !std::isfinite(lc) || !std::isfinite(l1 * l2)) { never = true; return; }
-        q = std::min(q, lc / (l1 * l2));
-        const double nn[3] = {c[0] / lc, c[1] / lc, c[2] / lc};
-        add_normal(nn, 0.0);
-    }
-    void merge(const NormalCone& o)
-    {
-        never = never || o.never; q = std::min(q, o.q);
-        if (o.n == 0) return;
-        if (n == 0) { a[0] = o.a[0]; a[1] = o.a[1]; a[2] = o.a[2]; alpha = o.alpha; n = o.n; return; }
-        const double sgn = (a[0] * o.a[0] + a[1] * o.a[1] + a[2] * o.a[2]) < 0 ? -1.0 : 1.0;
-        const double gam = ang(a, o.a);
-        n += o.n;
-        if (gam + o.alpha <= alpha) return;                                        // o inside this cone
-        if (gam + alpha <= o.alpha) { a[0] = o.a[0]; a[1] = o.a[1]; a[2] = o.a[2]; alpha = o.alpha; return; }
-        // smallest cone around both: axis between the two, rotated from a towards o by (gam + o.alpha - alpha) / 2
-        const double na = (gam + alpha + o.alpha) / 2;
-        const double w = gam > 1e-12 ? (na - alpha) / gam : 0.5;
-        double m[3] = {a[0] * (1 - w) + sgn * o.a[0] * w, a[1] * (1 - w) + sgn * o.a[1] * w, a[2] * (1 - w) + sgn * o.a[2] * w};
-        const double lm = std::sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
-        if (!(lm > 1e-9)) { never = true; return; }
-        for (int k = 0; k < 3; ++k) m[k] /= lm;
-        // (the linear blend is not the exact bisecting rotation: take the half-angle from the blended axis itself)
-        const double sgn_o[3] = {sgn * o.a[0], sgn * o.a[1], sgn * o.a[2]};
-        alpha = std::max(ang(m, a) + alpha, ang(m, sgn_o) + o.alpha);
-        a[0] = m[0]; a[1] = m[1]; a[2] = m[2];
-    }
-    // x | y << 8 | z << 16 | T << 24 (T: 7 bits, rdx_types.h wide_desc): a ray may be culled against this leaf / subtree only if
-    // |d^ . a'| >= T / 127 with a' = (b - 127.5) / 127 the quantised axis.  Derivation: every normal line is within
-    // alpha + eq of a' (eq: quantisation), so the ray makes >= asin|d^ . a'^| - (alpha + eq) with every triangle's plane; that must be
-    // >= asin(kappa0 / q).  |a'| is within 0.7 % of 1, which the factor 1.0075 covers, fp32 evaluation another 1e-5.
-    uint32_t pack() const
-    {
-        const double kappa0 = 1.0 / 128.0, eq = 0.0085;
-        uint32_t T = WIDE_CONE_NEVER;
-        uint32_t b[3] = {128, 128, 128};
-        if (!never && n > 0 && q > kappa0 && alpha + eq < 1.5) {
-            const double need = std::asin(std::min(1.0, kappa0 / q)) + alpha + eq;     // angle the ray must make with the axis PLANE
-            if (need < 1.55) {
-                const double thr = std::sin(need) * 1.0075 * 1.00002;
-                const double t8 = std::ceil(thr * 127.0) + 1.0;
-                if (t8 <= 126.0) T = (uint32_t)t8;
-            }
-            for (int k = 0; k < 3; ++k) b[k] = (uint32_t)std::min(255.0, std::max(0.0, std::floor(127.5 + 127.0 * a[k] + 0.5)));
-        }
-        return b[0] | (b[1] << 8) | (b[2] << 16) | (T << 24);
-    }
-};
-
-// Can the order-free engines (pool / cooperative / per-lane wide) trace instances whose SBT offset is k?  They assume that a
-// radiance ray's row (1 + k) has NO any-hit shader -- so the winner is the minimum, whatever the visiting order -- and that a
-// shadow ray's row (2 + k) is the stock pair: an any-hit shader that ends the walk at the first accepted candidate and a
-// closest-hit shader that only flags the hit (`anyShadow` / `shadow`: neither looks at WHICH candidate it was).  Rows are those
-// of the sbt.json this library was generated from (tools/genSBT.py -> sbt_generated.h); k = 0 always qualifies for the stock
-// table.  Anything else keeps the reference's DFS order: the reference-order kernel.
-bool sbt_offset_is_order_free(uint32_t k)
-{
-    struct Row { int row; const char* fn; };
-    static const Row anyHit[] = {
-#define X(row, fn) {row, #fn},
-        RDX_SBT_ANY_HIT(X)
-#undef X
-        {-1, nullptr}};
-    static const Row closest[] = {
-#define X(row, fn) {row, #fn},
-        RDX_SBT_CLOSEST_HIT(X)
-#undef X
-        {-1, nullptr}};
-    auto find = [](const Row* t, int row) -> const char* { for (; t->fn; ++t) if (t->row == row) return t->fn; return nullptr; };
-    if (k > 1000000u) return false;
-    const int r1 = 1 + (int)k, r2 = 2 + (int)k;
-    if (find(anyHit, r1)) return false;
-    const char* a2 = find(anyHit, r2); const char* c2 = find(closest, r2);
-    const char* a0 = find(anyHit, 2); const char* c0 = find(closest, 2);
-    auto same = [](const char* x, const char* y) { return (x == nullptr && y == nullptr) || (x && y && !std::strcmp(x, y)); };
-    return same(a2, a0) && same(c2, c0);
-}
-
+// accel_layout.cpp derives it on the host; here it is uploaded to the calling thread's device
 int derive_accel(rdx_buffer_s* tb)
 {
     if (acc(tb) && acc(tb)->version == tb->version) return 0;
@@ -371,508 +227,32 @@ int derive_accel(rdx_buffer_s* tb)
         HIP_OK(hipMemcpy(tb->shadow.data(), tb->dptr, tb->size, hipMemcpyDeviceToHost));
         tb->shadowVersion = tb->version;
     }
-    const uint8_t* blob = tb->shadow.data();
-    const size_t bsz = tb->shadow.size();
-    if (bsz < 16) return fail("TLAS buffer too small");
-    const auto* th = reinterpret_cast<const BlobTopHeader*>(blob);
-    if (th->type != TYPE_TOP_AS || th->nodeByteOffset != 16 || th->instByteOffset < 16 + sizeof(BlobNode) ||
-        th->instByteOffset > bsz || th->totalBufferSize > bsz)
-        return fail("descriptor slot 13 does not hold a top-level acceleration structure blob");
-    const uint32_t nTop = (th->instByteOffset - th->nodeByteOffset) / sizeof(BlobNode);
-    const auto* tnodes = reinterpret_cast<const BlobNode*>(blob + th->nodeByteOffset);
-    const auto* binst = reinterpret_cast<const BlobInst*>(blob + th->instByteOffset);
-    // instance count = max leaf (start+count)
-    uint32_t nInst = 0;
-    for (uint32_t i = 0; i < nTop; ++i)
-        if (tnodes[i].w0 & LEAF_BIT) nInst = std::max(nInst, tnodes[i].w1 + (tnodes[i].w0 & 0x7fffffffu));
-    if ((size_t)th->instByteOffset + (size_t)nInst * sizeof(BlobInst) > bsz) return fail("TLAS blob: instance array out of range");
-
-    // The derived layout (stack needs computed children-first, first-in-DFS tie-break = lowest slot) relies on the numbering
-    // the reference's flattener produces (bvh.cpp:475-497,551-563): DFS pre-order -- left child = parent + 1, right child
-    // behind the whole left subtree -- and leaves listing their instances / triangles in leaf order.  A foreign or
-    // corrupted blob (e.g. a cache file without side-car) that breaks it is refused here rather than mis-sized on the GPU.
-    std::vector<DNode> dT(nTop);
-    {
-        uint32_t expectInst = 0;
-        for (uint32_t i = 0; i < nTop; ++i) {
-            std::memcpy(&dT[i], &tnodes[i], sizeof(BlobNode));
-            if (!(tnodes[i].w0 & LEAF_BIT)) {
-                if (tnodes[i].w0 >= nTop || tnodes[i].w1 >= nTop) return fail("TLAS blob: child index out of range");
-                if (tnodes[i].w0 != i + 1 || tnodes[i].w1 <= tnodes[i].w0) return fail("TLAS blob: node %u is not in DFS pre-order (children %u, %u)", i, tnodes[i].w0, tnodes[i].w1);
-            } else {
-                if (tnodes[i].w1 != expectInst) return fail("TLAS blob: leaf %u does not list its instances in leaf order (start %u, expected %u)", i, tnodes[i].w1, expectInst);
-                expectInst += tnodes[i].w0 & 0x7fffffffu;
-            }
-        }
-    }
-    std::vector<DNode> dB;
-    std::vector<DTri> dTri;
-    std::vector<DWide> dW;
-    std::vector<DInst> dI(nInst);
-    struct BlasInfo { uint32_t nodeBase; uint32_t need; uint32_t coopNeed; uint32_t anyNeed; uint32_t triBase; uint32_t rootDesc0, rootDesc1; float rootMin[3], rootMax[3];
-                      uint32_t nTris; uint32_t users; };
-    bool hugeLeaf = false;                  // a leaf of more triangles than the wide layout's count field holds
-    bool coopOK = nInst <= RDX_COOP_MAX_INSTANCES;
-    bool sbtOffsets = false;
-    uint32_t maxLeafChunks = 0;             // extra stack entries an oversized (> 8 triangle) leaf can push
-    uint32_t maxLeafTris = 0;
-    std::map<uint32_t, BlasInfo> blasAt;    // byte offset -> merged-array base
-    for (uint32_t k = 0; k < nInst; ++k) {
-        const BlobInst& bi = binst[k];
-        // Dispatch index = instanceSBTOffset + sbtRecordOffset (radiance.cl:281, shader.cl:574-605).  With a non-zero offset the
-        // any-hit shader of a RADIANCE ray's row may end the walk at the first accepted candidate in the reference's DFS order --
-        // an order only the reference-order kernel keeps -- so scenes with such a row are traced by that kernel; offsets whose
-        // rows behave like the stock rows 1 / 2 (sbt_offset_is_order_free) stay on the production engines (the live loader always
-        // writes 0, tools/sceneBuilder.cpp:302).
-        if (bi.SBTOffset != 0 && !sbt_offset_is_order_free(bi.SBTOffset)) sbtOffsets = true;
-        auto it = blasAt.find(bi.instanceOffset);
-        if (it == blasAt.end()) {
-            if ((size_t)bi.instanceOffset + 16 > bsz) return fail("TLAS blob: BLAS offset out of range");
-            const uint8_t* bb = blob + bi.instanceOffset;
-            const auto* bh = reinterpret_cast<const BlobBotHeader*>(bb);
-            if (bh->type != TYPE_BOT_AS || bh->faceByteOffset < bh->nodeByteOffset || bh->vertexOffset < bh->faceByteOffset ||
-                (size_t)bi.instanceOffset + bh->vertexOffset > bsz)
-                return fail("TLAS blob: malformed bottom-level structure at byte %u", bi.instanceOffset);
-            const uint32_t nNodes = (bh->faceByteOffset - bh->nodeByteOffset) / sizeof(BlobNode);
-            const uint32_t nTris = (bh->vertexOffset - bh->faceByteOffset) / sizeof(BlobTri);
-            const auto* bn = reinterpret_cast<const BlobNode*>(bb + bh->nodeByteOffset);
-            const auto* bt = reinterpret_cast<const BlobTri*>(bb + bh->faceByteOffset);
-            const auto* bv = reinterpret_cast<const float*>(bb + bh->vertexOffset);
-            const size_t vertFloatsAvail = (bsz - bi.instanceOffset - bh->vertexOffset) / 4;
-            const uint32_t nodeBase = (uint32_t)dB.size(), triBase = (uint32_t)dTri.size();
-            if ((uint64_t)nodeBase + nNodes >= (1u << 30)) return fail("too many BVH nodes for 30-bit references");
-            dB.resize(nodeBase + nNodes);
-            uint32_t expectTri = 0;
-            for (uint32_t i = 0; i < nNodes; ++i) {
-                DNode& d = dB[nodeBase + i];
-                std::memcpy(&d, &bn[i], sizeof(BlobNode));
-                if (bn[i].w0 & LEAF_BIT) {
-                    if ((uint64_t)bn[i].w1 + (bn[i].w0 & 0x7fffffffu) > nTris) return fail("BLAS blob: leaf range out of bounds");
-                    if (bn[i].w2 == TYPE_TRIG) {
-                        if (bn[i].w1 != expectTri) return fail("BLAS blob: leaf %u does not list its triangles in leaf order (start %u, expected %u)", i, bn[i].w1, expectTri);
-                        expectTri += bn[i].w0 & 0x7fffffffu;
-                    }
-                    maxLeafChunks = std::max(maxLeafChunks, 2u * (((bn[i].w0 & 0x7fffffffu) + 7u) / 8u));
-                    maxLeafTris = std::max(maxLeafTris, bn[i].w0 & 0x7fffffffu);
-                    d.w1 = bn[i].w1 + triBase;
-                } else {
-                    if (bn[i].w0 >= nNodes || bn[i].w1 >= nNodes) return fail("BLAS blob: child index out of range");
-                    if (bn[i].w0 != i + 1 || bn[i].w1 <= bn[i].w0) return fail("BLAS blob: node %u is not in DFS pre-order (children %u, %u)", i, bn[i].w0, bn[i].w1);
-                    d.w0 = bn[i].w0 + nodeBase; d.w1 = bn[i].w1 + nodeBase;
-                }
-            }
-            if ((uint64_t)triBase + nTris > LEAF_START_MASK) return fail("too many triangles for 27-bit triangle-run references");
-            dTri.resize(triBase + nTris);
-            for (uint32_t i = 0; i < nTris; ++i) {
-                const BlobTri& t = bt[i];
-                if ((size_t)std::max({t.idx0, t.idx1, t.idx2}) * 4 + 3 > vertFloatsAvail)
-                    return fail("BLAS blob: vertex index out of range");
-                const float* v0 = bv + 4 * (size_t)t.idx0; const float* v1 = bv + 4 * (size_t)t.idx1; const float* v2 = bv + 4 * (size_t)t.idx2;
-                DTri& d = dTri[triBase + i];
-                d.v0[0] = v0[0]; d.v0[1] = v0[1]; d.v0[2] = v0[2]; d.primID = t.primID;
-                d.e1[0] = v1[0] - v0[0]; d.e1[1] = v1[1] - v0[1]; d.e1[2] = v1[2] - v0[2]; d._p0 = 0xffffffffu;   // radiance.cl:215; _p0: see "shared-transform group"
-                d.e2[0] = v2[0] - v0[0]; d.e2[1] = v2[1] - v0[1]; d.e2[2] = v2[2] - v0[2]; d._p1 = triBase;       // radiance.cl:216; _p1: first triangle slot of this BLAS
-            }
-            // wide layout: one record per inner node, numbered in the same DFS pre-order
-            const uint32_t wideBase = (uint32_t)dW.size();
-            std::vector<uint32_t> wideIdx(nNodes, 0);
-            uint32_t nInner = 0;
-            for (uint32_t i = 0; i < nNodes; ++i) if (!(bn[i].w0 & LEAF_BIT)) wideIdx[i] = nInner++;
-            if ((uint64_t)wideBase + nInner >= (1u << 30)) return fail("too many BVH nodes for 30-bit references");
-            std::vector<NormalCone> cone(nNodes);
-            auto desc = [&](uint32_t c, uint32_t& d0, uint32_t& d1) {
-                if (bn[c].w0 & LEAF_BIT) {
-                    const uint32_t cnt = bn[c].w2 == TYPE_TRIG ? (bn[c].w0 & 0x7fffffffu) : 0u;
-                    if (cnt > WIDE_MAX_LEAF_TRIS) hugeLeaf = true;
-                    wide_desc(true, bn[c].w1 + triBase, std::min(cnt, (uint32_t)WIDE_MAX_LEAF_TRIS), cone[c].pack(), d0, d1);
-                } else wide_desc(false, wideBase + wideIdx[c], 0u, cone[c].pack(), d0, d1);
-            };
-            dW.resize(wideBase + nInner);
-            // Normal cones (culled walk, kernels.hip): for every node the cone of LINES that holds the normals of all triangles
-            // below it -- axis, half-angle alpha -- and the worst triangle shape q = min sin(angle(e1, e2)).  Bottom-up (children
-            // have larger indices); computed in double from the fp32 edge vectors the intersection test uses.
-            for (uint32_t i = nNodes; i-- > 0;) {
-                NormalCone& c = cone[i];
-                if (bn[i].w0 & LEAF_BIT) {
-                    const uint32_t cnt = bn[i].w2 == TYPE_TRIG ? (bn[i].w0 & 0x7fffffffu) : 0u;
-                    for (uint32_t t = 0; t < cnt; ++t) c.add_triangle(dTri[triBase + bn[i].w1 + t]);
-                } else { c = cone[bn[i].w0]; c.merge(cone[bn[i].w1]); }
-            }
-            // Stack need of the wide walk: a leaf child is queued, never pushed; of two inner children one is followed
-            // and the other pushed.  The visiting order is free, so the child with the SMALLER need goes
-            // into the "followed" (left) half of the record: need = max(1 + smaller, larger) instead of
-            // max(1 + left, right).  Children have larger indices than their parent (DFS pre-order).
-            std::vector<uint32_t> aneed(nNodes, 0);                     // any push order: 1 + the deeper inner child
-            std::vector<uint32_t> cneed(nNodes, 0), wneed(nNodes, 0);   // wneed: per-lane wide kernel on the same records (pushes leaves too)
-            for (uint32_t i = nNodes; i-- > 0;) {
-                if (bn[i].w0 & LEAF_BIT) continue;
-                uint32_t a = bn[i].w0, b = bn[i].w1;
-                const bool la = bn[a].w0 & LEAF_BIT, lb = bn[b].w0 & LEAF_BIT;
-                if (!la && !lb) {
-                    aneed[i] = 1u + std::max(aneed[a], aneed[b]);
-                    if (cneed[b] < cneed[a]) std::swap(a, b);
-                    cneed[i] = std::max(1u + cneed[a], cneed[b]);
-                } else {
-                    cneed[i] = la ? (lb ? 0u : cneed[b]) : cneed[a];
-                    aneed[i] = la ? (lb ? 0u : aneed[b]) : aneed[a];
-                }
-                wneed[i] = std::max(1u + wneed[a], wneed[b]);
-                DWide& w = dW[wideBase + wideIdx[i]];
-                const BlobNode& L = bn[a]; const BlobNode& Rn = bn[b];
-                for (int k = 0; k < 3; ++k) { w.lmin[k] = L.bottom[k]; w.lmax[k] = L.top[k]; w.rmin[k] = Rn.bottom[k]; w.rmax[k] = Rn.top[k]; }
-                desc(a, w.ld0, w.ld1);
-                desc(b, w.rd0, w.rd1);
-            }
-            BlasInfo info{};
-            info.nodeBase = nodeBase; info.need = std::max(blas_need(bn, 0), wneed[0]); info.coopNeed = cneed[0]; info.anyNeed = aneed[0]; info.triBase = triBase;
-            if (nTris > RDX_COOP_MAX_BLAS_TRIS) coopOK = false;
-            desc(0, info.rootDesc0, info.rootDesc1);
-            for (int k = 0; k < 3; ++k) { info.rootMin[k] = bn[0].bottom[k]; info.rootMax[k] = bn[0].top[k]; }
-            info.nTris = nTris; info.users = 0;
-            it = blasAt.emplace(bi.instanceOffset, info).first;
-        }
-        it->second.users++;
-        DInst& d = dI[k];
-        std::memset(&d, 0, sizeof d);
-        std::memcpy(d.fwd, bi.m, 64);
-        inverse_mat4(bi.m, d.inv);          // zeros stay if singular (oracle convention; reference: uninitialised)
-        d.SBTOffset = bi.SBTOffset; d.instanceID = bi.instanceID; d.customInstanceID = bi.customInstanceID;
-        d.blasRoot = it->second.nodeBase;
-        d.rootDesc0 = it->second.rootDesc0; d.rootDesc1 = it->second.rootDesc1; d._p0 = it->second.triBase;
-        for (int k = 0; k < 3; ++k) { d.rootMin[k] = it->second.rootMin[k]; d.rootMax[k] = it->second.rootMax[k]; }
-        // conservative world-space box of the root OBB + margin coefficient for the instance pre-test
-        {
-            double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, fa = 0, fi = 0;
-            bool finite = true;
-            for (int c = 0; c < 8; ++c) {
-                const double p[3] = {(c & 1) ? d.rootMax[0] : d.rootMin[0], (c & 2) ? d.rootMax[1] : d.rootMin[1], (c & 4) ? d.rootMax[2] : d.rootMin[2]};
-                for (int r = 0; r < 3; ++r) {
-                    const double w = (double)bi.m[4 * r] * p[0] + (double)bi.m[4 * r + 1] * p[1] + (double)bi.m[4 * r + 2] * p[2] + (double)bi.m[4 * r + 3];
-                    lo[r] = std::min(lo[r], w); hi[r] = std::max(hi[r], w);
-                    finite = finite && std::isfinite(w);
-                }
-            }
-            for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { fa += (double)bi.m[4 * r + c] * bi.m[4 * r + c]; fi += (double)d.inv[4 * r + c] * d.inv[4 * r + c]; }
-            const bool affine = bi.m[12] == 0.f && bi.m[13] == 0.f && bi.m[14] == 0.f && bi.m[15] == 1.f;
-            const double kappa = std::sqrt(fa) * std::sqrt(fi);
-            const bool usable = finite && affine && !(d.rootDesc1 & WIDE_LEAF) && kappa > 0 && kappa < 1e4 && std::isfinite(kappa);
-            double ext = 0;
-            for (int r = 0; r < 3; ++r) {
-                d.worldMin[r] = std::nextafterf((float)lo[r], -INFINITY); d.worldMax[r] = std::nextafterf((float)hi[r], INFINITY);
-                ext = std::max(ext, std::max(std::fabs(lo[r]), std::fabs(hi[r])));
-            }
-            // margin = c * (|o|_inf + ext): 64 x the first-order bound 4u*kappa on the displacement of the
-            // object-space ray the reference builds in fp32 (DESIGN.md "instance pre-test")
-            d.worldMin[3] = usable ? (float)(64.0 * 5.97e-8 * 4.0 * kappa) : -1.0f;
-            d.worldMax[3] = (float)ext;
-        }
-    }
-    // Shared-transform group (pool engine, flat top level).  The object-space ray of an instance is inverse(object->world) applied
-    // to the world ray with the reference's expressions (radiance.cl:161-169) -- a function of the inverse matrix's BITS and the
-    // ray alone.  Instances whose inverse matrices are bit-identical (a loader that puts every mesh of an OBJ under one node:
-    // all identity, tools/sceneBuilder.cpp:287-315; every scene of this repository's bench) therefore share ONE object-space
-    // ray: a wave lane writes it to its LDS ray slot once and enters all of them without waiting for one instance's subtree and
-    // queued tests to drain before the next (traverse_pool.h).  The instance slot a candidate belongs to then cannot come from
-    // the ray slot; it is kept in the triangle record (DTri._p0), which needs the BLAS to belong to exactly one instance.
-    // The largest such set of instances (>= 2, inner-node roots only) is the group.
-    uint32_t groupBits[8] = {0, 0, 0, 0, 0, 0, 0, 0}, groupCount = 0;
-    bool groupIdentity = false;
-    if (nInst <= 256) {
-        std::map<std::array<uint32_t, 16>, std::vector<uint32_t>> byInv;
-        for (uint32_t k = 0; k < nInst; ++k) {
-            const BlasInfo& bi = blasAt[binst[k].instanceOffset];
-            if (bi.users != 1 || (dI[k].rootDesc1 & WIDE_LEAF)) continue;
-            std::array<uint32_t, 16> key;
-            std::memcpy(key.data(), dI[k].inv, 64);
-            byInv[key].push_back(k);
-        }
-        const std::vector<uint32_t>* best = nullptr;
-        for (auto& kv : byInv) if (kv.second.size() >= 2 && (!best || kv.second.size() > best->size())) best = &kv.second;
-        if (best) {
-            // identity group: the group's object-space ray equals the world ray up to the sign of zeros, on which no slab decision
-            // depends -- the flat top-level step then runs the reference's root-box test of these instances itself (world ray)
-            groupIdentity = true;
-            for (int e = 0; e < 16; ++e) if (!(dI[(*best)[0]].inv[e] == ((e % 5 == 0) ? 1.0f : 0.0f))) groupIdentity = false;
-        }
-        if (best)
-            for (uint32_t k : *best) {
-                groupBits[k >> 5] |= 1u << (k & 31u); ++groupCount;
-                const BlasInfo& bi = blasAt[binst[k].instanceOffset];
-                for (uint32_t t = 0; t < bi.nTris; ++t) dTri[bi.triBase + t]._p0 = k;
-            }
-    }
-    // Unified tree (pool engine; scenes whose top level is too large for the flat step: > 64 nodes or > 256 instances -- a loader
-    // that makes one instance per mesh, tools/sceneBuilder.cpp:287-315).  When EVERY instance has the identity transform and a
-    // BLAS of its own, the object-space ray of all instances is one ray (the group's; it equals the world ray up to the sign
-    // of zeros, which no slab decision depends on: (b - o) / d keeps its value, min / max of +-0 or of equally signed infinities
-    // decide the same) -- so top-level nodes can be walked like BLAS nodes, by the pool, on that one ray slot:
-    //   top-level inner node -> wide record (boxes of its two children; an inner child is entered iff its box is hit, as the
-    //                           reference does when it pops the child; a leaf child is always entered: the reference never tests it)
-    //   top-level leaf       -> a balanced fan-out of always-entered pseudo nodes over its instances
-    //   instance             -> a child entry whose box is the BLAS root box and whose descriptor is the BLAS root (the root
-    //                           test of radiance.cl:61-63 for an inner root; a leaf root has its triangles tested directly)
-    // One item -- a super-root that holds the top-level root's box -- starts a ray; no top-level step, no instance step.
-    uint32_t unifiedRoot = 0, unifiedNeed = 0;
-    if ((nTop > 64 || nInst > 256) && nInst >= 2 && !(tnodes[0].w0 & LEAF_BIT) && !sbtOffsets) {
-        bool ok = true;
-        for (uint32_t k = 0; k < nInst && ok; ++k) {
-            const BlasInfo& bi = blasAt[binst[k].instanceOffset];
-            if (bi.users != 1) ok = false;
-            for (int e = 0; e < 16 && ok; ++e) if (!(dI[k].inv[e] == ((e % 5 == 0) ? 1.0f : 0.0f))) ok = false;      // (zero signs do not matter)
-            if (std::memcmp(dI[k].inv, dI[0].inv, 64) != 0) ok = false;                                               // ... but one ray needs one matrix
-        }
-        if (ok) {
-            const float BIG = 1.0e30f;
-            const uint32_t never = WIDE_CONE_NEVER << 24;
-            auto always = [&](float* mn, float* mx) { for (int k = 0; k < 3; ++k) { mn[k] = -BIG; mx[k] = BIG; } };
-            auto none = [&](float* mn, float* mx, uint32_t& d0, uint32_t& d1) { for (int k = 0; k < 3; ++k) { mn[k] = 0.f; mx[k] = 0.f; } wide_desc(true, 0u, 0u, never, d0, d1); };
-            auto inst_child = [&](uint32_t k, float* mn, float* mx, uint32_t& d0, uint32_t& d1) {
-                for (int c = 0; c < 3; ++c) { mn[c] = dI[k].rootMin[c]; mx[c] = dI[k].rootMax[c]; }
-                d0 = dI[k].rootDesc0; d1 = dI[k].rootDesc1;
-                const BlasInfo& bi = blasAt[binst[k].instanceOffset];
-                for (uint32_t t = 0; t < bi.nTris; ++t) dTri[bi.triBase + t]._p0 = k;          // the candidate's instance comes from the triangle
-            };
-            // fan-out over instances [a, b): returns the child entry for that range
-            std::function<uint32_t(uint32_t, uint32_t, float*, float*, uint32_t&, uint32_t&)> range_child =
-                [&](uint32_t a, uint32_t b, float* mn, float* mx, uint32_t& d0, uint32_t& d1) -> uint32_t {
-                    if (b - a == 1) { inst_child(a, mn, mx, d0, d1); return (dI[a].rootDesc1 & WIDE_LEAF) ? 0u : 1u + blasAt[binst[a].instanceOffset].anyNeed; }
-                    const uint32_t mid = a + (b - a) / 2;
-                    const uint32_t idx = (uint32_t)dW.size();
-                    dW.emplace_back();
-                    DWide w{};
-                    const uint32_t hl = range_child(a, mid, w.lmin, w.lmax, w.ld0, w.ld1);
-                    const uint32_t hr = range_child(mid, b, w.rmin, w.rmax, w.rd0, w.rd1);
-                    dW[idx] = w;
-                    always(mn, mx);
-                    wide_desc(false, idx, 0u, never, d0, d1);
-                    return 1u + std::max(hl, hr);
-                };
-            // top-level nodes, children first (DFS pre-order: children have larger indices)
-            std::vector<uint32_t> uIdx(nTop, 0), uH(nTop, 0);
-            for (uint32_t i = nTop; i-- > 0;) {
-                const BlobNode& n = tnodes[i];
-                if (n.w0 & LEAF_BIT) continue;
-                const uint32_t idx = (uint32_t)dW.size();
-                dW.emplace_back();
-                DWide w{};
-                uint32_t h[2] = {0, 0};
-                for (int c = 0; c < 2; ++c) {
-                    const uint32_t ch = c ? n.w1 : n.w0;
-                    float* mn = c ? w.rmin : w.lmin; float* mx = c ? w.rmax : w.lmax;
-                    uint32_t& d0 = c ? w.rd0 : w.ld0; uint32_t& d1 = c ? w.rd1 : w.ld1;
-                    const BlobNode& cn = tnodes[ch];
-                    if (!(cn.w0 & LEAF_BIT)) {
-                        for (int k = 0; k < 3; ++k) { mn[k] = cn.bottom[k]; mx[k] = cn.top[k]; }
-                        wide_desc(false, uIdx[ch], 0u, never, d0, d1);
-                        h[c] = 1u + uH[ch];
-                    } else {
-                        const uint32_t cnt = cn.w2 == TYPE_INST ? (cn.w0 & 0x7fffffffu) : 0u;
-                        if (cnt == 0) none(mn, mx, d0, d1);
-                        else {
-                            h[c] = range_child(cn.w1, cn.w1 + cnt, mn, mx, d0, d1);      // (one instance: its root test is this child's box test)
-                        }
-                    }
-                }
-                dW[idx] = w;
-                uIdx[i] = idx; uH[i] = std::max(h[0], h[1]);
-            }
-            // super-root: the reference tests the top-level root's own box when it pops it
-            DWide sr{};
-            for (int k = 0; k < 3; ++k) { sr.lmin[k] = tnodes[0].bottom[k]; sr.lmax[k] = tnodes[0].top[k]; }
-            wide_desc(false, uIdx[0], 0u, never, sr.ld0, sr.ld1);
-            none(sr.rmin, sr.rmax, sr.rd0, sr.rd1);
-            unifiedRoot = (uint32_t)dW.size();
-            dW.push_back(sr);
-            unifiedNeed = uH[0] + 2u;
-        }
-    }
-    // Quad records (rdx_types.h DQuad): one per wide record, built from the finished wide array -- BLAS nodes and the unified
-    // tree's records alike.  need[i] = entries the LIFO pool grows by while the subtree of a popped record i is walked alone
-    // (tight mode of the pool step): the inner entries are pushed together and popped first-entry-first, so
-    // need = max(k, max_j(entries below j + need[target j])); the halves and the entries inside a half are ordered to
-    // minimise it (the visiting order is free in the exhaustive walk).
-    // (not built where the culled walk will run -- large scenes under the automatic rule, or option "cull" 1: the culled walk keeps
-    // the 64-byte records, and the quad records of a 10 M-triangle scene are 0.6 GB and a second of host time.  Option "cull"
-    // changed later: the exhaustive walk then uses the 64-byte records until the structure is derived again.)
-    const bool wantQuad = g0.quad != 0 && !(g0.cull > 0 || (g0.cull < 0 && dW.size() >= RDX_CULL_AUTO_MIN_WIDE)) && !unifiedRoot;
-    std::vector<DQuad> dQ(wantQuad ? dW.size() : 0);
-    std::vector<uint32_t> qneed(dW.size(), 0);
-    if (wantQuad) {
-        struct QE { float mn[3], mx[3]; uint32_t d0, d1; };
-        auto empty = [](QE& e) { for (int k = 0; k < 3; ++k) { e.mn[k] = 0.f; e.mx[k] = 0.f; } e.d0 = 0u; e.d1 = WIDE_LEAF; };
-        auto entry_of = [](const DWide& w, int side, QE& e) {
-            for (int k = 0; k < 3; ++k) { e.mn[k] = side ? w.rmin[k] : w.lmin[k]; e.mx[k] = side ? w.rmax[k] : w.lmax[k]; }
-            const uint32_t d0 = side ? w.rd0 : w.ld0, d1 = side ? w.rd1 : w.ld1;
-            if (d1 & WIDE_LEAF) { e.d0 = wide_slot(d0); e.d1 = WIDE_LEAF | (wide_count(d1) << 24); }
-            else { e.d0 = d0; e.d1 = 0u; }
-        };
-        // the half for child `side` of wide record N
-        auto half_of = [&](const DWide& N, int side, QE out[2]) {
-            QE c;
-            entry_of(N, side, c);
-            bool pair = false;
-            if (!(c.d1 & WIDE_LEAF) && c.d0 < dW.size()) {
-                const DWide& C = dW[c.d0];
-                pair = true;
-                for (int k = 0; k < 3; ++k)
-                    if (!(std::min(C.lmin[k], C.rmin[k]) == c.mn[k] && std::max(C.lmax[k], C.rmax[k]) == c.mx[k])) pair = false;
-                // an empty entry in C (count-0 leaf with a zero box) would have entered the union above: such a record keeps its own test
-                if (pair) {
-                    entry_of(C, 0, out[0]); entry_of(C, 1, out[1]);
-                    for (int e = 0; e < 2; ++e) {
-                        out[e].d1 |= QUAD_PAIR;
-                        if (out[e].d1 & WIDE_LEAF) for (int k = 0; k < 3; ++k) { out[e].mn[k] = c.mn[k]; out[e].mx[k] = c.mx[k]; }
-                    }
-                }
-            }
-            if (!pair) { out[0] = c; empty(out[1]); }
-        };
-        // children first: explicit DFS over the records (BLAS records have larger-index children, unified records smaller ones)
-        std::vector<uint8_t> state(dW.size(), 0);       // 0 new, 1 open, 2 done
-        std::vector<uint32_t> stk;
-        for (size_t r = 0; r < dW.size(); ++r) {
-            if (state[r]) continue;
-            stk.push_back((uint32_t)r);
-            while (!stk.empty()) {
-                const uint32_t i = stk.back();
-                QE e[4];
-                half_of(dW[i], 0, e); half_of(dW[i], 1, e + 2);
-                if (state[i] == 0) {
-                    state[i] = 1;
-                    bool wait = false;
-                    for (int k = 0; k < 4; ++k)
-                        if (!(e[k].d1 & WIDE_LEAF)) {
-                            if (e[k].d0 >= dW.size()) return fail("derive_accel: wide record %u refers to record %u of %zu", i, e[k].d0, dW.size());
-                            if (state[e[k].d0] == 1) return fail("derive_accel: the wide records are not a tree (cycle through record %u)", e[k].d0);
-                            if (state[e[k].d0] == 0) { stk.push_back(e[k].d0); wait = true; }
-                        }
-                    if (wait) continue;
-                }
-                // all targets done: order the entries and store the record
-                auto nd = [&](const QE& x) -> int { return (x.d1 & WIDE_LEAF) ? -1 : (int)qneed[x.d0]; };
-                uint32_t bestNeed = ~0u; int bestArr = 0;
-                for (int arr = 0; arr < 8; ++arr) {
-                    int ord[4];
-                    const int h0 = (arr & 1) ? 2 : 0, h1 = (arr & 1) ? 0 : 2;
-                    ord[0] = h0 + ((arr >> 1) & 1); ord[1] = h0 + 1 - ((arr >> 1) & 1);
-                    ord[2] = h1 + ((arr >> 2) & 1); ord[3] = h1 + 1 - ((arr >> 2) & 1);
-                    uint32_t inner = 0, need = 0;
-                    for (int j = 3; j >= 0; --j) {          // j = pop position; `inner` = inner entries popped after j
-                        const int n = nd(e[ord[j]]);
-                        if (n < 0) continue;
-                        need = std::max(need, inner + (uint32_t)n);
-                        ++inner;
-                    }
-                    need = std::max(need, inner);
-                    if (need < bestNeed) { bestNeed = need; bestArr = arr; }
-                }
-                {
-                    const int arr = bestArr;
-                    int ord[4];
-                    const int h0 = (arr & 1) ? 2 : 0, h1 = (arr & 1) ? 0 : 2;
-                    ord[0] = h0 + ((arr >> 1) & 1); ord[1] = h0 + 1 - ((arr >> 1) & 1);
-                    ord[2] = h1 + ((arr >> 2) & 1); ord[3] = h1 + 1 - ((arr >> 2) & 1);
-                    DQuad& q = dQ[i];
-                    for (int hh = 0; hh < 2; ++hh) {
-                        const QE& a = e[ord[2 * hh]]; const QE& b = e[ord[2 * hh + 1]];
-                        DWide& w = q.half[hh];
-                        for (int k = 0; k < 3; ++k) { w.lmin[k] = a.mn[k]; w.lmax[k] = a.mx[k]; w.rmin[k] = b.mn[k]; w.rmax[k] = b.mx[k]; }
-                        w.ld0 = a.d0; w.ld1 = a.d1; w.rd0 = b.d0; w.rd1 = b.d1;
-                    }
-                }
-                qneed[i] = bestNeed;
-                state[i] = 2;
-                stk.pop_back();
-            }
-        }
-    }
-    uint32_t maxBlasQuad = 0;
-    for (auto& kv : blasAt) if (!(kv.second.rootDesc1 & WIDE_LEAF)) maxBlasQuad = std::max(maxBlasQuad, qneed[kv.second.rootDesc0]);
-    // stack need: TLAS part
-    // (cooperative kernel: the instances of a top-level leaf are pushed as 16-bit masks, one entry per 16 instances,
-    //  and the entry being consumed is pushed back while one of its instances is walked)
-    std::vector<uint32_t> needT(nTop, 0), needC(nTop, 0), needTopOnly(nTop, 0);
-    uint32_t maxBlasCoop = 0, maxBlasAny = 0;
-    std::vector<DNode> dTc(dT);
-    for (uint32_t i = nTop; i-- > 0;) {
-        const BlobNode& n = tnodes[i];
-        if (n.w0 & LEAF_BIT) {
-            const uint32_t cnt = n.w0 & 0x7fffffffu;
-            uint32_t mx = 0, mxc = 0;
-            for (uint32_t k = 0; k < cnt; ++k) {
-                const BlasInfo& bi = blasAt[binst[n.w1 + k].instanceOffset];
-                mx = std::max(mx, bi.need); mxc = std::max(mxc, bi.coopNeed); maxBlasAny = std::max(maxBlasAny, bi.anyNeed);
-            }
-            maxBlasCoop = std::max(maxBlasCoop, mxc);
-            needTopOnly[i] = (cnt + 15u) / 16u;
-            needT[i] = (cnt ? cnt - 1 : 0) + mx;
-            needC[i] = (cnt + 15u) / 16u + mxc;
-        } else {
-            needT[i] = std::max(1u + needT[n.w0], needT[n.w1]);   // children have larger indices (DFS pre-order)
-            // cooperative kernel: its own copy of the top-level nodes with the smaller-need child in the followed slot
-            if (needC[n.w1] < needC[n.w0]) std::swap(dTc[i].w0, dTc[i].w1);
-            needC[i] = std::max(1u + needC[dTc[i].w0], needC[dTc[i].w1]);
-            needTopOnly[i] = std::max(1u + needTopOnly[dTc[i].w0], needTopOnly[dTc[i].w1]);
-        }
-    }
+    AccelLayout L;
+    std::string err;
+    if (derive_accel_layout(tb->shadow.data(), tb->shadow.size(), AccelOptions{g.opt.quad, g.opt.cull}, L, err)) return fail_str(err);
     auto ac = std::make_unique<AccelCache>();
-    ac->stackNeed = std::max(1u, needT[0]) + 1u + maxLeafChunks;
-    // oversized leaves are cut into 8-triangle work items: all but the first piece of each child are pushed
-    ac->coopNeed = std::max(1u, needC[0]) + 1u + 2u * ((std::max(maxLeafTris, 1u) + 7u) / 8u - 1u);
-    ac->topNeed = std::max(1u, needTopOnly[0]) + 1u;
-    {
-        uint32_t masks = 0;
-        for (uint32_t i = 0; i < nTop; ++i) if (tnodes[i].w0 & LEAF_BIT) masks += ((tnodes[i].w0 & 0x7fffffffu) + 15u) / 16u;
-        // flat top level: <= 64 nodes (one reach bit each); the pending instances of a ray are a bitmap of <= 8 words per lane
-        ac->topFlat = (nTop <= 64 && nInst <= 256) ? nTop : 0u;
-        // spare word of a top-level leaf: it holds instances whose BLAS is a single leaf of <= 8 triangles (pool engine)
-        for (uint32_t i = 0; i < nTop; ++i) {
-            dT[i].w3 = 0;
-            if (!(tnodes[i].w0 & LEAF_BIT)) continue;
-            for (uint32_t k = 0; k < (tnodes[i].w0 & 0x7fffffffu); ++k) {
-                const DInst& di = dI[tnodes[i].w1 + k];
-                if ((di.rootDesc1 & WIDE_LEAF) && wide_count(di.rootDesc1) <= 8u) { dT[i].w3 = 1; ac->leafRoots = true; }
-            }
-        }
-        ac->nInst = nInst;
-        ac->topFlatNeed = std::max(1u, (nInst + 31u) / 32u);       // words per lane of the pending-instance bitmap
-        (void)masks;
-    }
-    ac->blasNeed = maxBlasCoop;
-    ac->blasNeedAny = maxBlasAny;
-    for (int k = 0; k < 3; ++k) { ac->sceneLo[k] = tnodes[0].bottom[k]; ac->sceneHi[k] = tnodes[0].top[k]; }
-    ac->sbtOffsets = sbtOffsets || hugeLeaf;      // (either way: the reference-order kernel, which reads the blob's own node layout)
-    ac->groupCount = groupCount; ac->groupIdentity = groupIdentity;
-    ac->unifiedRoot = unifiedRoot; ac->unifiedNeed = unifiedNeed;
-    ac->quadNeed = maxBlasQuad; ac->quadUnifiedNeed = unifiedRoot ? qneed[unifiedRoot] + 1u : 0u;
-    ac->nWide = (uint32_t)dW.size();
-    // per-lane kernels: [need][64 lanes] words of LDS per wave, 64 KB at most
-    if (ac->stackNeed > 250) return fail("BVH too deep for the LDS traversal stack: %u entries per ray needed, 250 available", ac->stackNeed);
-    auto up = [&](auto*& dptr, const auto& vec) -> hipError_t {
-        using T = typename std::remove_reference<decltype(vec)>::type::value_type;
-        const size_t bytes = std::max<size_t>(vec.size(), 1) * sizeof(T);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), bytes);
+    ac->s = L.s;
+    auto up = [&](auto*& dptr, const auto* src, size_t n) -> hipError_t {
+        const size_t elem = sizeof(*src);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), std::max<size_t>(n, 1) * elem);
         if (e != hipSuccess) return e;
-        return vec.empty() ? hipSuccess : hipMemcpy(dptr, vec.data(), vec.size() * sizeof(T), hipMemcpyHostToDevice);
+        return n ? hipMemcpy(dptr, src, n * elem, hipMemcpyHostToDevice) : hipSuccess;
     };
-    HIP_OK(up(ac->tnodes, dT));
-    HIP_OK(up(ac->ctnodes, dTc));
-    HIP_OK(up(ac->insts, dI));
-    HIP_OK(up(ac->bnodes, dB));
-    HIP_OK(up(ac->tris, dTri));
-    HIP_OK(up(ac->wide, dW));
-    if (!dQ.empty()) HIP_OK(up(ac->quad, dQ));
-    {
-        const std::vector<uint32_t> gb{groupBits[0], groupBits[1], groupBits[2], groupBits[3], groupBits[4], groupBits[5], groupBits[6], groupBits[7], 0u};
-        HIP_OK(up(ac->groupBits, gb));
-    }
-    // packed-word limits of the cooperative engines (kernels.h) and their LDS footprint; beyond them the per-lane wide kernel runs
-    ac->coopOK = coopOK && dTri.size() <= RDX_COOP_MAX_TRI_SLOTS - 1u && dW.size() < RDX_COOP_MAX_WIDE &&
-                 coop_lds_words(ac->coopNeed) <= RDX_LDS_WORDS_PER_WAVE_MAX &&
-                 pool_lds_words(std::max(ac->topNeed, ac->topFlatNeed), std::max({ac->blasNeed, ac->blasNeedAny, ac->quadNeed, ac->quadUnifiedNeed})) <= RDX_LDS_WORDS_PER_WAVE_MAX;
+    HIP_OK(up(ac->tnodes, L.tnodes.data(), L.tnodes.size()));
+    HIP_OK(up(ac->ctnodes, L.ctnodes.data(), L.ctnodes.size()));
+    HIP_OK(up(ac->insts, L.insts.data(), L.insts.size()));
+    HIP_OK(up(ac->bnodes, L.bnodes.data(), L.bnodes.size()));
+    HIP_OK(up(ac->tris, L.tris.data(), L.tris.size()));
+    HIP_OK(up(ac->wide, L.wide.data(), L.wide.size()));
+    if (!L.quad.empty()) HIP_OK(up(ac->quad, L.quad.data(), L.quad.size()));
+    HIP_OK(up(ac->groupBits, L.groupBits, 9));
+    // beyond the packed-word limits of the cooperative engines or their LDS footprint the per-lane wide kernel runs
+    const rdx_accel_scalars& S = ac->s;
+    ac->s.coopOK = S.coopOK && coop_lds_words(S.coopNeed) <= RDX_LDS_WORDS_PER_WAVE_MAX &&
+                   pool_lds_words(std::max(S.topNeed, S.topFlatNeed), std::max({S.blasNeed, S.blasNeedAny, S.quadNeed, S.quadUnifiedNeed})) <= RDX_LDS_WORDS_PER_WAVE_MAX;
     if (std::getenv("RDX_VERBOSE"))
-        std::fprintf(stderr, "[rdx] accel: %u top nodes, %u instances, %zu wide nodes, %zu triangle slots, stack need %u (cooperative kernel %u = top %u + BLAS %u; quad walk %u)\n",
-                     nTop, nInst, dW.size(), dTri.size(), ac->stackNeed, ac->coopNeed, ac->topNeed, ac->blasNeed, ac->quadNeed);
+        std::fprintf(stderr, "[rdx] accel: %zu top nodes, %u instances, %zu wide nodes, %zu triangle slots, stack need %u (cooperative kernel %u = top %u + BLAS %u; quad walk %u)\n",
+                     L.tnodes.size(), S.nInst, L.wide.size(), L.tris.size(), S.stackNeed, S.coopNeed, S.topNeed, S.blasNeed, S.quadNeed);
     ac->version = tb->version;
     if (acc(tb)) acc(tb)->release();
     acc(tb) = std::move(ac);
@@ -886,24 +266,24 @@ AccelView view_of(const rdx_buffer_s* tb, bool smallChunk = false)
     v.tnodes = acc(tb)->tnodes; v.ctnodes = acc(tb)->ctnodes; v.insts = acc(tb)->insts; v.bnodes = acc(tb)->bnodes; v.tris = acc(tb)->tris;
     v.wide = acc(tb)->wide;
     v.status = g.dStatus;
-    v.kernel = acc(tb)->sbtOffsets ? 0u : (g.kernel >= 2 && !acc(tb)->coopOK) ? 1u : (uint32_t)g.kernel;
-    v.stackNeed = acc(tb)->stackNeed;
-    v.coopNeed = acc(tb)->coopNeed;
+    v.kernel = acc(tb)->s.sbtOffsets ? 0u : (g.opt.kernel >= 2 && !acc(tb)->s.coopOK) ? 1u : (uint32_t)g.opt.kernel;
+    v.stackNeed = acc(tb)->s.stackNeed;
+    v.coopNeed = acc(tb)->s.coopNeed;
     // culled walk (docs/CULLED_WALK.md): with the conditioning gate that makes it exact it pays on the scene whose BVH lives in HBM
     // (10.4 M triangles: 66.2 vs 72.1 ms) and not on scenes that fit the caches (Sponza-class: 25.9 vs 25.3 ms exhaustive -- the
     // gate's ~45 vector instructions per node cost what the skipped triangle tests save) -- hence the size rule
-    v.cull = (v.kernel == 3 && (g.cull > 0 || (g.cull < 0 && acc(tb)->nWide >= RDX_CULL_AUTO_MIN_WIDE))) ? 1u : 0u;
-    v.topNeed = acc(tb)->topNeed; v.blasNeed = v.cull ? acc(tb)->blasNeedAny : acc(tb)->blasNeed;
-    v.topFlat = g.topFlat ? acc(tb)->topFlat : 0u;
-    v.numInsts = acc(tb)->nInst;
-    if (v.topFlat) v.topNeed = acc(tb)->topFlatNeed;          // flat top level: words per lane of the pending-instance bitmap
-    v.leafRoots = (v.topFlat && g.inlineLeafRoots && acc(tb)->leafRoots) ? 1u : 0u;
+    v.cull = (v.kernel == 3 && (g.opt.cull > 0 || (g.opt.cull < 0 && acc(tb)->s.nWide >= RDX_CULL_AUTO_MIN_WIDE))) ? 1u : 0u;
+    v.topNeed = acc(tb)->s.topNeed; v.blasNeed = v.cull ? acc(tb)->s.blasNeedAny : acc(tb)->s.blasNeed;
+    v.topFlat = g.opt.topFlat ? acc(tb)->s.topFlat : 0u;
+    v.numInsts = acc(tb)->s.nInst;
+    if (v.topFlat) v.topNeed = acc(tb)->s.topFlatNeed;          // flat top level: words per lane of the pending-instance bitmap
+    v.leafRoots = (v.topFlat && g.opt.inlineLeafRoots && acc(tb)->s.leafRoots) ? 1u : 0u;
     v.unifiedRoot = 0;
-    if (v.kernel == 3 && !v.topFlat && g.unifiedTree && acc(tb)->unifiedRoot) {
+    if (v.kernel == 3 && !v.topFlat && g.opt.unifiedTree && acc(tb)->s.unifiedRoot) {
         // unified tree: no top-level state per lane at all (one bitmap word stays allocated: the engine's flat-mode bookkeeping)
-        v.unifiedRoot = acc(tb)->unifiedRoot;
+        v.unifiedRoot = acc(tb)->s.unifiedRoot;
         v.topFlat = 1u; v.topNeed = 1u; v.leafRoots = 0u;
-        v.blasNeed = acc(tb)->unifiedNeed;
+        v.blasNeed = acc(tb)->s.unifiedNeed;
     }
     // exhaustive walk of the pool engine: quad records, two tree levels per fetch (option "quad"; the culled walk keeps the
     // wide records, whose children carry the normal cones)
@@ -911,13 +291,13 @@ AccelView view_of(const rdx_buffer_s* tb, bool smallChunk = false)
     // (not for the unified tree: its always-entered fan-outs gain nothing from a second level per item -- 39.4 vs 35.4 ms on the
     // 400-instance scene)
     v.quadWaves = 6u;
-    if (v.kernel == 3 && !v.cull && acc(tb)->quad && !v.unifiedRoot && (g.quad > 0 || (g.quad < 0 && smallChunk))) {
+    if (v.kernel == 3 && !v.cull && acc(tb)->quad && !v.unifiedRoot && (g.opt.quad > 0 || (g.opt.quad < 0 && smallChunk))) {
         v.quad = acc(tb)->quad;
-        v.quadWaves = (!smallChunk && pool_lds_words(v.topNeed, std::max(acc(tb)->quadNeed, v.blasNeed)) <= 1462u) ? 7u : 6u;      // (7 waves: 160 KB / 28)
+        v.quadWaves = (!smallChunk && pool_lds_words(v.topNeed, std::max(acc(tb)->s.quadNeed, v.blasNeed)) <= 1462u) ? 7u : 6u;      // (7 waves: 160 KB / 28)
         // (launches without a quad variant walk the wide records on the same view)
-        v.blasNeed = std::max(acc(tb)->quadNeed, v.blasNeed);
+        v.blasNeed = std::max(acc(tb)->s.quadNeed, v.blasNeed);
     }
-    v.groupCount = (v.topFlat && !v.unifiedRoot && g.groupInstances) ? acc(tb)->groupCount : 0u;
+    v.groupCount = (v.topFlat && !v.unifiedRoot && g.opt.groupInstances) ? acc(tb)->s.groupCount : 0u;
     v.groupBits = acc(tb)->groupBits;
     return v;
 }
@@ -1064,7 +444,7 @@ int scene_args(SceneArgs& sc)
     // slots 11 / 12: texture array + sampler.  Read only when option "textures" is on (the live reference shader has its
     // reads stubbed to 0, samples/shader.cl:379-445)
     sc.tex = TexView{nullptr, 0, 0, 0, 0};
-    if (g.textures && g.slots[11] && known_buffer(g.slots[11])) {
+    if (g.opt.textures && g.slots[11] && known_buffer(g.slots[11])) {
         const auto* img = static_cast<const rdx_buffer_s*>(g.slots[11]);
         if (img->imgW && img->imgH && img->imgLayers) {
             uint32_t bits = TEX_ADDR_REPEAT << TEX_ADDR_SHIFT;     // no sampler bound: repeat + nearest
@@ -1097,8 +477,8 @@ struct StageTimer {
         if (used == pool.size()) { hipEvent_t e; HIP_IGN(hipEventCreate(&e)); pool.push_back(e); }
         return pool[used++];
     }
-    void begin(float* dst, hipStream_t st = nullptr) { if (!g.profiling) return; Span s{get(), get(), dst}; HIP_IGN(hipEventRecord(s.a, st ? st : g.stream)); spans.push_back(s); }
-    void end(hipStream_t st = nullptr) { if (!g.profiling) return; HIP_IGN(hipEventRecord(spans.back().b, st ? st : g.stream)); }
+    void begin(float* dst, hipStream_t st = nullptr) { if (!g.opt.profiling) return; Span s{get(), get(), dst}; HIP_IGN(hipEventRecord(s.a, st ? st : g.stream)); spans.push_back(s); }
+    void end(hipStream_t st = nullptr) { if (!g.opt.profiling) return; HIP_IGN(hipEventRecord(spans.back().b, st ? st : g.stream)); }
     void resolve()
     {
         for (auto& s : spans) { float ms = 0; HIP_IGN(hipEventElapsedTime(&ms, s.a, s.b)); *s.dst += ms; }
@@ -1894,7 +1274,7 @@ extern "C" rdx_shader rdx_shader_module_create(const char* code, uint32_t size, 
         // 3b. anything else: the program's own raygen, as a megakernel.
         constexpr uint64_t kStockReducedHash = RDX_STOCK_REDUCED_HASH;     // of samples/shader.cl, by tools/stock_shader_hash.py
         //     "user_stages" 2: the caller asserts it for a program written from scratch (the raygen text is then not looked at).
-        const bool stages = g0.userStages == 2 || (g0.userStages == 1 && fnv1a64_nows(blank_stage_bodies(text)) == kStockReducedHash);
+        const bool stages = g0.opt.userStages == 2 || (g0.opt.userStages == 1 && fnv1a64_nows(blank_stage_bodies(text)) == kStockReducedHash);
         if (stages) {
             // the stage kernel replaces the program's raygen: its body and that of the stock skeleton's camera helper go (dead
             // code there, and their get_global_id(0) has no `sceneData` in scope for the stage-mode macro)
@@ -1902,7 +1282,7 @@ extern "C" rdx_shader rdx_shader_module_create(const char* code, uint32_t size, 
             blank_bodies(t, {"raygen", "generateRay"});
             std::string err2;
             s->program = compile_user_shader(t, g0.shaderInclude, arch, true, err2);
-            if (!s->program && g0.userStages == 2) { fail_str(err2); return nullptr; }
+            if (!s->program && g0.opt.userStages == 2) { fail_str(err2); return nullptr; }
         }
         if (!s->program) s->program = compile_user_shader(text, g0.shaderInclude, arch, false, err);
         if (!s->program) { fail_str(err); return nullptr; }
@@ -1993,34 +1373,34 @@ extern "C" int rdx_unpack_tiles_multi(const rdx_buffer* packed, uint32_t first_r
 // ------------------------------------------------------------------------------------------------
 // TraceRays
 // ------------------------------------------------------------------------------------------------
-extern "C" int rdx_set_profiling(int on) { g.profiling = on != 0; return 0; }
+extern "C" int rdx_set_profiling(int on) { g.opt.profiling = on != 0; return 0; }
 extern "C" int rdx_set_option(const char* name, int64_t value)
 {
     if (!name) return fail("rdx_set_option: null name");
-    if (!strcmp(name, "chunk_paths")) { if (value < 1) return fail("chunk_paths must be >= 1"); g.chunkPaths = value; return 0; }
-    if (!strcmp(name, "count_visits")) { g.countVisits = value != 0; return 0; }
-    if (!strcmp(name, "groups")) { if (value < 0 || value > Context::MAX_GROUPS) return fail("groups must be 0 (auto) or 1..4"); g.groupsOpt = (int)value; return 0; }
-    if (!strcmp(name, "overlap")) { if (value < 0 || value > 1) return fail("overlap must be 0 or 1"); g.overlap = (int)value; return 0; }
-    if (!strcmp(name, "pipeline")) { if (value < 0 || value > 1) return fail("pipeline must be 0 (staged) or 1 (paths)"); g.pathMode = (int)value; return 0; }
-    if (!strcmp(name, "fuse")) { if (value < -1 || value > 1) return fail("fuse must be -1 (auto), 0 or 1"); g.fuse = (int)value; return 0; }
-    if (!strcmp(name, "user_shader_local_size")) { if (value < 1 || value > 1024) return fail("user_shader_local_size must be 1..1024"); g.userLocalSize = (int)value; return 0; }
-    if (!strcmp(name, "sort")) { g.sortRays = value < 0 ? -1 : (value != 0); return 0; }
-    if (!strcmp(name, "textures")) { g.textures = value != 0; return 0; }
-    if (!strcmp(name, "cull")) { g.cull = value < 0 ? -1 : (value != 0); return 0; }
-    if (!strcmp(name, "top_flat")) { g.topFlat = value != 0; return 0; }
-    if (!strcmp(name, "group_instances")) { g.groupInstances = value != 0; return 0; }
-    if (!strcmp(name, "unified_tree")) { g.unifiedTree = value != 0; return 0; }
+    if (!strcmp(name, "chunk_paths")) { if (value < 1) return fail("chunk_paths must be >= 1"); g.opt.chunkPaths = value; return 0; }
+    if (!strcmp(name, "count_visits")) { g.opt.countVisits = value != 0; return 0; }
+    if (!strcmp(name, "groups")) { if (value < 0 || value > Context::MAX_GROUPS) return fail("groups must be 0 (auto) or 1..4"); g.opt.groupsOpt = (int)value; return 0; }
+    if (!strcmp(name, "overlap")) { if (value < 0 || value > 1) return fail("overlap must be 0 or 1"); g.opt.overlap = (int)value; return 0; }
+    if (!strcmp(name, "pipeline")) { if (value < 0 || value > 1) return fail("pipeline must be 0 (staged) or 1 (paths)"); g.opt.pathMode = (int)value; return 0; }
+    if (!strcmp(name, "fuse")) { if (value < -1 || value > 1) return fail("fuse must be -1 (auto), 0 or 1"); g.opt.fuse = (int)value; return 0; }
+    if (!strcmp(name, "user_shader_local_size")) { if (value < 1 || value > 1024) return fail("user_shader_local_size must be 1..1024"); g.opt.userLocalSize = (int)value; return 0; }
+    if (!strcmp(name, "sort")) { g.opt.sortRays = value < 0 ? -1 : (value != 0); return 0; }
+    if (!strcmp(name, "textures")) { g.opt.textures = value != 0; return 0; }
+    if (!strcmp(name, "cull")) { g.opt.cull = value < 0 ? -1 : (value != 0); return 0; }
+    if (!strcmp(name, "top_flat")) { g.opt.topFlat = value != 0; return 0; }
+    if (!strcmp(name, "group_instances")) { g.opt.groupInstances = value != 0; return 0; }
+    if (!strcmp(name, "unified_tree")) { g.opt.unifiedTree = value != 0; return 0; }
     if (!strcmp(name, "gpu_build") || !strcmp(name, "gpu_build_min")) {
         if (!strcmp(name, "gpu_build")) g0.gpuBuild = value != 0; else g0.gpuBuildMin = value > 0 ? value : 32768;
         set_gpu_binner((g0.initialized && g0.gpuBuild) ? &g_hipBinner : nullptr, (size_t)g0.gpuBuildMin);
         return 0;
     }
-    if (!strcmp(name, "sort_min_paths")) { g.sortMinPaths = value > 0 ? value : (3ll << 19); return 0; }
-    if (!strcmp(name, "small_chunk_paths")) { g.smallChunkPaths = value > 0 ? value : (9ll << 19); return 0; }
-    if (!strcmp(name, "quad")) { g.quad = value < 0 ? -1 : (value != 0); return 0; }
-    if (!strcmp(name, "user_stages")) { g.userStages = value > 2 ? 1 : (int)value; return 0; }
-    if (!strcmp(name, "inline_leaf_roots")) { g.inlineLeafRoots = value != 0; return 0; }
-    if (!strcmp(name, "kernel")) { if (value < 0 || value > 3) return fail("kernel must be 0, 1, 2 or 3"); g.kernel = (int)value; return 0; }
+    if (!strcmp(name, "sort_min_paths")) { g.opt.sortMinPaths = value > 0 ? value : (3ll << 19); return 0; }
+    if (!strcmp(name, "small_chunk_paths")) { g.opt.smallChunkPaths = value > 0 ? value : (9ll << 19); return 0; }
+    if (!strcmp(name, "quad")) { g.opt.quad = value < 0 ? -1 : (value != 0); return 0; }
+    if (!strcmp(name, "user_stages")) { g.opt.userStages = value > 2 ? 1 : (int)value; return 0; }
+    if (!strcmp(name, "inline_leaf_roots")) { g.opt.inlineLeafRoots = value != 0; return 0; }
+    if (!strcmp(name, "kernel")) { if (value < 0 || value > 3) return fail("kernel must be 0, 1, 2 or 3"); g.opt.kernel = (int)value; return 0; }
     return fail("rdx_set_option: unknown option '%s'", name);
 }
 extern "C" int rdx_get_bounce_counts(uint64_t* out, uint32_t n)
@@ -2072,7 +1452,7 @@ static int trace_rays_device(uint32_t width, uint32_t height)
         g.stats.pixels = nPix;
         HIP_OK(hipEventRecord(g.evA, g.stream));
         std::string err;
-        if (launch_user_shader(g.pipeline->program, g.stream, ptrs, (uint32_t)nPix, (uint32_t)g.userLocalSize, err)) return fail_str(err);
+        if (launch_user_shader(g.pipeline->program, g.stream, ptrs, (uint32_t)nPix, (uint32_t)g.opt.userLocalSize, err)) return fail_str(err);
         HIP_OK(hipEventRecord(g.evB, g.stream));
         HIP_OK(hipStreamSynchronize(g.stream));
         HIP_OK(hipEventElapsedTime(&g.stats.ms_total, g.evA, g.evB));
@@ -2111,17 +1491,17 @@ static int trace_rays_device(uint32_t width, uint32_t height)
     std::memset(&g.stats, 0, sizeof g.stats);
     std::memset(g.bounceCounts, 0, sizeof g.bounceCounts);
     g.stats.pixels = P;
-    unsigned long long* visit = g.countVisits ? g.dVisit : nullptr;
+    unsigned long long* visit = g.opt.countVisits ? g.dVisit : nullptr;
     if (visit) HIP_OK(hipMemsetAsync(g.dVisit, 0, 64 * 8 * sizeof(unsigned long long), g.stream));
 
     HIP_OK(hipEventRecord(g.evA, g.stream));
     const uint32_t batch = rt.batchSize;
     uint32_t samplesPerChunk = batch;
-    if (P && (uint64_t)batch * P > (uint64_t)g.chunkPaths) samplesPerChunk = (uint32_t)std::max<int64_t>(1, g.chunkPaths / P);
+    if (P && (uint64_t)batch * P > (uint64_t)g.opt.chunkPaths) samplesPerChunk = (uint32_t)std::max<int64_t>(1, g.opt.chunkPaths / P);
     if (P && batch) { if (ensure_samples((size_t)samplesPerChunk * P)) return -1; }
     // quad records (two tree levels per fetch, kernels at 4 waves per SIMD) for chunks whose launches do not fill the chip --
     // shards of a multi-GPU frame, low resolutions -- where a launch lasts as long as its longest chain of dependent fetches
-    const AccelView av = view_of(bTlas, (uint64_t)samplesPerChunk * P <= (uint64_t)g.sortMinPaths);
+    const AccelView av = view_of(bTlas, (uint64_t)samplesPerChunk * P <= (uint64_t)g.opt.sortMinPaths);
 
     const float tmin = 0.001f, tmax = 1000.0f;      // shader.cl:235-236, 500
     for (uint32_t s0 = 0; s0 < batch && P; s0 += samplesPerChunk) {
@@ -2133,24 +1513,23 @@ static int trace_rays_device(uint32_t width, uint32_t height)
         // The chunk's samples are split into groups with their own streams and counts, each launching 1/nGroups of
         // the resident grid, so that one group's launches run inside the ramp and drain of the other's
         // (kernels.hip: set_grid_share).  Two groups: -5 % at 1/8, -3 % at 1/2 of a 1080p x 4 spp frame; four: slower.
-        const bool small = chunkPaths <= (uint64_t)g.smallChunkPaths && sc_n >= 2 && av.kernel >= 2;
-        const uint32_t wantGroups = visit ? 1u : g.groupsOpt ? (uint32_t)g.groupsOpt : small ? 2u : 1u;
+        const bool small = chunkPaths <= (uint64_t)g.opt.smallChunkPaths && sc_n >= 2 && av.kernel >= 2;
+        const uint32_t wantGroups = visit ? 1u : g.opt.groupsOpt ? (uint32_t)g.opt.groupsOpt : small ? 2u : 1u;
         int nGroups = (int)std::min<uint32_t>(wantGroups, sc_n);
         set_grid_share((uint32_t)nGroups);
         g.stats.groups = (uint32_t)nGroups;
         // Small chunks (multi-GPU shards, low resolutions): a traversal launch costs ~0.2 ms of ramp + tail
         // whatever its size (tools/trav_scale.py), so shadow(d) and extend(d+1) -- same ray count, disjoint
         // streams -- go into ONE cooperative launch: 9 traversal launches per depth-8 frame instead of 16.
-        const bool fuse = g.fuse != 0 && !visit && av.kernel >= 2;
-        (void)small;
-        const bool overlap = g.overlap == 1 && !fuse && !visit;
+        const bool fuse = g.opt.fuse != 0 && !visit && av.kernel >= 2;
+        const bool overlap = g.opt.overlap == 1 && !fuse && !visit;
         // per-bounce ray sort (north star; kernels.h): only the cooperative engines hand rays out by index
         const bool sortOn = !visit && av.kernel >= 2 &&
-                            (g.sortRays > 0 || (g.sortRays < 0 && (acc(bTlas)->nWide >= RDX_SORT_AUTO_MIN_WIDE ||
-                                                                    (acc(bTlas)->nWide >= RDX_SORT_AUTO_MIN_WIDE_FULL && chunkPaths > (uint64_t)g.sortMinPaths))));
+                            (g.opt.sortRays > 0 || (g.opt.sortRays < 0 && (acc(bTlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE ||
+                                                                    (acc(bTlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE_FULL && chunkPaths > (uint64_t)g.opt.sortMinPaths))));
         SortBox sortBox;
         for (int k = 0; k < 3; ++k) {
-            const float lo = acc(bTlas)->sceneLo[k], ext = acc(bTlas)->sceneHi[k] - lo;
+            const float lo = acc(bTlas)->s.sceneLo[k], ext = acc(bTlas)->s.sceneHi[k] - lo;
             sortBox.lo[k] = lo; sortBox.inv[k] = ext > 0.0f ? 16.0f / ext : 0.0f;
         }
         HIP_OK(hipEventRecord(g.evChunk, g.stream));          // everything before this chunk (previous accumulate) is done first
@@ -2215,7 +1594,7 @@ static int trace_rays_device(uint32_t width, uint32_t height)
             g.stats.launches_extend += maxDepth; g.stats.launches_shadow += maxDepth;
             continue;
         }
-        if (g.pathMode == 1 && !visit && av.kernel == 3 && maxDepth > 0) {
+        if (g.opt.pathMode == 1 && !visit && av.kernel == 3 && maxDepth > 0) {
             // ---- whole paths in one persistent launch (k_path_pool) + accumulate ----
             Context::Group& G = g.groups[0];
             const uint32_t n0 = sc_n * P;
@@ -2294,7 +1673,7 @@ static int trace_rays_device(uint32_t width, uint32_t height)
                     // per-bounce ray sort: the traversal launch below hands its rays out in (octant, Morton cell) order
                     if (!G.sortBins) HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.sortBins), (size_t)ray_sort_tiles_words() * 4));
                     g_timer.begin(&g.stats.ms_sort, G.s0);
-                    launch_ray_sort_tiles(G.s0, ps, G.dCounts + d + 1, n0, sortBox, G.sortBins, G.permE, acc(bTlas)->nWide >= RDX_SORT_AUTO_MIN_WIDE);
+                    launch_ray_sort_tiles(G.s0, ps, G.dCounts + d + 1, n0, sortBox, G.sortBins, G.permE, acc(bTlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE);
                     g_timer.end(G.s0);
                     ps.permS = G.permE; ps.permE = G.permE;
                 }
@@ -2406,10 +1785,7 @@ extern "C" int rdx_trace_rays(uint32_t, uint32_t, uint32_t, uint32_t width, uint
         Context& c = *g_dev[d];
         std::memcpy(c.slots, g0.slots, sizeof c.slots);
         c.nslots = g0.nslots; c.pipeline = g0.pipeline;
-        c.groupsOpt = g0.groupsOpt; c.fuse = g0.fuse; c.pathMode = g0.pathMode; c.chunkPaths = g0.chunkPaths;
-        c.countVisits = g0.countVisits; c.profiling = g0.profiling; c.inlineLeafRoots = g0.inlineLeafRoots; c.cull = g0.cull;
-        c.textures = g0.textures; c.topFlat = g0.topFlat; c.kernel = g0.kernel; c.overlap = g0.overlap; c.groupInstances = g0.groupInstances; c.unifiedTree = g0.unifiedTree;
-        c.sortRays = g0.sortRays; c.quad = g0.quad; c.smallChunkPaths = g0.smallChunkPaths; c.sortMinPaths = g0.sortMinPaths;
+        c.opt = g0.opt;
     }
     for (int d = 0; d < n; ++d) {
         tl_ctx = g_dev[d]; tl_dev = d;
@@ -2568,5 +1944,27 @@ extern "C" int rdx_pcg3d_batch(const uint32_t* in3, float* out3, uint32_t n)
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(g.stream));
     if (n) HIP_OK(hipMemcpy(out3, dO.p, 12 * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int rdx_debug_accel_layout(const void* blob, size_t size, int quad, int cull, rdx_accel_scalars* scalars,
+                                      void* const* arrays, size_t* bytes)
+{
+    if (!blob) return fail("rdx_debug_accel_layout: no blob");
+    if (arrays && !bytes) return fail("rdx_debug_accel_layout: arrays need their capacities in bytes[]");
+    AccelLayout L;
+    std::string err;
+    if (derive_accel_layout(blob, size, AccelOptions{quad, cull}, L, err)) return fail_str(err);
+    if (scalars) *scalars = L.s;
+    auto view = [](const auto& v) { return std::make_pair(static_cast<const void*>(v.data()), v.size() * sizeof(v[0])); };
+    const std::pair<const void*, size_t> arr[8] = {view(L.tnodes), view(L.ctnodes), view(L.insts), view(L.bnodes), view(L.tris), view(L.wide),
+                                                   view(L.quad), {L.groupBits, sizeof L.groupBits}};
+    for (int i = 0; i < 8 && bytes; ++i) {
+        if (arrays && arrays[i]) {
+            if (bytes[i] < arr[i].second) return fail("rdx_debug_accel_layout: array %d needs %zu bytes", i, arr[i].second);
+            if (arr[i].second) std::memcpy(arrays[i], arr[i].first, arr[i].second);
+        }
+        bytes[i] = arr[i].second;
+    }
     return 0;
 }

@@ -75,7 +75,7 @@ struct alignas(16) DInst {        // 224 B
 // Child descriptor in full:
 //   d1 = bit 31 leaf | bits 24-30 c7 | byte 2 cone y | byte 1 cone x | byte 0 cone z      c7 = triangle count (leaf) or cone T (inner)
 //   d0 = leaf: cone T << 25 | first triangle slot (25 bits);   inner: DWide index
-// The NORMAL CONE of a child (rdx_runtime.cpp derive_accel, kernels.hip "culled walk") bounds how close to parallel a ray can
+// The NORMAL CONE of a child (accel_layout.cpp, kernels.hip "culled walk") bounds how close to parallel a ray can
 // be to any triangle of the leaf / below the inner child: axis byte b = round(127.5 + 127 a), read with v_cvt_f32_ubyte0/1/2;
 // threshold T (7 bits): the culled walk may skip the child only for rays with |d . (b - 127.5)| >= T |d|; T = 127: never.
 enum : uint32_t { WIDE_LEAF = 0x80000000u, WIDE_MAX_LEAF_TRIS = 127u, WIDE_SLOT_BITS = 25u, WIDE_SLOT_MASK = (1u << 25) - 1u, WIDE_CONE_NEVER = 127u };
@@ -99,7 +99,7 @@ struct alignas(16) DWide {        // 64 B
     float rmin[3]; uint32_t rd0;
     float rmax[3]; uint32_t rd1;
 };
-// "Quad" record of the pool engine's exhaustive walk (rdx_runtime.cpp derive_accel, traverse_pool.h): record i belongs to the
+// "Quad" record of the pool engine's exhaustive walk (accel_layout.cpp, traverse_pool.h): record i belongs to the
 // same inner node N as DWide record i and holds, for each of N's two children c, one HALF of two entries:
 //   * c is an inner node whose box is exactly the union of its children's boxes (always, in a tree the reference's builder
 //     made): the two children of c -- N's grandchildren -- each with its own box.  c itself is never fetched: a grandchild g's
@@ -114,5 +114,12 @@ struct alignas(16) DWide {        // 64 B
 enum : uint32_t { QUAD_PAIR = 1u };
 struct alignas(16) DQuad { DWide half[2]; };
 static_assert(sizeof(DWide) == 64 && sizeof(DQuad) == 128 && sizeof(DInst) == 224, "derived layout");
+
+// limits of the cooperative engines' packed words, shared by the kernels (traverse_coop.h) and the host's fallback rule
+// (accel_layout.cpp)
+constexpr uint32_t RDX_COOP_MAX_TRI_SLOTS = 1u << 25;    // queue entry: lane << 26 | parity << 25 | absolute triangle slot
+constexpr uint32_t RDX_COOP_MAX_WIDE = 1u << 26;         // pool item: lane << 26 | wide-node index
+constexpr uint32_t RDX_COOP_MAX_INSTANCES = 1u << 10;    // key: instance slot << 22 | BLAS-local triangle slot
+constexpr uint32_t RDX_COOP_MAX_BLAS_TRIS = 1u << 22;
 
 } // namespace rdx

@@ -49,7 +49,7 @@
 //
 // LDS per wave = (stack need + 18) * 256 B: the stack [need][64], the 512-entry queue ring, the parked rays
 // [7][64], best[64] (64-bit) and the helper counts [64].  Residency is LDS-bound and the kernel lives on residency
-// (tools/occupancy_probe.sh), hence the small stack need (derive_accel: smaller subtree first) and the single slot.
+// (tools/occupancy_probe.sh), hence the small stack need (accel_layout.cpp: smaller subtree first) and the single slot.
 //
 // Any-hit (shadow) rays use the same machinery and drop their remaining work as soon as a candidate
 // has been published.
@@ -67,7 +67,7 @@ static_assert(COOP_QCAP >= 512u && (COOP_QCAP & (COOP_QCAP - 1u)) == 0u, "queue 
 #define COOP_LANE_SHIFT 26u            // queue entry = walking lane << 26 | instance parity << 25 | absolute triangle slot
 #define COOP_PAR_SHIFT 25u
 #define COOP_SLOT_MASK ((1u << 25) - 1u)
-static_assert(COOP_SLOT_MASK + 1u == RDX_COOP_MAX_TRI_SLOTS, "the host's fallback rule (derive_accel) must match the queue entry layout");
+static_assert(COOP_SLOT_MASK + 1u == RDX_COOP_MAX_TRI_SLOTS, "the host's fallback rule (accel_layout.cpp) must match the queue entry layout");
 #define COOP_INST_SHIFT 22u            // key low word = instance slot << 22 | BLAS-local triangle slot
 #define COOP_LOCAL_MASK ((1u << 22) - 1u)
 static_assert((1u << COOP_INST_SHIFT) == RDX_COOP_MAX_BLAS_TRIS && (RDX_COOP_MAX_INSTANCES << COOP_INST_SHIFT) == 0u, "key layout");

@@ -73,7 +73,7 @@ __host__ __device__ inline uint32_t pool_words_per_wave(uint32_t topNeed, uint32
 
 #define POOL_LANE_SHIFT 26u            // pool item = owning lane << 26 | wide-node index
 #define POOL_NODE_MASK ((1u << POOL_LANE_SHIFT) - 1u)
-static_assert(POOL_NODE_MASK + 1u >= RDX_COOP_MAX_WIDE, "the host's fallback rule (derive_accel) must match the pool item layout");
+static_assert(POOL_NODE_MASK + 1u >= RDX_COOP_MAX_WIDE, "the host's fallback rule (accel_layout.cpp) must match the pool item layout");
 #define POOL_INBLAS 0xfffffffeu        // top-level cursor of a lane whose instance is in the pool
 #ifndef POOL_TEST_MIN
 #define POOL_TEST_MIN 16u              // queued triangle tests a test step waits for (final engine, with POOL_REPEAT 16: 16 / 24 / 32 -> 24.09 / 24.11 / 24.31 ms, Sponza-class)
@@ -306,7 +306,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
     // entries -- a quarter to a tenth of the LDS (25 instances: 1 word instead of 9 per lane), which is residency.
     const bool flatTop = A.topFlat != 0u;
     // flat mode: tsp = pending instances (bits 0-9) | of which in the shared-transform group (bits 10-19) | bit 31: the lane's ray
-    // slot holds the group's object-space ray.  Shared-transform group (rdx_runtime.cpp derive_accel): instances whose inverse
+    // slot holds the group's object-space ray.  Shared-transform group (accel_layout.cpp): instances whose inverse
     // matrices are bit-identical have the same object-space ray, so a lane enters ALL of them on one ray slot -- without waiting,
     // between two of them, for the subtree and the queued tests of the first to drain -- before it turns to the others.
 #define POOL_ILEFT (tsp & 0x3ffu)
@@ -495,7 +495,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
             COOP_STAT(4, nTop);
             if (REC != 1) { if (anyHit && isTop && L.best[lane] != ~0ull) POOL_DROP(); }
             if (A.unifiedRoot != 0u) {
-                // Unified tree (rdx_runtime.cpp derive_accel): top level, instances and BLASes are ONE tree of wide records on ONE
+                // Unified tree (accel_layout.cpp): top level, instances and BLASes are ONE tree of wide records on ONE
                 // object-space ray -- every instance has the identity transform.  The ray is taken through the (identity) inverse
                 // with the reference's expressions, goes into the lane's slot, and one item -- the super-root -- enters the pool.
                 bool push = false;
@@ -630,7 +630,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                             const uint32_t count = w.x & 0x7fffffffu;
                             if (INL && w.w != 0u) {
                                 // this leaf holds instances whose BLAS is one small leaf (a quad: 2 triangles; flagged by
-                                // derive_accel in the node's spare word).  They are dealt with on the spot: matrix and
+                                // accel_layout.cpp in the node's spare word).  They are dealt with on the spot: matrix and
                                 // triangles are the same for all lanes of the step (scalar loads), each lane transforms its
                                 // own ray with the reference's expressions and runs the branch-free Moeller-Trumbore -- no
                                 // instance step, no parked ray, no queued tests for them.
@@ -758,7 +758,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                     POOL_RB(rays, lane) = make_float4(R.d.x, R.d.y, R.d.z, __uint_as_float(((R.exactOnly ? 1u : 0u) | (anyHit ? 4u : 0u)) << 29));
                     if (grpNext) tsp |= POOL_SLOTGROUP;
                 }
-                if (rdsc.y & WIDE_LEAF) {      // (never an instance of the group: derive_accel keeps leaf roots out of it)
+                if (rdsc.y & WIDE_LEAF) {      // (never an instance of the group: accel_layout.cpp keeps leaf roots out of it)
                     cntE = wide_count(rdsc.y); stE = wide_slot(rdsc.x);
                     POOL_TPOP();
                 } else {
@@ -846,7 +846,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                     const float4 c0 = qp[4], c1 = qp[5], e0 = qp[6], e1 = qp[7];
                     if (live) quad_half(Q, c0, c1, e0, e1, pushC, pushE, runC, runE);
                 }
-                {   // entry A ends on top: the host put the subtree with the smallest pool need there (derive_accel)
+                {   // entry A ends on top: the host put the subtree with the smallest pool need there (accel_layout.cpp)
                     const unsigned long long mE = __ballot(pushE != COOP_NONE), mC = __ballot(pushC != COOP_NONE);
                     const unsigned long long mB = __ballot(pushB != COOP_NONE), mA = __ballot(pushA != COOP_NONE);
                     uint32_t at = poolTop;

@@ -399,6 +399,42 @@ def TraceBatch(tlas, origins, dirs, tmin=0.001, tmax=1000.0, sbtRecordOffset=1, 
     return (out, visit) if count_visits else out
 
 
+# the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
+_DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
+_DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),
+                   ("rmax", "<f4", 3), ("rd1", "<u4")])
+ACCEL_ARRAYS = (("tnodes", _DNODE), ("ctnodes", _DNODE),
+                ("insts", np.dtype([("inv", "<f4", 16), ("fwd", "<f4", 16), ("SBTOffset", "<u4"), ("instanceID", "<u4"),
+                                    ("customInstanceID", "<u4"), ("blasRoot", "<u4"), ("rootDesc0", "<u4"), ("rootDesc1", "<u4"),
+                                    ("_p0", "<u4"), ("_p1", "<u4"), ("rootMin", "<f4", 4), ("rootMax", "<f4", 4),
+                                    ("worldMin", "<f4", 4), ("worldMax", "<f4", 4)])),
+                ("bnodes", _DNODE),
+                ("tris", np.dtype([("v0", "<f4", 3), ("primID", "<u4"), ("e1", "<f4", 3), ("_p0", "<u4"), ("e2", "<f4", 3), ("_p1", "<u4")])),
+                ("wide", _DWIDE), ("quad", np.dtype([("half", _DWIDE, 2)])), ("groupBits", np.dtype("<u4")))
+
+
+def DebugAccelLayout(blob, quad=1, cull=-1, lib=None):
+    """Test seam: the traversal layout derived from a TLAS blob under options "quad" / "cull", on the host (no device, no
+    Platform) -> (dict of the rdx_accel_scalars members, dict name -> structured array).  `lib`: another build of the library."""
+    L = lib if lib is not None else _lib.lib()
+    blob = bytes(blob)
+    sc = _lib.rdx_accel_scalars()
+    sizes = (C.c_size_t * 8)()
+
+    def call(*args):
+        if L.rdx_debug_accel_layout(blob, len(blob), int(quad), int(cull), *args) != 0:
+            raise RadianceError(L.rdx_last_error().decode("utf-8", "replace"))
+    call(C.byref(sc), None, sizes)
+    arrays = {}
+    for (name, dt), n in zip(ACCEL_ARRAYS, sizes):
+        assert n % dt.itemsize == 0, (name, n)
+        arrays[name] = np.zeros(n // dt.itemsize, dt)
+    ptrs = (C.c_void_p * 8)(*[a.ctypes.data if a.size else None for a in arrays.values()])
+    call(None, ptrs, sizes)
+    scalars = {n: (list(getattr(sc, n)) if n.startswith("scene") else int(getattr(sc, n))) for n, _ in sc._fields_}
+    return scalars, arrays
+
+
 def MaterialBatch(hits, ray_dirs, pixels, frame_ids, depths):
     h = np.ascontiguousarray(hits, HIT_DTYPE)
     d = np.ascontiguousarray(ray_dirs, np.float32).reshape(-1, 3)

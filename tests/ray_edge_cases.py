@@ -60,7 +60,7 @@ def _moved(mesh, dx, dy, dz):
 def edges_inst(scenes, identity_group=False):
     """Instanced scene: shared BLASes under a non-uniformly scaled and under a mirrored (negative determinant) transform, and three
     DISTINCT meshes (a BLAS of its own each, inner-node roots) under ONE bit-identical transform -- the product's transform group
-    (rdx_runtime.cpp derive_accel: instances with bit-identical inverse matrices whose BLAS has a single user).  With
+    (accel_layout.cpp: instances with bit-identical inverse matrices whose BLAS has a single user).  With
     `identity_group` that shared transform is the identity (identity group).  14 instances: a top level far below 64 nodes."""
     s = scenes.Scene("edges_inst_id" if identity_group else "edges_inst")
     ball = s.add_mesh(scenes.icosphere(2, 0.45))

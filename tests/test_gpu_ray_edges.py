@@ -26,10 +26,10 @@ shader/radiance.cl: the user-program test fails (433 of 1024 rays of c1 / A / (0
 skip), which is the reference's arithmetic by construction; it costs speed, not answers.
 
 Transform groups: no statistic exposes the group the product forms on edges_inst, so it was shown indirectly, with two local
-mutations (never committed).  (a) derive_accel writing the group's FIRST member into the `_p0` instance slot of every member's
+mutations (never committed).  (a) the layout derivation (accel_layout.cpp) writing the group's FIRST member into the `_p0` instance slot of every member's
 triangles: every kernel-3 cell of edges_inst / edges_inst_id then fails on instanceIndex (11 -> 10, 12 -> 10), so a group of
 these three instances forms -- but with group_instances 0 as well as 1, because the pool's test step takes a candidate's instance
-from the triangle record whenever derive_accel wrote one, whatever the launch option says.  (b) the instance step's "slot already
+from the triangle record whenever the derivation wrote one, whatever the launch option says.  (b) the instance step's "slot already
 holds the group's ray" branch (traverse_pool.h) made to miss the root box: exactly the cells with kernel 3, group_instances 1 and
 top_flat 1 fail, every cell with group_instances 0 (or top_flat 0, or kernel 2 / 1) passes: the option is exercised, and the
 cells tell its two settings apart.

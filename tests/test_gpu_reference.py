@@ -236,7 +236,7 @@ def test_user_stage_functions_the_pipeline_cannot_serve_are_refused(mods):
 def test_many_instance_scene_identical_to_reference(mods, ref):
     """The Sponza-class scene as a one-instance-per-mesh loader delivers it (tools/sceneBuilder.cpp:287-315): 400 instances,
     a top level of ~200 nodes -- too large for the flat top-level step, so the pool engine walks top level, instances and BLASes
-    as ONE tree (rdx_runtime.cpp "unified tree").  HitData of 64 k primary + scattered rays (closest and any hit) and a 640x360
+    as ONE tree (accel_layout.cpp "unified tree").  HitData of 64 k primary + scattered rays (closest and any hit) and a 640x360
     x 2 spp x depth 8 frame against the reference's own kernels, with the unified tree and with the walked top level."""
     rd, scenes = mods
     s = scenes.CONFIGS["c2_atrium_400"](640, 360, 2, 8)
