@@ -233,6 +233,33 @@ int         rdx_set_profiling(int on);
  * (experimental: shadow rays on a second stream when "fuse" is 0; off by default) */
 int         rdx_set_option(const char* name, int64_t value);
 
+/* Ray queries on device memory: `n` rays of the caller's own, read from `rays` at byte `rays_offset`, against `tlas`; one record
+ * per ray written to `hits` at byte `hits_offset`.  Both are device buffers (rdx_buffer_create, or rdx_buffer_wrap around e.g. a
+ * torch tensor): nothing is staged through the host and nothing is allocated per call; the call blocks like every call of this ABI
+ * (work the caller has queued on streams of its own must be complete before).  Every ray carries its OWN interval: a candidate
+ * at distance t is accepted iff t > 0 && t > tmin && t < tmax, the reference's rule (radiance.cl:90-91) with the ray's bounds -- a
+ * NaN bound accepts nothing; the shadow ray towards a point light has tmax = the distance to it, an ambient-occlusion ray its
+ * radius.  RDX_QUERY_CLOSEST is the walk of traceRay() with sbtRecordOffset 1: on a hit, t / b1 / b2 are the bits of
+ * HitData.distance / barycentric[1] / barycentric[2] and the four integers the HitData fields of the same name (hitPoint is
+ * origin + t * direction in the instance's space, barycentric[0] is 1 - b1 - b2, the transform is the instance's: all the
+ * caller's to derive).  RDX_QUERY_ANY is the walk of sbtRecordOffset 2, which ends at the first accepted candidate, whichever it
+ * is: only `hit` is meaningful.  On a miss, and for RDX_QUERY_ANY, every field but `hit` is 0.
+ * The engine is chosen as for rdx_trace_batch mode 0, by options "kernel", "cull", "quad", "group_instances", "unified_tree",
+ * "top_flat" and "inline_leaf_roots": the pool engine (kernel 3) in a variant that keeps each ray's interval in LDS next to the
+ * ray; kernel 2 is served by the per-lane wide-node kernel of kernel 1, as are scenes the pool engine does not
+ * fit; kernel 0 and scenes with instance SBT offsets by the reference-order kernel.  Results do not depend on any of them.
+ * rdx_get_trace_stats().ms_extend is the kernel time of the call; multi-device mode runs the query on logical device 0.
+ * Refused, before anything is launched: an uninitialised library, an unknown or NULL handle, a `kind` other than 1 / 2, an offset
+ * that is not a multiple of 16, offset + 32 * n beyond the buffer's size, a ray range that overlaps the hit range.  n == 0
+ * succeeds and touches nothing. */
+typedef struct rdx_ray     { float origin[3]; float tmin; float direction[3]; float tmax; } rdx_ray;       /* 32 B, two float4 */
+typedef struct rdx_ray_hit { float t, b1, b2; uint32_t hit;
+                             uint32_t primitiveIndex, instanceIndex, instanceCustomIndex, instanceSBTOffset; } rdx_ray_hit; /* 32 B */
+#define RDX_QUERY_CLOSEST 1   /* the walk of sbtRecordOffset 1: the reference's closest hit */
+#define RDX_QUERY_ANY     2   /* the walk of sbtRecordOffset 2: only `hit` is meaningful */
+int         rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, uint32_t n, int kind,
+                           rdx_buffer hits, size_t hits_offset);
+
 /* Test seams: run single stages on caller-supplied batches (device or host pointers are NOT
  * accepted -- plain host arrays in, host arrays out; the library stages them through HBM). */
 typedef struct rdx_hit {

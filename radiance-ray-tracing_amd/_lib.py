@@ -51,6 +51,15 @@ class rdx_hit(C.Structure):
                 ("transform", C.c_float * 16)]
 
 
+class rdx_ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("tmin", C.c_float), ("direction", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class rdx_ray_hit(C.Structure):
+    _fields_ = [("t", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("hit", C.c_uint32), ("primitiveIndex", C.c_uint32),
+                ("instanceIndex", C.c_uint32), ("instanceCustomIndex", C.c_uint32), ("instanceSBTOffset", C.c_uint32)]
+
+
 class rdx_payload(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("hit", C.c_uint32), ("nextFactor", C.c_float * 3),
                 ("nextRayOrigin", C.c_float * 3), ("nextRayDirection", C.c_float * 3)]
@@ -106,6 +115,7 @@ SIGNATURES = {
     "rdx_get_bounce_counts": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rdx_set_profiling": (C.c_int, [C.c_int]),
     "rdx_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+    "rdx_query_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
     "rdx_trace_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     "rdx_material_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

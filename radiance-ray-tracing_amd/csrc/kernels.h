@@ -139,6 +139,9 @@ void launch_bvh_bin(hipStream_t st, const float* prims9, const uint32_t* work, u
 void launch_pack_tiles(hipStream_t st, const uint8_t* image, uint8_t* packed, uint32_t w, uint32_t h, uint32_t elem,
                        uint32_t tileW, uint32_t tileH, uint32_t rank, uint32_t world, bool unpack);
 
+// device-resident ray queries (rdx_query_rays): 32-byte rays (origin | tmin, direction | tmax) in, 32-byte records out
+void launch_query_rays(hipStream_t st, const AccelView& av, const float4* rays, uint32_t n, int rec, float4* hits, uint32_t* counter);
+
 // test seams
 void launch_trace_batch(hipStream_t st, const AccelView& av, const float* o, const float* d, uint32_t n, float tmin,
                         float tmax, int rec, rdx_hit* out, unsigned long long* visit, int mode, uint32_t* counter);

@@ -939,6 +939,7 @@ __device__ __forceinline__ void write_hit_record(const AccelView& A, const Trace
 #define RDX_SINGLE_RAY_POLICY                                                                                   \
     struct State {};                                                                                             \
     static constexpr bool kShades = false;                                                                       \
+    static constexpr bool kRayInterval = false;                                                                  \
     __device__ __forceinline__ bool load(uint32_t i, f3& o, f3& d, bool& anyHit, State&) const { return load(i, o, d, anyHit); } \
     __device__ __forceinline__ int finish(uint32_t i, const Best& b, f3& o, f3& d, bool&, State&) const { store(i, b, o, d); return COOP_RELEASE; } \
     __device__ __forceinline__ int shade(uint32_t, f3&, f3&, bool&, State&) const { return COOP_RELEASE; }            \
@@ -1170,6 +1171,7 @@ struct PathPolicy {
     struct State { uint32_t phase;    // 0 closest-hit ray, 1 shadow query, 2 nothing to trace (the path ended in load)
                    uint32_t nClosest, nShadow; };      // rays started by this lane (never reset): summed in retire()
     static constexpr bool kShades = true;
+    static constexpr bool kRayInterval = false;
 
     __device__ __forceinline__ void end_path(uint32_t p, f3 c) const
     {
@@ -1339,6 +1341,100 @@ k_trace_batch_pool2_q(AccelView A, const float* __restrict__ o, const float* __r
 {
     BatchPolicy pol{A, o, d, out};
     traverse_pool<2, INL, false, BatchPolicy, true>(A, pol, n, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
+}
+
+// ---------------------------------------------------------------------------------------------
+// device-resident ray queries (rdx_query_rays): 32-byte rays with their own interval in, 32-byte records out
+// ---------------------------------------------------------------------------------------------
+// record of one ray: (t, b1, b2, hit) | (primitiveIndex, instanceIndex, instanceCustomIndex, instanceSBTOffset); everything but
+// `hit` is 0 on a miss and for any-hit queries (ANY), whose walk ends at the first accepted candidate, whichever it is
+template <bool ANY>
+__device__ __forceinline__ void write_query_record(const AccelView& A, bool hit, float t, float b1, float b2, uint32_t inst, uint32_t prim,
+                                                   float4* __restrict__ dst)
+{
+    float4 h0 = make_float4(0.f, 0.f, 0.f, u2f(hit ? 1u : 0u)), h1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!ANY && hit) {
+        const DInst& I = A.insts[inst];
+        h0 = make_float4(t, b1, b2, u2f(1u));
+        h1 = make_float4(u2f(prim), u2f(I.instanceID), u2f(I.customInstanceID), u2f(I.SBTOffset));
+    }
+    dst[0] = h0; dst[1] = h1;
+}
+
+// the pool engine's policy with per-ray intervals (traverse_pool.h, Policy::kRayInterval): two float4 in, two float4 out
+template <bool ANY>
+struct QueryPolicy {
+    AccelView A; const float4* rays; float4* hits;
+    struct State {};
+    static constexpr bool kShades = false;
+    static constexpr bool kRayInterval = true;
+    __device__ __forceinline__ bool load(uint32_t i, f3& o, f3& d, bool& anyHit, State&, float2& iv) const
+    {
+        const float4 r0 = rays[2u * i], r1 = rays[2u * i + 1u];
+        o = mk3(r0.x, r0.y, r0.z); d = mk3(r1.x, r1.y, r1.z);
+        iv = make_float2(r0.w, r1.w);
+        anyHit = false;
+        return true;
+    }
+    __device__ __forceinline__ int finish(uint32_t i, const Best& b, f3&, f3&, bool&, State&) const
+    {
+        write_query_record<ANY>(A, b.hit, b.t, b.b1, b.b2, b.inst, (!ANY && b.hit) ? A.tris[b.slot].primID : 0u, hits + 2u * (size_t)i);
+        return COOP_RELEASE;
+    }
+    __device__ __forceinline__ int shade(uint32_t, f3&, f3&, bool&, State&) const { return COOP_RELEASE; }
+    __device__ __forceinline__ void retire(State&) const {}
+};
+#define RDX_QUERY_LDS(A) (s_stack + (threadIdx.x >> 6) * (pool_words_per_wave((A).topNeed, (A).blasNeed) + POOL_INTERVAL_LDS_WORDS))
+template <bool INL, bool CULL>
+__global__ void POOL_BOUNDS
+k_query_pool1(AccelView A, const float4* __restrict__ rays, uint32_t n, uint32_t* __restrict__ counter, float4* __restrict__ hits)
+{
+    QueryPolicy<false> pol{A, rays, hits};
+    traverse_pool<1, INL, CULL>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
+}
+template <bool INL, bool CULL>
+__global__ void POOL_BOUNDS
+k_query_pool2(AccelView A, const float4* __restrict__ rays, uint32_t n, uint32_t* __restrict__ counter, float4* __restrict__ hits)
+{
+    QueryPolicy<true> pol{A, rays, hits};
+    traverse_pool<2, INL, CULL>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
+}
+// (the same over quad records, as the frames and the test seam walk them)
+template <bool INL, int W>
+__global__ void __launch_bounds__(RDX_BLOCK, W)
+k_query_pool1_q(AccelView A, const float4* __restrict__ rays, uint32_t n, uint32_t* __restrict__ counter, float4* __restrict__ hits)
+{
+    QueryPolicy<false> pol{A, rays, hits};
+    traverse_pool<1, INL, false, QueryPolicy<false>, true>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
+}
+template <bool INL, int W>
+__global__ void __launch_bounds__(RDX_BLOCK, W)
+k_query_pool2_q(AccelView A, const float4* __restrict__ rays, uint32_t n, uint32_t* __restrict__ counter, float4* __restrict__ hits)
+{
+    QueryPolicy<true> pol{A, rays, hits};
+    traverse_pool<2, INL, false, QueryPolicy<true>, true>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
+}
+#undef RDX_QUERY_LDS
+
+// one ray per lane, for scenes and options the pool engine does not run (launch_query_rays): the per-lane walks take the interval
+// per thread already.  WIDE: wide nodes (`kernel` 1, and 2), else the reference's own order (`kernel` 0, SBT offsets)
+template <int REC, bool WIDE>
+__global__ void __launch_bounds__(RDX_BLOCK)
+k_query_rays(AccelView A, const float4* __restrict__ rays, uint32_t n, float4* __restrict__ hits)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 r0 = rays[2u * i], r1 = rays[2u * i + 1u];
+    const f3 ro = mk3(r0.x, r0.y, r0.z), rd = mk3(r1.x, r1.y, r1.z);
+    if (WIDE) {
+        Best b;
+        traverse_wide<REC>(A, ro, rd, r0.w, r1.w, s_stack + threadIdx.x, blockDim.x, b);
+        write_query_record<REC == 2>(A, b.hit, b.t, b.b1, b.b2, b.inst, (REC != 2 && b.hit) ? A.tris[b.slot].primID : 0u, hits + 2u * (size_t)i);
+    } else {
+        TraceResult r;
+        traverse<REC, false>(A, ro, rd, r0.w, r1.w, s_stack + threadIdx.x, blockDim.x, r);
+        write_query_record<REC == 2>(A, r.hit, r.t, r.b1, r.b2, r.inst, r.prim, hits + 2u * (size_t)i);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1672,6 +1768,39 @@ void launch_trace_batch(hipStream_t st, const AccelView& av, const float* o, con
     else if (mode == 1 || av.kernel == 0) { if (rec == 2) RDX_TB(2, false, false); else RDX_TB(1, false, false); }
     else { if (rec == 2) RDX_TB(2, false, true); else RDX_TB(1, false, true); }
 #undef RDX_TB
+}
+
+// Kernels are chosen as launch_trace_batch chooses them (mode 0): the pool engine over quad records for the exhaustive walk,
+// over 64-byte records with `cull`, INL for leaf roots -- with POOL_INTERVAL_LDS_WORDS more LDS per wave, sized here with the
+// function the kernels index with.  `kernel` 2 is served by the per-lane wide kernel (traverse_coop.h takes wave-uniform bounds
+// only), like `kernel` 1 and scenes the cooperative engines do not fit; `kernel` 0 and SBT offsets by the reference-order walk.
+void launch_query_rays(hipStream_t st, const AccelView& av, const float4* rays, uint32_t n, int rec, float4* hits, uint32_t* counter)
+{
+    if (!n) return;
+    const uint32_t words = pool_words_per_wave(av.topNeed, av.blasNeed) + POOL_INTERVAL_LDS_WORDS;
+    if (av.kernel == 3 && words <= RDX_LDS_WORDS_PER_WAVE_MAX) {      // (a scene whose pool fills a wave's LDS to the last 128 words: per lane)
+        if (av.quad && !av.cull) {
+            // (the 6-wave build only: a seventh wave would need LDS the interval table takes)
+            size_t ldsq; const uint32_t thq = coop_threads_words(words, ldsq, POOL_WPE_QUAD);
+            const dim3 gq(coop_blocks(n, thq, ldsq, POOL_WPE_QUAD));
+#define RDX_QQ(K) do { if (av.leafRoots) hipLaunchKernelGGL((K<true, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, av, rays, n, counter, hits); \
+                       else hipLaunchKernelGGL((K<false, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, av, rays, n, counter, hits); } while (0)
+            if (rec == 2) RDX_QQ(k_query_pool2_q); else RDX_QQ(k_query_pool1_q);
+#undef RDX_QQ
+            return;
+        }
+        size_t lds; const uint32_t th = coop_threads_words(words, lds, POOL_WPE);
+        const dim3 gp(coop_blocks(n, th, lds, POOL_WPE));
+        if (rec == 2) RDX_POOL_LAUNCH(k_query_pool2, gp, av, rays, n, counter, hits);
+        else RDX_POOL_LAUNCH(k_query_pool1, gp, av, rays, n, counter, hits);
+        return;
+    }
+    size_t lds; const uint32_t th = trav_threads(av.stackNeed, lds);
+    const dim3 g(blocks_for(n, th)), b(th);
+#define RDX_QR(REC, WIDE) hipLaunchKernelGGL((k_query_rays<REC, WIDE>), g, b, lds, st, av, rays, n, hits)
+    if (av.kernel == 0) { if (rec == 2) RDX_QR(2, false); else RDX_QR(1, false); }
+    else { if (rec == 2) RDX_QR(2, true); else RDX_QR(1, true); }
+#undef RDX_QR
 }
 
 void launch_material_batch(hipStream_t st, const SceneArgs& sc, const rdx_hit* hits, const float* dirs,

@@ -1902,6 +1902,44 @@ extern "C" int rdx_trace_batch(rdx_buffer tlas, const float* o, const float* d, 
     return 0;
 }
 
+// Device-resident ray queries: nothing is staged through the host and nothing is allocated; the steps around the launch are those
+// of rdx_trace_batch above, in the same order
+extern "C" int rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, uint32_t n, int kind, rdx_buffer hits, size_t hits_offset)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_query_rays: invalid TLAS handle");
+    if (!rays || !known_buffer(rays)) return fail("rdx_query_rays: invalid ray buffer handle");
+    if (!hits || !known_buffer(hits)) return fail("rdx_query_rays: invalid hit buffer handle");
+    if (kind != RDX_QUERY_CLOSEST && kind != RDX_QUERY_ANY) return fail("rdx_query_rays: kind must be RDX_QUERY_CLOSEST (1) or RDX_QUERY_ANY (2), not %d", kind);
+    if ((rays_offset & 15u) || (hits_offset & 15u)) return fail("rdx_query_rays: offsets must be multiples of 16 bytes (rays_offset %zu, hits_offset %zu)", rays_offset, hits_offset);
+    const size_t bytes = (size_t)n * sizeof(rdx_ray);
+    static_assert(sizeof(rdx_ray) == 32 && sizeof(rdx_ray_hit) == 32, "two float4 per ray, two per record");
+    if (rays_offset > rays->size || bytes > rays->size - rays_offset)
+        return fail("rdx_query_rays: %u rays at offset %zu run past the ray buffer (%zu bytes)", n, rays_offset, rays->size);
+    if (hits_offset > hits->size || bytes > hits->size - hits_offset)
+        return fail("rdx_query_rays: %u records at offset %zu run past the hit buffer (%zu bytes)", n, hits_offset, hits->size);
+    if (!n) return 0;
+    if ((reinterpret_cast<uintptr_t>(rays->dptr) & 15u) || (reinterpret_cast<uintptr_t>(hits->dptr) & 15u))
+        return fail("rdx_query_rays: wrapped device memory must be 16-byte aligned");
+    {   // the two ranges must not overlap, in one buffer or in two that wrap the same memory
+        const uintptr_t r0 = reinterpret_cast<uintptr_t>(rays->dptr) + rays_offset, h0 = reinterpret_cast<uintptr_t>(hits->dptr) + hits_offset;
+        if (r0 < h0 + bytes && h0 < r0 + bytes) return fail("rdx_query_rays: the ray range and the hit range overlap");
+    }
+    if (derive_accel(tlas)) return -1;
+    HIP_OK(hipMemsetAsync(g.dCounts + 64, 0, sizeof(uint32_t), g.stream));
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_query_rays(g.stream, view_of(tlas), reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset), n, kind,
+                      reinterpret_cast<float4*>(static_cast<char*>(hits->dptr) + hits_offset), g.dCounts + 64);
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    ++hits->version; hits->mirrorValid = false;      // device code wrote it
+    if (take_status()) return fail("rdx_query_rays: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_extend, g.evA, g.evB));      // kernel time of this call
+    return 0;
+}
+
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,
                                   const int32_t* depths, uint32_t n, rdx_payload* out)
 {

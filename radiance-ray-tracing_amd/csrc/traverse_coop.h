@@ -253,6 +253,8 @@ __device__ __forceinline__ bool coop_inst_pretest(const DInst& I, f3 o, f3 rcpW,
 // Ray source / result sink of one use of the engine (extend, shadow, both in one launch, whole paths, test batch):
 //   typedef ... State;                                  per-lane state the policy keeps while a work item lives
 //   static constexpr bool kShades;                      does the policy use the shade step?
+//   static constexpr bool kRayInterval;                 pool engine only (traverse_pool.h): load() takes a trailing float2& and
+//                                                       returns the ray's own (tmin, tmax); the kernel's scalars are not read
 //   bool load(i, o, d, anyHit, State&)                  first ray of work item i; false: nothing to trace, finish()
 //                                                       is called with a miss.  anyHit is honoured when REC == 3.
 //   int  finish(i, B, o, d, anyHit, State&)             the lane's ray is complete.  COOP_RELEASE: item done;

@@ -104,6 +104,7 @@ static_assert(POOL_NODE_MASK + 1u >= RDX_COOP_MAX_WIDE, "the host's fallback rul
 #define POOL_RQ_CAP 256u               // ray queue (entries: path ids).  Bound: camera rays are taken only while it is empty, so a
 #define POOL_SQ_CAP 128u               // wave owns < 64 + 128 paths; shade queue: a hand-over adds <= 64 to < 64 entries
 #define POOL_PATH_LDS_WORDS (POOL_RQ_CAP + POOL_SQ_CAP)
+#define POOL_INTERVAL_LDS_WORDS 128u   // policies with per-ray intervals (Policy::kRayInterval): (tmin, tmax) per lane, in the same place
 #define POOL_QUEUED 0x80000000u        // work item = path id | POOL_QUEUED: a path from the ray queue (not a camera ray)
 #ifndef POOL_QUAD_FETCH
 #define POOL_QUAD_FETCH 0              // node records fetched by quads of lanes (quad_gather64) instead of per lane
@@ -153,9 +154,12 @@ __device__ __forceinline__ void quad_gather64(const uint4* __restrict__ table, u
     out[3] = make_uint4(quad_from<3>(t3.x), quad_from<3>(t3.y), quad_from<3>(t3.z), quad_from<3>(t3.w));
 }
 
-// one test step: up to 64 queued (ray slot, triangle) pairs, one per lane; the ray comes from the entry's LDS slot
+// one test step: up to 64 queued (ray slot, triangle) pairs, one per lane; the ray comes from the entry's LDS slot.
+// RI (Policy::kRayInterval): so does the interval -- bnds[owner] = (tmin, tmax) of the owner's ray; the scalars are not read
+template <bool RI = false>
 __device__ __forceinline__ void pool_test_step(const AccelView& A, const uint32_t* queue, const float4* rays, unsigned long long* best,
-                                               uint32_t lane, uint32_t& qHead, uint32_t qTail, float tmin, float tmax)
+                                               uint32_t lane, uint32_t& qHead, uint32_t qTail, float tmin, float tmax,
+                                               const float2* bnds = nullptr)
 {
     const uint32_t n = min(64u, qTail - qHead);
 #ifdef COOP_STATS
@@ -165,6 +169,7 @@ __device__ __forceinline__ void pool_test_step(const AccelView& A, const uint32_
     const float4* tp = reinterpret_cast<const float4*>(A.tris + (e & COOP_SLOT_MASK));      // requested first (idle lanes read slot 0)
     const float4 tq0 = tp[0], tq1 = tp[1], tq2 = tp[2];
     const float4 ra = POOL_RA(rays, e >> COOP_LANE_SHIFT), rb = POOL_RB(rays, e >> COOP_LANE_SHIFT);
+    if constexpr (RI) { const float2 iv = bnds[e >> COOP_LANE_SHIFT]; tmin = iv.x; tmax = iv.y; }
     if (lane < n) {
         float t, b1, b2;
         if (coop_triangle_regs(tq0, tq1, tq2, mk3(ra.x, ra.y, ra.z), mk3(rb.x, rb.y, rb.z), tmin, tmax, t, b1, b2)) {
@@ -179,8 +184,10 @@ __device__ __forceinline__ void pool_test_step(const AccelView& A, const uint32_
     qHead += n;
 }
 // append `cnt` (0..POOL_PIECE) consecutive triangle slots starting at `start` for every lane; wave-uniform control
+template <bool RI = false>
 __device__ __forceinline__ void pool_enqueue(const AccelView& A, uint32_t* queue, const float4* rays, unsigned long long* best, uint32_t lane,
-                                             uint32_t tagBits, uint32_t cnt, uint32_t start, uint32_t& qHead, uint32_t& qTail, float tmin, float tmax)
+                                             uint32_t tagBits, uint32_t cnt, uint32_t start, uint32_t& qHead, uint32_t& qTail, float tmin, float tmax,
+                                             const float2* bnds = nullptr)
 {
     uint32_t pre = 0, total = 0;
 #pragma unroll
@@ -190,7 +197,7 @@ __device__ __forceinline__ void pool_enqueue(const AccelView& A, uint32_t* queue
         total += (uint32_t)__popcll(m) << b;
     }
     if (total == 0) return;
-    while (qTail - qHead + total > POOL_QCAP) pool_test_step(A, queue, rays, best, lane, qHead, qTail, tmin, tmax);
+    while (qTail - qHead + total > POOL_QCAP) pool_test_step<RI>(A, queue, rays, best, lane, qHead, qTail, tmin, tmax, bnds);
     const uint32_t at = qTail + pre;
     for (uint32_t k = 0; k < cnt; ++k) queue[(at + k) & (POOL_QCAP - 1u)] = tagBits | (start + k);
     qTail += total;
@@ -198,9 +205,10 @@ __device__ __forceinline__ void pool_enqueue(const AccelView& A, uint32_t* queue
 
 // the same for the two leaf children of a pool item at once: `ca` slots from `sa`, then `cb` slots from `sb` (ca, cb <= POOL_PIECE) --
 // one prefix sum over ca + cb instead of two
+template <bool RI = false>
 __device__ __forceinline__ void pool_enqueue2(const AccelView& A, uint32_t* queue, const float4* rays, unsigned long long* best, uint32_t lane,
                                               uint32_t tagBits, uint32_t ca, uint32_t sa, uint32_t cb, uint32_t sb, uint32_t& qHead,
-                                              uint32_t& qTail, float tmin, float tmax)
+                                              uint32_t& qTail, float tmin, float tmax, const float2* bnds = nullptr)
 {
     const uint32_t cnt = ca + cb;
     uint32_t pre = 0, total = 0;
@@ -212,11 +220,11 @@ __device__ __forceinline__ void pool_enqueue2(const AccelView& A, uint32_t* queu
     }
     if (total == 0) return;
     if (total > POOL_QCAP) {       // more than the ring holds (over half the lanes with two full leaves): one side at a time
-        pool_enqueue(A, queue, rays, best, lane, tagBits, ca, sa, qHead, qTail, tmin, tmax);
-        pool_enqueue(A, queue, rays, best, lane, tagBits, cb, sb, qHead, qTail, tmin, tmax);
+        pool_enqueue<RI>(A, queue, rays, best, lane, tagBits, ca, sa, qHead, qTail, tmin, tmax, bnds);
+        pool_enqueue<RI>(A, queue, rays, best, lane, tagBits, cb, sb, qHead, qTail, tmin, tmax, bnds);
         return;
     }
-    while (qTail - qHead + total > POOL_QCAP) pool_test_step(A, queue, rays, best, lane, qHead, qTail, tmin, tmax);
+    while (qTail - qHead + total > POOL_QCAP) pool_test_step<RI>(A, queue, rays, best, lane, qHead, qTail, tmin, tmax, bnds);
     const uint32_t at = qTail + pre;
     for (uint32_t k = 0; k < ca; ++k) queue[(at + k) & (POOL_QCAP - 1u)] = tagBits | (sa + k);
     for (uint32_t k = 0; k < cb; ++k) queue[(at + ca + k) & (POOL_QCAP - 1u)] = tagBits | (sb + k);
@@ -253,6 +261,15 @@ __device__ __forceinline__ void quad_half(const RayInst& Q, const float4 a0, con
     if (leafB) { if (sB || !pair) runB = (wide_count(bd1) << WIDE_SLOT_BITS) | bd0; } else if (sB) pushB = bd0;
 }
 
+// a policy's load(): one with per-ray intervals (Policy::kRayInterval) also returns the ray's (tmin, tmax), which go into the
+// lane's entry of the interval table
+template <class Policy>
+__device__ __forceinline__ bool pool_load_ray(const Policy& pol, uint32_t idx, f3& o, f3& d, bool& anyHit, typename Policy::State& st, float2* iv)
+{
+    if constexpr (Policy::kRayInterval) { float2 v; const bool walk = pol.load(idx, o, d, anyHit, st, v); *iv = v; return walk; }
+    else return pol.load(idx, o, d, anyHit, st);
+}
+
 // INL: the scene has instances whose BLAS is a single leaf of <= 8 triangles; they are handled inside the top-level step
 // (below).  A separate instantiation, chosen by the host per scene: the kernel sits at its register budget, and the extra
 // code costs scenes without such instances 10-15 % through spills even when it never runs.
@@ -280,8 +297,15 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
     uint32_t* rayQ = reinterpret_cast<uint32_t*>(L.best + 64);      // whole-path policies only (the kernel allocates POOL_PATH_LDS_WORDS more)
     uint32_t* shadeQ = rayQ + POOL_RQ_CAP;
     uint32_t rqHead = 0, rqTail = 0, sqHead = 0, sqTail = 0;        // wave-uniform
-#define POOL_TEST() pool_test_step(A, L.queue, rays, L.best, lane, qHead, qTail, tmin, tmax)
-#define POOL_ENQ(TAG, CNT, START) pool_enqueue(A, L.queue, rays, L.best, lane, TAG, CNT, START, qHead, qTail, tmin, tmax)
+    // Per-ray intervals (Policy::kRayInterval; never a whole-path policy): bnds[lane] = (tmin, tmax) of the lane's ray, in the same
+    // place behind the engine's own words (the kernel allocates POOL_INTERVAL_LDS_WORDS more).  Written when the lane takes a ray --
+    // none of its items or queued tests is then left -- and read by whichever lane tests or culls for that ray; the scalars
+    // `tmin` / `tmax` are not read at all.
+    constexpr bool RI = Policy::kRayInterval;
+    static_assert(!(RI && Policy::kShades), "the interval table and the path queues share their place in LDS");
+    float2* bnds = reinterpret_cast<float2*>(L.best + 64);
+#define POOL_TEST() pool_test_step<RI>(A, L.queue, rays, L.best, lane, qHead, qTail, tmin, tmax, bnds)
+#define POOL_ENQ(TAG, CNT, START) pool_enqueue<RI>(A, L.queue, rays, L.best, lane, TAG, CNT, START, qHead, qTail, tmin, tmax, bnds)
     pendN[lane] = 0u;
 
     const uint32_t nWavesGrid = gridDim.x * (blockDim.x >> 6);
@@ -415,7 +439,8 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                         const f3 ro = mat4_mul3(I.inv, o.x, o.y, o.z, 1.0f);
                         const f3 rd = mat4_mul3(I.inv, d.x, d.y, d.z, 0.0f);
                         float t, b1, b2;
-                        coop_triangle(A, B.slot, ro, rd, tmin, tmax, t, b1, b2);
+                        if constexpr (RI) { const float2 iv = bnds[lane]; coop_triangle(A, B.slot, ro, rd, iv.x, iv.y, t, b1, b2); }
+                        else coop_triangle(A, B.slot, ro, rd, tmin, tmax, t, b1, b2);
                         B.t = t; B.b1 = b1; B.b2 = b2;
                     }
                 }
@@ -442,7 +467,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                     const uint32_t idx = rayQ[(rqHead + rank) & (POOL_RQ_CAP - 1u)] | POOL_QUEUED;
                     rayIdx = idx;
                     bool ah = false;
-                    const bool walk = pol.load(idx, o, d, ah, st);
+                    const bool walk = pool_load_ray(pol, idx, o, d, ah, st, bnds + lane);
                     anyHit = (REC == 2) || (REC == 3 && ah);
                     POOL_START_RAY(walk);
                 }
@@ -472,7 +497,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                         const uint32_t idx = base + rank;
                         rayIdx = idx;
                         bool ah = false;
-                        const bool walk = pol.load(idx, o, d, ah, st);
+                        const bool walk = pool_load_ray(pol, idx, o, d, ah, st, bnds + lane);
                         anyHit = (REC == 2) || (REC == 3 && ah);
                         POOL_START_RAY(walk);
                     }
@@ -644,9 +669,11 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                                             if (!((REC != 1) && anyHit && L.best[lane] != ~0ull)) {
                                                 const f3 ro = mat4_mul3(I.inv, o.x, o.y, o.z, 1.0f);
                                                 const f3 rd = mat4_mul3(I.inv, d.x, d.y, d.z, 0.0f);
+                                                float tlo = tmin, thi = tmax;
+                                                if constexpr (RI) { const float2 iv = bnds[lane]; tlo = iv.x; thi = iv.y; }
                                                 for (uint32_t j = 0; j < rcnt; ++j) {
                                                     float t, b1, b2;
-                                                    if (coop_triangle(A, wide_slot(I.rootDesc0) + j, ro, rd, tmin, tmax, t, b1, b2)) {
+                                                    if (coop_triangle(A, wide_slot(I.rootDesc0) + j, ro, rd, tlo, thi, t, b1, b2)) {
                                                         const uint32_t low = (ci << COOP_INST_SHIFT) | (wide_slot(I.rootDesc0) + j - I._p0);
                                                         atomicMin(&L.best[lane], ((unsigned long long)__float_as_uint(t) << 32) | low);
                                                     }
@@ -771,6 +798,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                         // gate of the whole BLAS: the root descriptor's normal cone, every vertex is inside the root box
                         const CullGate G = cull_gate(R, cull_ray(R), rdsc.x, rdsc.y, false, mk3(rmin.x, rmin.y, rmin.z), mk3(rmax.x, rmax.y, rmax.z));
                         float tlim = tmax;
+                        if constexpr (RI) tlim = bnds[lane].y;
                         if (!anyHit && hb != 0xffffffffu) tlim = fminf(tlim, __uint_as_float(hb));
                         if (tnRoot > cull_limit(G, tlim)) enter = false;
                     } else enter = slab_fast(R, mk3(rmin.x, rmin.y, rmin.z), mk3(rmax.x, rmax.y, rmax.z));
@@ -863,10 +891,10 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                 }
                 while (__any((runA | runB | runC | runE) >> WIDE_SLOT_BITS)) {
                     uint32_t ca = min(runA >> WIDE_SLOT_BITS, POOL_PIECE), cb = min(runB >> WIDE_SLOT_BITS, POOL_PIECE);
-                    pool_enqueue2(A, L.queue, rays, L.best, lane, slotBits, ca, runA & WIDE_SLOT_MASK, cb, runB & WIDE_SLOT_MASK, qHead, qTail, tmin, tmax);
+                    pool_enqueue2<RI>(A, L.queue, rays, L.best, lane, slotBits, ca, runA & WIDE_SLOT_MASK, cb, runB & WIDE_SLOT_MASK, qHead, qTail, tmin, tmax, bnds);
                     runA = runA - (ca << WIDE_SLOT_BITS) + ca; runB = runB - (cb << WIDE_SLOT_BITS) + cb;
                     ca = min(runC >> WIDE_SLOT_BITS, POOL_PIECE); cb = min(runE >> WIDE_SLOT_BITS, POOL_PIECE);
-                    pool_enqueue2(A, L.queue, rays, L.best, lane, slotBits, ca, runC & WIDE_SLOT_MASK, cb, runE & WIDE_SLOT_MASK, qHead, qTail, tmin, tmax);
+                    pool_enqueue2<RI>(A, L.queue, rays, L.best, lane, slotBits, ca, runC & WIDE_SLOT_MASK, cb, runE & WIDE_SLOT_MASK, qHead, qTail, tmin, tmax, bnds);
                     runC = runC - (ca << WIDE_SLOT_BITS) + ca; runE = runE - (cb << WIDE_SLOT_BITS) + cb;
                 }
                 if (qTail - qHead >= POOL_TEST_MIN) POOL_TEST();
@@ -923,6 +951,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
                         const CullGate GL = cull_gate(Q, CR, ld0, ld1, leafL, mk3(l0.x, l0.y, l0.z), mk3(l1.x, l1.y, l1.z));
                         const CullGate GR = cull_gate(Q, CR, rd0, rd1, leafR, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z));
                         float tlim = tmax;
+                        if constexpr (RI) tlim = bnds[wl].y;          // (the OWNER's bound: this lane processes the item of lane wl)
                         if (((REC == 1) || !(qf & 4u)) && hb != 0xffffffffu) tlim = fminf(tlim, __uint_as_float(hb));
                         float tnL = 0.f, tnR = 0.f;
                         if (cull_child(Q, mk3(l0.x, l0.y, l0.z), mk3(l1.x, l1.y, l1.z), leafL, GL, tlim, tnL)) {
@@ -961,7 +990,7 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
             const uint32_t tagBits = slotBits;
             while (__any((cntL | cntR) != 0u)) {
                 const uint32_t cl = min(cntL, POOL_PIECE), cr = min(cntR, POOL_PIECE);
-                pool_enqueue2(A, L.queue, rays, L.best, lane, tagBits, cl, stL, cr, stR, qHead, qTail, tmin, tmax);
+                pool_enqueue2<RI>(A, L.queue, rays, L.best, lane, tagBits, cl, stL, cr, stR, qHead, qTail, tmin, tmax, bnds);
                 stL += cl; cntL -= cl; stR += cr; cntR -= cr;
             }
             if (qTail - qHead >= POOL_TEST_MIN) POOL_TEST();

@@ -399,6 +399,51 @@ def TraceBatch(tlas, origins, dirs, tmin=0.001, tmax=1000.0, sbtRecordOffset=1, 
     return (out, visit) if count_visits else out
 
 
+# ---- ray queries on device memory (rdx_query_rays) ---------------------------------------------------------------
+RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
+RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("hit", "<u4"), ("primitiveIndex", "<u4"),
+                          ("instanceIndex", "<u4"), ("instanceCustomIndex", "<u4"), ("instanceSBTOffset", "<u4")])
+assert RAY_DTYPE.itemsize == C.sizeof(_lib.rdx_ray) == 32 and RAY_HIT_DTYPE.itemsize == C.sizeof(_lib.rdx_ray_hit) == 32
+QUERY_CLOSEST, QUERY_ANY = 1, 2
+
+
+def QueryRays(tlas, rays, n, kind=QUERY_CLOSEST, hits=None, rays_offset=0, hits_offset=0):
+    """Extension: `n` rays (RAY_DTYPE records, each with its own tmin / tmax) from the device buffer `rays` at byte `rays_offset`
+    against `tlas`; one RAY_HIT_DTYPE record per ray goes to the device buffer `hits` at byte `hits_offset` (created when None:
+    hits_offset + 32 n bytes).  kind: QUERY_CLOSEST (sbtRecordOffset 1) or QUERY_ANY (2: only `hit` is meaningful).  Nothing
+    passes through the host.  Returns `hits`."""
+    if not isinstance(rays, Buffer) or not isinstance(tlas, Buffer):
+        raise RadianceError("QueryRays: tlas and rays must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    if hits is None:
+        hits = CreateBuffer(None, max(int(hits_offset) + RAY_HIT_DTYPE.itemsize * int(n), 1))
+    elif not isinstance(hits, Buffer):
+        raise RadianceError("QueryRays: hits must be a Buffer or None")
+    _check(_lib.lib().rdx_query_rays(tlas.handle, rays.handle, int(rays_offset), int(n), int(kind), hits.handle, int(hits_offset)))
+    return hits
+
+
+def QueryRaysTorch(tlas, rays_tensor, kind=QUERY_CLOSEST, out=None):
+    """Extension: rays from a contiguous float32 CUDA tensor of shape (n, 8) -- origin, tmin, direction, tmax per row; the records
+    land in `out`, an int32 (or float32) CUDA tensor of shape (n, 8) (created when None: int32; `.view(torch.float32)` shows t,
+    b1, b2).  The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
+    import torch
+    t = rays_tensor
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 8 and t.is_contiguous()):
+        raise RadianceError("QueryRaysTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(t.shape[0])
+    if out is None:
+        out = torch.empty((n, 8), dtype=torch.int32, device=t.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.int32, torch.float32) and tuple(out.shape) == (n, 8)
+              and out.is_contiguous() and out.device == t.device):
+        raise RadianceError("QueryRaysTorch: out must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
+    torch.cuda.current_stream(t.device).synchronize()
+    if n:
+        rays = WrapDeviceMemory(None, t.data_ptr(), n * 32, keepalive=t)
+        hits = WrapDeviceMemory(None, out.data_ptr(), n * 32, keepalive=out)
+        QueryRays(tlas, rays, n, kind, hits)
+    return out
+
+
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
 _DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
 _DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),
