@@ -125,9 +125,10 @@ inline BottomAccelStruct BuildAccelStruct(Platform*, Mesh& mesh)
     return as;
 }
 
-inline TopAccelStruct BuildAccelStruct(Platform*, std::vector<Instance>& instances)
+namespace detail
 {
-    printf("\nStart building top level BVH\n\tInstance count: %ld\n", (long)instances.size());
+inline std::vector<rdx_instance> instances_in(std::vector<Instance>& instances)
+{
     std::vector<rdx_instance> in(instances.size());
     for (size_t i = 0; i < instances.size(); ++i) {
         const float* m = &instances[i].transform.a1;
@@ -136,7 +137,23 @@ inline TopAccelStruct BuildAccelStruct(Platform*, std::vector<Instance>& instanc
         in[i].customInstanceID = instances[i].customInstanceID;
         in[i].bottomAccelStruct = instances[i].bottomAccelStruct ? instances[i].bottomAccelStruct->handle : nullptr;
     }
+    return in;
+}
+} // namespace detail
+
+inline TopAccelStruct BuildAccelStruct(Platform*, std::vector<Instance>& instances)
+{
+    printf("\nStart building top level BVH\n\tInstance count: %ld\n", (long)instances.size());
+    std::vector<rdx_instance> in = detail::instances_in(instances);
     return detail::need(rdx_tlas_build(in.data(), (uint32_t)in.size()), "BuildAccelStruct(instances)");
+}
+
+// Extension (no reference counterpart; rdx_tlas_update): other transforms, SBT offsets or custom ids for the instances
+// `accelStruct` was built from -- same count, same bottom-level structure at every index.  The handle stays valid and bound.
+inline void UpdateAccelStruct(Platform*, TopAccelStruct accelStruct, std::vector<Instance>& instances)
+{
+    std::vector<rdx_instance> in = detail::instances_in(instances);
+    if (rdx_tlas_update(accelStruct, in.data(), (uint32_t)in.size())) detail::fatal("UpdateAccelStruct");
 }
 
 inline void TopAccelStructToFile(Platform*, TopAccelStruct accelStruct, const char* path) { if (rdx_tlas_to_file(accelStruct, path)) detail::fatal("TopAccelStructToFile"); }

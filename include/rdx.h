@@ -97,6 +97,25 @@ int         rdx_blas_build_many(uint32_t count, const float* const* verts_xyz, c
 const void* rdx_blas_data(rdx_blas b, uint32_t* size_out);
 int         rdx_blas_max_depth(rdx_blas b);
 rdx_buffer  rdx_tlas_build(const rdx_instance* instances, uint32_t ninstances);
+/* Other transforms, SBT offsets or custom ids for the instances of a TLAS that rdx_tlas_build made: afterwards `tlas` holds exactly
+ * the blob rdx_tlas_build(instances, ninstances) would have produced -- rdx_buffer_read / rdx_buffer_size / rdx_tlas_to_file return it,
+ * every later trace, query, batch and user program sees it.  The handle stays valid and stays bound in descriptor sets; the raw device
+ * pointer (rdx_buffer_device_ptr) MAY CHANGE: when the number of top-level nodes changes, the blob's size does, and it moves to a new
+ * allocation (the old one is freed: no device memory is lost per call).  Only the top part of the blob is built and uploaded; a
+ * traversal layout already derived from the buffer is updated in place -- small arrays, one kernel for the triangles' owner words --
+ * or, where the change reaches further (the unified tree or the quad records appear or vanish), derived again in full.
+ * Blocks like every call.  Refused, with nothing touched: an uninitialised library, a NULL or unknown handle, a buffer that is not a
+ * TLAS built by rdx_tlas_build (rdx_buffer_wrap, rdx_tlas_from_file, plain buffers; a TLAS written to through rdx_buffer_write), an
+ * `ninstances` other than the build's, another BLAS handle at any index. */
+typedef struct rdx_tlas_update_stats {
+    uint32_t path;                 /* 0 = blob only (no layout had been derived yet), 1 = incremental, 2 = full re-derivation */
+    uint32_t top_nodes_before, top_nodes_after;
+    uint64_t bytes_h2d, bytes_d2d; /* moved by this call, all devices summed */
+    uint64_t tri_slots_rewritten;  /* DTri owner words written by the device kernel */
+    float    ms_host, ms_device;
+} rdx_tlas_update_stats;
+int         rdx_tlas_update(rdx_buffer tlas, const rdx_instance* instances, uint32_t ninstances);
+int         rdx_get_tlas_update_stats(rdx_tlas_update_stats* out);   /* of the last successful rdx_tlas_update */
 /* host-only variant: returns the malloc'ed TLAS blob (release with rdx_free); needs no GPU */
 void*       rdx_tlas_build_blob(const rdx_instance* instances, uint32_t ninstances, uint32_t* size_out,
                                 int* max_depth_out);
@@ -318,6 +337,12 @@ typedef struct rdx_accel_scalars {
  * entry receives that array; the caller states its capacity in bytes[i], from a size query made before. */
 int         rdx_debug_accel_layout(const void* blob, size_t size, int quad, int cull, rdx_accel_scalars* scalars,
                                    void* const* arrays, size_t* bytes);
+
+/* Test seam: the layout of blobs[count - 1], reached the way rdx_tlas_update reaches it -- blobs[0] derived afresh, then one update
+ * per further blob (csrc/accel_layout.h update_accel_layout, owner words and wide tail written on the host).  Output as above.
+ * path_per_step (optional, count - 1 entries): 1 = that step was incremental, 2 = it took the full derivation.  Needs no device. */
+int         rdx_debug_accel_layout_update(const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull,
+                                          rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes, uint32_t* path_per_step);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,12 @@ class rdx_trace_stats(C.Structure):
                 ("groups", C.c_uint32), ("ms_sort", C.c_float)]
 
 
+class rdx_tlas_update_stats(C.Structure):
+    _fields_ = [("path", C.c_uint32), ("top_nodes_before", C.c_uint32), ("top_nodes_after", C.c_uint32),
+                ("bytes_h2d", C.c_uint64), ("bytes_d2d", C.c_uint64), ("tri_slots_rewritten", C.c_uint64),
+                ("ms_host", C.c_float), ("ms_device", C.c_float)]
+
+
 class rdx_material(C.Structure):
     _fields_ = [("albedo", C.c_float * 4), ("metallic", C.c_float), ("roughness", C.c_float), ("transmission", C.c_float),
                 ("ior", C.c_float), ("albedoTexIdx", C.c_int32), ("metallicTexIdx", C.c_int32), ("roughnessTexIdx", C.c_int32),
@@ -96,6 +102,8 @@ SIGNATURES = {
     "rdx_blas_data": (C.c_void_p, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "rdx_blas_max_depth": (C.c_int, [C.c_void_p]),
     "rdx_tlas_build": (C.c_void_p, [C.POINTER(rdx_instance), C.c_uint32]),
+    "rdx_tlas_update": (C.c_int, [C.c_void_p, C.POINTER(rdx_instance), C.c_uint32]),
+    "rdx_get_tlas_update_stats": (C.c_int, [C.POINTER(rdx_tlas_update_stats)]),
     "rdx_tlas_build_blob": (C.c_void_p, [C.POINTER(rdx_instance), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int)]),
     "rdx_free": (None, [C.c_void_p]),
     "rdx_tlas_to_file": (C.c_int, [C.c_void_p, C.c_char_p]),
@@ -123,6 +131,9 @@ SIGNATURES = {
     "rdx_pcg3d_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "rdx_debug_accel_layout": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(rdx_accel_scalars), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_size_t)]),
+    "rdx_debug_accel_layout_update": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_int,
+                                                C.POINTER(rdx_accel_scalars), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_uint32)]),
     "rdx_obj_load": (C.c_int, [C.c_char_p, C.POINTER(rdx_obj_scene)]),
     "rdx_obj_free": (None, [C.POINTER(rdx_obj_scene)]),
 }

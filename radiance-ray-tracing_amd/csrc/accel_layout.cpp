@@ -186,7 +186,9 @@ void quad_order(int arr, int ord[4])
 }
 
 struct BlasInfo { uint32_t nodeBase; uint32_t need; uint32_t coopNeed; uint32_t anyNeed; uint32_t triBase; uint32_t rootDesc0, rootDesc1; float rootMin[3], rootMax[3];
-                  uint32_t nTris; uint32_t users; };
+                  uint32_t nTris; uint32_t users;
+                  uint32_t quadNeed;        // pool-stack need of the quad walk from its root (0: leaf root, or no quad records)
+                  uint32_t owner; };        // DTri._p0 of its triangles: the slot of its one instance (group / unified tree), or 0xffffffff
 
 // one derivation: the steps below run in the order of derive_accel_layout and share this state
 struct Deriver {
@@ -201,12 +203,23 @@ struct Deriver {
     // steps 2, 3
     std::map<uint32_t, BlasInfo> blasAt;    // byte offset -> merged-array base
     bool hugeLeaf = false;                  // a leaf of more triangles than the wide layout's count field holds
-    bool coopOK = true;
+    bool coopOK = true, coopBlasOK = true;
     bool sbtOffsets = false;
     uint32_t maxLeafChunks = 0;             // extra stack entries an oversized (> 8 triangle) leaf can push
     uint32_t maxLeafTris = 0;
     // step 6
     std::vector<uint32_t> qneed;
+    uint32_t unifiedQuadNeed = 0;
+    // update_accel_layout: L holds no BLAS blocks -- blasAt comes from the book, L.wide is only the tail behind wideOffset records
+    bool update = false, needFull = false;
+    uint32_t wideOffset = 0, bookTris = 0;
+    uint32_t nBlasWide = 0;                 // wide records of the BLAS blocks (the unified tree's follow)
+    uint32_t total_tris() const { return update ? bookTris : (uint32_t)L.tris.size(); }
+    uint32_t total_wide() const { return wideOffset + (uint32_t)L.wide.size(); }
+    bool want_quad() const
+    {
+        return opt.quad != 0 && !(opt.cull > 0 || (opt.cull < 0 && total_wide() >= RDX_CULL_AUTO_MIN_WIDE)) && !L.s.unifiedRoot;
+    }
 
     int fail(const char* fmt, ...)
     {
@@ -225,7 +238,9 @@ struct Deriver {
     void world_box(const BlobInst& bi, DInst& d);
     void shared_transform_group();
     void unified_tree();
+    void write_owners();
     int quad_records();
+    void make_book();
     int top_level_needs();
 };
 
@@ -319,9 +334,9 @@ int Deriver::import_blas(uint32_t byteOffset, BlasInfo& info)
         d.e2[0] = v2[0] - v0[0]; d.e2[1] = v2[1] - v0[1]; d.e2[2] = v2[2] - v0[2]; d._p1 = triBase;       // radiance.cl:216; _p1: first triangle slot of this BLAS
     }
     info = BlasInfo{};
-    info.nodeBase = nodeBase; info.triBase = triBase; info.nTris = nTris; info.users = 0;
+    info.nodeBase = nodeBase; info.triBase = triBase; info.nTris = nTris; info.users = 0; info.owner = 0xffffffffu;
     if (blas_wide_records(bn, nNodes, triBase, info)) return -1;
-    if (nTris > RDX_COOP_MAX_BLAS_TRIS) coopOK = false;
+    if (nTris > RDX_COOP_MAX_BLAS_TRIS) { coopOK = false; coopBlasOK = false; }
     for (int k = 0; k < 3; ++k) { info.rootMin[k] = bn[0].bottom[k]; info.rootMax[k] = bn[0].top[k]; }
     return 0;
 }
@@ -401,6 +416,7 @@ int Deriver::instance_records()
         if (bi.SBTOffset != 0 && !sbt_offset_is_order_free(bi.SBTOffset)) sbtOffsets = true;
         auto it = blasAt.find(bi.instanceOffset);
         if (it == blasAt.end()) {
+            if (update) { needFull = true; return -1; }      // a BLAS the book does not know
             BlasInfo info;
             if (import_blas(bi.instanceOffset, info)) return -1;
             it = blasAt.emplace(bi.instanceOffset, info).first;
@@ -476,8 +492,7 @@ void Deriver::shared_transform_group()
     L.s.groupIdentity = is_identity(dI[(*best)[0]].inv);
     for (uint32_t k : *best) {
         L.groupBits[k >> 5] |= 1u << (k & 31u); ++L.s.groupCount;
-        const BlasInfo& bi = blasAt[binst[k].instanceOffset];
-        for (uint32_t t = 0; t < bi.nTris; ++t) L.tris[bi.triBase + t]._p0 = k;
+        blasAt[binst[k].instanceOffset].owner = k;
     }
 }
 
@@ -496,8 +511,7 @@ void Deriver::shared_transform_group()
 void Deriver::unified_tree()
 {
     std::vector<DInst>& dI = L.insts;
-    std::vector<DTri>& dTri = L.tris;
-    std::vector<DWide>& dW = L.wide;
+    std::vector<DWide>& dW = L.wide;      // (update: only the tail, behind wideOffset records)
     if (!((nTop > 64 || nInst > 256) && nInst >= 2 && !(tnodes[0].w0 & LEAF_BIT) && !sbtOffsets)) return;
     for (uint32_t k = 0; k < nInst; ++k) {
         if (blasAt[binst[k].instanceOffset].users != 1) return;
@@ -511,20 +525,19 @@ void Deriver::unified_tree()
     auto inst_child = [&](uint32_t k, float* mn, float* mx, uint32_t& d0, uint32_t& d1) {
         for (int c = 0; c < 3; ++c) { mn[c] = dI[k].rootMin[c]; mx[c] = dI[k].rootMax[c]; }
         d0 = dI[k].rootDesc0; d1 = dI[k].rootDesc1;
-        const BlasInfo& bi = blasAt[binst[k].instanceOffset];
-        for (uint32_t t = 0; t < bi.nTris; ++t) dTri[bi.triBase + t]._p0 = k;          // the candidate's instance comes from the triangle
+        blasAt[binst[k].instanceOffset].owner = k;          // the candidate's instance comes from the triangle
     };
     // fan-out over instances [a, b): returns the child entry for that range
     std::function<uint32_t(uint32_t, uint32_t, float*, float*, uint32_t&, uint32_t&)> range_child =
         [&](uint32_t a, uint32_t b, float* mn, float* mx, uint32_t& d0, uint32_t& d1) -> uint32_t {
             if (b - a == 1) { inst_child(a, mn, mx, d0, d1); return (dI[a].rootDesc1 & WIDE_LEAF) ? 0u : 1u + blasAt[binst[a].instanceOffset].anyNeed; }
             const uint32_t mid = a + (b - a) / 2;
-            const uint32_t idx = (uint32_t)dW.size();
+            const uint32_t idx = wideOffset + (uint32_t)dW.size();
             dW.emplace_back();
             DWide w{};
             const uint32_t hl = range_child(a, mid, w.lmin, w.lmax, w.ld0, w.ld1);
             const uint32_t hr = range_child(mid, b, w.rmin, w.rmax, w.rd0, w.rd1);
-            dW[idx] = w;
+            dW[idx - wideOffset] = w;
             always(mn, mx);
             wide_desc(false, idx, 0u, never, d0, d1);
             return 1u + std::max(hl, hr);
@@ -534,7 +547,7 @@ void Deriver::unified_tree()
     for (uint32_t i = nTop; i-- > 0;) {
         const BlobNode& n = tnodes[i];
         if (n.w0 & LEAF_BIT) continue;
-        const uint32_t idx = (uint32_t)dW.size();
+        const uint32_t idx = wideOffset + (uint32_t)dW.size();
         dW.emplace_back();
         DWide w{};
         uint32_t h[2] = {0, 0};
@@ -555,7 +568,7 @@ void Deriver::unified_tree()
                 }
             }
         }
-        dW[idx] = w;
+        dW[idx - wideOffset] = w;
         uIdx[i] = idx; uH[i] = std::max(h[0], h[1]);
     }
     // super-root: the reference tests the top-level root's own box when it pops it
@@ -563,9 +576,19 @@ void Deriver::unified_tree()
     for (int k = 0; k < 3; ++k) { sr.lmin[k] = tnodes[0].bottom[k]; sr.lmax[k] = tnodes[0].top[k]; }
     wide_desc(false, uIdx[0], 0u, never, sr.ld0, sr.ld1);
     none(sr.rmin, sr.rmax, sr.rd0, sr.rd1);
-    L.s.unifiedRoot = (uint32_t)dW.size();
+    L.s.unifiedRoot = wideOffset + (uint32_t)dW.size();
     dW.push_back(sr);
     L.s.unifiedNeed = uH[0] + 2u;
+}
+
+// the owner words the two steps above decided (a fresh derivation: every other triangle keeps the 0xffffffff of import_blas)
+void Deriver::write_owners()
+{
+    for (auto& kv : blasAt) {
+        const BlasInfo& bi = kv.second;
+        if (bi.owner == 0xffffffffu) continue;
+        for (uint32_t t = 0; t < bi.nTris; ++t) L.tris[bi.triBase + t]._p0 = bi.owner;
+    }
 }
 
 // ---- step 6: quad records ----------------------------------------------------------------------------------------------------
@@ -581,7 +604,7 @@ int Deriver::quad_records()
 {
     const std::vector<DWide>& dW = L.wide;
     std::vector<DQuad>& dQ = L.quad;
-    const bool wantQuad = opt.quad != 0 && !(opt.cull > 0 || (opt.cull < 0 && dW.size() >= RDX_CULL_AUTO_MIN_WIDE)) && !L.s.unifiedRoot;
+    const bool wantQuad = want_quad();
     dQ.assign(wantQuad ? dW.size() : 0, DQuad{});
     qneed.assign(dW.size(), 0);
     if (!wantQuad) return 0;
@@ -664,6 +687,8 @@ int Deriver::quad_records()
             stk.pop_back();
         }
     }
+    for (auto& kv : blasAt) kv.second.quadNeed = (kv.second.rootDesc1 & WIDE_LEAF) ? 0u : qneed[kv.second.rootDesc0];
+    unifiedQuadNeed = L.s.unifiedRoot ? qneed[L.s.unifiedRoot] : 0u;
     return 0;
 }
 
@@ -673,7 +698,7 @@ int Deriver::top_level_needs()
     rdx_accel_scalars& s = L.s;
     std::vector<DNode>& dT = L.tnodes;
     uint32_t maxBlasQuad = 0;
-    for (auto& kv : blasAt) if (!(kv.second.rootDesc1 & WIDE_LEAF)) maxBlasQuad = std::max(maxBlasQuad, qneed[kv.second.rootDesc0]);
+    for (auto& kv : blasAt) maxBlasQuad = std::max(maxBlasQuad, kv.second.quadNeed);
     // stack need: TLAS part
     // (cooperative kernel: the instances of a top-level leaf are pushed as 16-bit masks, one entry per 16 instances,
     //  and the entry being consumed is pushed back while one of its instances is walked)
@@ -723,13 +748,39 @@ int Deriver::top_level_needs()
     s.blasNeedAny = maxBlasAny;
     for (int k = 0; k < 3; ++k) { s.sceneLo[k] = tnodes[0].bottom[k]; s.sceneHi[k] = tnodes[0].top[k]; }
     s.sbtOffsets = sbtOffsets || hugeLeaf;      // (either way: the reference-order kernel, which reads the blob's own node layout)
-    s.quadNeed = maxBlasQuad; s.quadUnifiedNeed = s.unifiedRoot ? qneed[s.unifiedRoot] + 1u : 0u;
-    s.nWide = (uint32_t)L.wide.size();
+    s.quadNeed = maxBlasQuad; s.quadUnifiedNeed = s.unifiedRoot ? unifiedQuadNeed + 1u : 0u;
+    s.nWide = total_wide();
     // packed-word limits of the cooperative engines (rdx_types.h); the runtime adds their LDS footprint
-    s.coopOK = coopOK && L.tris.size() <= RDX_COOP_MAX_TRI_SLOTS - 1u && L.wide.size() < RDX_COOP_MAX_WIDE;
+    s.coopOK = coopOK && total_tris() <= RDX_COOP_MAX_TRI_SLOTS - 1u && total_wide() < RDX_COOP_MAX_WIDE;
     // per-lane kernels: [need][64 lanes] words of LDS per wave, 64 KB at most
     if (s.stackNeed > 250) return fail("BVH too deep for the LDS traversal stack: %u entries per ray needed, 250 available", s.stackNeed);
     return 0;
+}
+
+// ---- the book: what update_accel_layout needs of this derivation ----------------------------------------------------------------
+void Deriver::make_book()
+{
+    AccelBook& B = L.book;
+    const auto* th = reinterpret_cast<const BlobTopHeader*>(blob);
+    const uint64_t regionStart = (uint64_t)th->instByteOffset + (uint64_t)nInst * sizeof(BlobInst);
+    B = AccelBook{};
+    B.valid = th->totalBufferSize >= regionStart;
+    B.blasRegionBytes = B.valid ? th->totalBufferSize - regionStart : 0;
+    B.nInst = nInst; B.nTris = total_tris(); B.nBlasWide = nBlasWide;
+    B.maxLeafChunks = maxLeafChunks; B.maxLeafTris = maxLeafTris;
+    B.hugeLeaf = hugeLeaf; B.coopBlasOK = coopBlasOK; B.quadBuilt = want_quad();
+    for (auto& kv : blasAt) {
+        const BlasInfo& bi = kv.second;
+        if (kv.first < regionStart) { B.valid = false; break; }
+        AccelBlasBlock b{};
+        b.relOffset = (uint32_t)(kv.first - regionStart);
+        b.nodeBase = bi.nodeBase; b.triBase = bi.triBase; b.nTris = bi.nTris;
+        b.need = bi.need; b.coopNeed = bi.coopNeed; b.anyNeed = bi.anyNeed; b.quadNeed = bi.quadNeed;
+        b.rootDesc0 = bi.rootDesc0; b.rootDesc1 = bi.rootDesc1;
+        for (int k = 0; k < 3; ++k) { b.rootMin[k] = bi.rootMin[k]; b.rootMax[k] = bi.rootMax[k]; }
+        b.owner = bi.owner;
+        B.blocks.push_back(b);
+    }
 }
 
 } // namespace
@@ -740,9 +791,73 @@ int derive_accel_layout(const void* blob, size_t size, const AccelOptions& opt, 
     Deriver d{static_cast<const uint8_t*>(blob), size, opt, out, err};
     if (d.import_top() || d.instance_records()) return -1;      // (a BLAS is imported when the first instance refers to it)
     d.shared_transform_group();
+    d.nBlasWide = (uint32_t)out.wide.size();
     d.unified_tree();
+    d.write_owners();
     if (d.quad_records() || d.top_level_needs()) return -1;
+    d.make_book();
     return 0;
+}
+
+int update_accel_layout(const void* blob, size_t size, const AccelOptions& opt, AccelLayout& inout, AccelUpdate& what, std::string& err)
+{
+    what = AccelUpdate{};
+    const AccelBook& B = inout.book;
+    if (!B.valid) return 1;
+    AccelLayout N;                  // the top-level part, derived into a layout without BLAS blocks
+    Deriver d{static_cast<const uint8_t*>(blob), size, opt, N, err};
+    d.update = true; d.wideOffset = d.nBlasWide = B.nBlasWide; d.bookTris = B.nTris;
+    if (d.import_top()) return -1;
+    const auto* th = reinterpret_cast<const BlobTopHeader*>(blob);
+    const uint64_t regionStart = (uint64_t)th->instByteOffset + (uint64_t)d.nInst * sizeof(BlobInst);
+    if (d.nInst != B.nInst || th->totalBufferSize < regionStart || th->totalBufferSize - regionStart != B.blasRegionBytes) return 1;
+    for (const AccelBlasBlock& b : B.blocks) {
+        BlasInfo bi{};
+        bi.nodeBase = b.nodeBase; bi.triBase = b.triBase; bi.nTris = b.nTris;
+        bi.need = b.need; bi.coopNeed = b.coopNeed; bi.anyNeed = b.anyNeed; bi.quadNeed = b.quadNeed;
+        bi.rootDesc0 = b.rootDesc0; bi.rootDesc1 = b.rootDesc1;
+        for (int k = 0; k < 3; ++k) { bi.rootMin[k] = b.rootMin[k]; bi.rootMax[k] = b.rootMax[k]; }
+        bi.users = 0; bi.owner = 0xffffffffu;
+        d.blasAt.emplace((uint32_t)(regionStart + b.relOffset), bi);
+    }
+    d.maxLeafChunks = B.maxLeafChunks; d.maxLeafTris = B.maxLeafTris; d.hugeLeaf = B.hugeLeaf;
+    d.coopBlasOK = B.coopBlasOK; d.coopOK = d.coopOK && B.coopBlasOK;
+    if (d.instance_records()) return d.needFull ? 1 : -1;
+    for (auto& kv : d.blasAt) if (kv.second.users == 0) return 1;
+    d.shared_transform_group();
+    d.unified_tree();
+    // quad records exist for every wide record or for none: a change of that is a change of the BLAS blocks' part too
+    if (d.want_quad() != B.quadBuilt) return 1;
+    if ((N.s.unifiedRoot != 0) != (inout.s.unifiedRoot != 0)) return 1;
+    if (d.top_level_needs()) return -1;
+
+    // what changed
+    auto differs = [](const auto& a, const auto& b) { return a.size() != b.size() || (a.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) != 0); };
+    what.tnodes = differs(N.tnodes, inout.tnodes); what.ctnodes = differs(N.ctnodes, inout.ctnodes); what.insts = differs(N.insts, inout.insts);
+    what.groupBits = std::memcmp(N.groupBits, inout.groupBits, sizeof N.groupBits) != 0;
+    size_t bi = 0;
+    for (auto& kv : d.blasAt) {     // (the map's order is the blocks' order: both ascend by byte offset)
+        const AccelBlasBlock& old = B.blocks[bi++];
+        if (kv.second.owner != old.owner && old.nTris) what.owners.push_back(AccelOwnerRange{old.triBase, old.nTris, kv.second.owner});
+    }
+    what.wideTailFirst = B.nBlasWide;
+    what.wideTail = std::move(N.wide);
+    what.wideTailChanged = !what.wideTail.empty() || inout.s.nWide != B.nBlasWide;
+    N.wide.clear();
+    d.make_book();
+    inout.tnodes = std::move(N.tnodes); inout.ctnodes = std::move(N.ctnodes); inout.insts = std::move(N.insts);
+    std::memcpy(inout.groupBits, N.groupBits, sizeof N.groupBits);
+    inout.s = N.s;
+    inout.book = std::move(N.book);
+    return 0;
+}
+
+void apply_accel_update(AccelLayout& L, const AccelUpdate& what)
+{
+    for (const AccelOwnerRange& r : what.owners)
+        for (uint32_t t = 0; t < r.count; ++t) L.tris[r.first + t]._p0 = r.owner;
+    L.wide.resize(what.wideTailFirst);
+    L.wide.insert(L.wide.end(), what.wideTail.begin(), what.wideTail.end());
 }
 
 } // namespace rdx

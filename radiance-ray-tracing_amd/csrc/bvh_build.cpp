@@ -364,7 +364,10 @@ Blas* build_blas(const float* v, uint32_t nverts, const uint32_t* idx, uint32_t 
 // bvh.cpp:343-420 + :568-597 + radiance.cpp:366-425.
 // The corner transform is assimp's aiMatrix4x4t::operator* (un-vendored third party):
 // out[r][c] = V[0][c]*T[r][0] + V[1][c]*T[r][1] + V[2][c]*T[r][2] + V[3][c]*T[r][3], left to right.
-bool build_tlas(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& blob, int& maxDepthOut, std::string& err)
+// topOnly: only the top part -- header, top-level nodes, instance records (their instanceOffset already that of the
+// whole blob) -- is produced; blob.size() is then instByteOffset + ninst * sizeof(BlobInst) and the header's totalBufferSize the
+// size the whole blob would have (rdx_tlas_update uploads just that part).
+static bool build_tlas_impl(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& blob, int& maxDepthOut, std::string& err, bool topOnly)
 {
     if (ninst == 0) { err = "BuildAccelStruct(instances): empty instance list"; return false; }
     std::vector<Prim> prims(ninst);
@@ -420,7 +423,7 @@ bool build_tlas(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& 
     const uint64_t total = topSize + next;
     if (total > 0xffffffffull) { err = "TLAS exceeds the 4 GiB blob limit (32-bit byte offsets)"; return false; }
 
-    blob.assign((size_t)total, 0);
+    blob.assign((size_t)(topOnly ? topSize : total), 0);
     BlobTopHeader hdr{TYPE_TOP_AS, 16u, (uint32_t)(16u + (uint64_t)nodeCount * sizeof(BlobNode)), (uint32_t)total};
     std::memcpy(blob.data(), &hdr, sizeof hdr);
     auto* nodes = reinterpret_cast<BlobNode*>(blob.data() + hdr.nodeByteOffset);
@@ -434,10 +437,20 @@ bool build_tlas(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& 
         d.customInstanceID = inst[id].customInstanceID;
         d.instanceOffset = offsetOf[inst[id].blas];
     });
-    for (auto& kv : offsetOf) std::memcpy(blob.data() + kv.second, kv.first->data.data(), kv.first->data.size());
+    if (!topOnly) for (auto& kv : offsetOf) std::memcpy(blob.data() + kv.second, kv.first->data.data(), kv.first->data.size());
     maxDepthOut = 0;
     max_depth(root.get(), 0, maxDepthOut);
     return true;
+}
+
+bool build_tlas(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& blob, int& maxDepthOut, std::string& err)
+{
+    return build_tlas_impl(inst, ninst, blob, maxDepthOut, err, false);
+}
+
+bool build_tlas_top(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& top, int& maxDepthOut, std::string& err)
+{
+    return build_tlas_impl(inst, ninst, top, maxDepthOut, err, true);
 }
 
 } // namespace rdx

@@ -39,5 +39,8 @@ Blas* build_blas(const float* verts_xyz, uint32_t nverts, const uint32_t* indice
                  std::string& err);
 bool  build_tlas(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& blob, int& maxDepth,
                  std::string& err);
+// the same blob without its BLAS region: header (totalBufferSize = the whole blob's), top-level nodes, instance records
+bool  build_tlas_top(const InstanceDesc* inst, uint32_t ninst, std::vector<uint8_t>& top, int& maxDepth,
+                     std::string& err);
 
 } // namespace rdx

@@ -151,5 +151,8 @@ void launch_material_batch(hipStream_t st, const SceneArgs& sc, const rdx_hit* h
 void launch_generate_batch(hipStream_t st, const CameraArgs& cam, const uint32_t* pixels, const uint32_t* rnd,
                            uint32_t n, float* o, float* d);
 void launch_pcg3d_batch(hipStream_t st, const uint32_t* in3, float* out3, uint32_t n);
+// TLAS update: tris[first + k]._p0 = owner for every range of `table` = {first, count, owner, slots in the ranges before}; `total`
+// = slots of all ranges (device table; ranges inside [0, nTris))
+void launch_tri_owner_fill(hipStream_t st, DTri* tris, uint32_t nTris, const uint4* table, uint32_t nRanges, uint32_t total);
 
 } // namespace rdx

@@ -17,6 +17,7 @@
 #include <memory>
 #include <mutex>
 #include <cfloat>
+#include <chrono>
 #include <string>
 #include <atomic>
 #include <thread>
@@ -61,11 +62,17 @@ struct AccelCache {                // derived traversal layout of one TLAS buffe
     DQuad* quad = nullptr;             // null: the quad records were not built
     uint32_t* groupBits = nullptr;     // 9 words
     rdx_accel_scalars s{};             // coopOK: ... and the engines' LDS footprint fits (derive_accel)
+    // rdx_tlas_update: the host side of the layout without its four large arrays (small arrays, scalars, per-BLAS book), the
+    // elements tnodes / ctnodes and wide were allocated for, and the device table of the owner-fill kernel
+    AccelLayout host;
+    size_t topCap = 0, wideCap = 0;
+    uint4* ownerTable = nullptr; size_t ownerCap = 0;
     void release()
     {
-        for (void* p : {(void*)tnodes, (void*)ctnodes, (void*)insts, (void*)bnodes, (void*)tris, (void*)wide, (void*)quad, (void*)groupBits})
+        for (void* p : {(void*)tnodes, (void*)ctnodes, (void*)insts, (void*)bnodes, (void*)tris, (void*)wide, (void*)quad, (void*)groupBits, (void*)ownerTable})
             if (p) HIP_IGN(hipFree(p));
         tnodes = nullptr; ctnodes = nullptr; insts = nullptr; bnodes = nullptr; tris = nullptr; wide = nullptr; quad = nullptr; groupBits = nullptr;
+        ownerTable = nullptr; ownerCap = 0;
     }
 };
 
@@ -77,6 +84,7 @@ struct rdx_buffer_s {
     std::vector<uint8_t> shadow;           // host copy of a TLAS blob (valid iff shadowVersion == version)
     uint64_t shadowVersion = ~0ull;
     std::unique_ptr<AccelCache> accel;
+    std::vector<rdx_blas> tlasBlas;        // rdx_tlas_build: the BLAS handle of every instance, by index (empty: not a TLAS built here)
     // small parameter buffers (RTProp, camera): a host mirror kept current by the write path, so that TraceRays does
     // not read them back from the device every frame.  Valid only for library-owned buffers whose every byte has been
     // written through the API since creation (device code never writes them); wrapped memory is never mirrored.
@@ -174,6 +182,7 @@ struct Context {
     bool texViewsValid = false;
     std::string shaderInclude;              // -I for user shader programs (rdx_shader_include_path; the reference's SHADER_LIB_PATH)
     rdx_trace_stats stats{};
+    rdx_tlas_update_stats updStats{};       // of the last rdx_tlas_update (g0 only)
     float camAngles[3] = {0, 0, 0}, camTrig[6] = {1, 0, 1, 0, 1, 0};      // camera_args: cos / sin of the camera angles, evaluated on the device
     bool camCached = false;
     uint32_t visitDepth = 0;                // bounces covered by hVisit after a count_visits frame
@@ -217,6 +226,13 @@ bool known_buffer(const void* h)
 }
 
 // ---- derived traversal layout ------------------------------------------------------------------
+// beyond the packed-word limits of the cooperative engines or their LDS footprint the per-lane wide kernel runs
+bool runtime_coop_ok(const rdx_accel_scalars& S)
+{
+    return S.coopOK && coop_lds_words(S.coopNeed) <= RDX_LDS_WORDS_PER_WAVE_MAX &&
+           pool_lds_words(std::max(S.topNeed, S.topFlatNeed), std::max({S.blasNeed, S.blasNeedAny, S.quadNeed, S.quadUnifiedNeed})) <= RDX_LDS_WORDS_PER_WAVE_MAX;
+}
+
 // accel_layout.cpp derives it on the host; here it is uploaded to the calling thread's device
 int derive_accel(rdx_buffer_s* tb)
 {
@@ -232,28 +248,32 @@ int derive_accel(rdx_buffer_s* tb)
     if (derive_accel_layout(tb->shadow.data(), tb->shadow.size(), AccelOptions{g.opt.quad, g.opt.cull}, L, err)) return fail_str(err);
     auto ac = std::make_unique<AccelCache>();
     ac->s = L.s;
-    auto up = [&](auto*& dptr, const auto* src, size_t n) -> hipError_t {
+    auto up = [&](auto*& dptr, const auto* src, size_t n, size_t cap = 0) -> hipError_t {
         const size_t elem = sizeof(*src);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), std::max<size_t>(n, 1) * elem);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&dptr), std::max<size_t>({n, cap, 1}) * elem);
         if (e != hipSuccess) return e;
         return n ? hipMemcpy(dptr, src, n * elem, hipMemcpyHostToDevice) : hipSuccess;
     };
-    HIP_OK(up(ac->tnodes, L.tnodes.data(), L.tnodes.size()));
-    HIP_OK(up(ac->ctnodes, L.ctnodes.data(), L.ctnodes.size()));
+    // (a binary tree over nInst instances has at most 2 nInst - 1 nodes: room for every top level rdx_tlas_update can bring)
+    ac->topCap = std::max<size_t>(L.tnodes.size(), 2 * (size_t)L.s.nInst);
+    ac->wideCap = L.wide.size();
+    HIP_OK(up(ac->tnodes, L.tnodes.data(), L.tnodes.size(), ac->topCap));
+    HIP_OK(up(ac->ctnodes, L.ctnodes.data(), L.ctnodes.size(), ac->topCap));
     HIP_OK(up(ac->insts, L.insts.data(), L.insts.size()));
     HIP_OK(up(ac->bnodes, L.bnodes.data(), L.bnodes.size()));
     HIP_OK(up(ac->tris, L.tris.data(), L.tris.size()));
     HIP_OK(up(ac->wide, L.wide.data(), L.wide.size()));
     if (!L.quad.empty()) HIP_OK(up(ac->quad, L.quad.data(), L.quad.size()));
     HIP_OK(up(ac->groupBits, L.groupBits, 9));
-    // beyond the packed-word limits of the cooperative engines or their LDS footprint the per-lane wide kernel runs
     const rdx_accel_scalars& S = ac->s;
-    ac->s.coopOK = S.coopOK && coop_lds_words(S.coopNeed) <= RDX_LDS_WORDS_PER_WAVE_MAX &&
-                   pool_lds_words(std::max(S.topNeed, S.topFlatNeed), std::max({S.blasNeed, S.blasNeedAny, S.quadNeed, S.quadUnifiedNeed})) <= RDX_LDS_WORDS_PER_WAVE_MAX;
+    ac->s.coopOK = runtime_coop_ok(S);
     if (std::getenv("RDX_VERBOSE"))
         std::fprintf(stderr, "[rdx] accel: %zu top nodes, %u instances, %zu wide nodes, %zu triangle slots, stack need %u (cooperative kernel %u = top %u + BLAS %u; quad walk %u)\n",
                      L.tnodes.size(), S.nInst, L.wide.size(), L.tris.size(), S.stackNeed, S.coopNeed, S.topNeed, S.blasNeed, S.quadNeed);
     ac->version = tb->version;
+    // kept for rdx_tlas_update: everything but the four large arrays
+    std::vector<DNode>().swap(L.bnodes); std::vector<DTri>().swap(L.tris); std::vector<DWide>().swap(L.wide); std::vector<DQuad>().swap(L.quad);
+    ac->host = std::move(L);
     if (acc(tb)) acc(tb)->release();
     acc(tb) = std::move(ac);
     return 0;
@@ -965,7 +985,7 @@ static rdx_buffer tlas_from_blob(std::vector<uint8_t>&& blob)
     return tb;
 }
 
-static bool tlas_blob(const rdx_instance* inst, uint32_t n, std::vector<uint8_t>& blob, int& depth)
+static bool tlas_blob(const rdx_instance* inst, uint32_t n, std::vector<uint8_t>& blob, int& depth, bool topOnly = false)
 {
     std::vector<InstanceDesc> d(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -975,7 +995,7 @@ static bool tlas_blob(const rdx_instance* inst, uint32_t n, std::vector<uint8_t>
         d[i].blas = inst[i].bottomAccelStruct ? inst[i].bottomAccelStruct->blas.get() : nullptr;
     }
     std::string err;
-    if (!build_tlas(d.data(), n, blob, depth, err)) { fail("%s", err.c_str()); return false; }
+    if (!(topOnly ? build_tlas_top(d.data(), n, blob, depth, err) : build_tlas(d.data(), n, blob, depth, err))) { fail("%s", err.c_str()); return false; }
     return true;
 }
 
@@ -999,7 +1019,156 @@ extern "C" rdx_buffer rdx_tlas_build(const rdx_instance* inst, uint32_t n)
     std::vector<uint8_t> blob;
     int depth = 0;
     if (!tlas_blob(inst, n, blob, depth)) return nullptr;
-    return tlas_from_blob(std::move(blob));
+    rdx_buffer tb = tlas_from_blob(std::move(blob));
+    if (tb) for (uint32_t i = 0; i < n; ++i) tb->tlasBlas.push_back(inst[i].bottomAccelStruct);
+    return tb;
+}
+
+// ---- rdx_tlas_update ---------------------------------------------------------------------------------------------------------
+// The blob of other transforms differs from the one in the buffer in its top part only -- header, top-level nodes, instance
+// records; the BLAS region behind them is byte-identical and merely shifts when the number of top-level nodes changes
+// (build_tlas appends the distinct BLASes in order of first appearance by instance INDEX, which an update keeps).  So: the top
+// part is built by the builder (build_tlas_top) and uploaded; a shifted region is copied on the device into a buffer of the new
+// size, and the old buffer freed.  A traversal layout that was derived for the old blob follows by update_accel_layout: the small
+// arrays are uploaded again, the triangle owner words rewritten by one kernel, and nothing else moves.
+namespace {
+// the layout part of the update for the calling thread's device (tl_ctx / tl_dev, HIP device current); `oldVersion`: what the
+// cache must have been derived from to be updated rather than left for the next derive_accel
+int update_accel(rdx_buffer_s* tb, uint64_t oldVersion, rdx_tlas_update_stats& st)
+{
+    AccelCache* ac = acc(tb).get();
+    if (!ac || ac->version != oldVersion) return 0;
+    AccelUpdate upd;
+    std::string err;
+    const uint32_t topBefore = (uint32_t)ac->host.tnodes.size();
+    int rc = update_accel_layout(tb->shadow.data(), tb->shadow.size(), AccelOptions{g.opt.quad, g.opt.cull}, ac->host, upd, err);
+    if (rc < 0) return fail_str(err);
+    uint64_t total = 0;
+    for (const AccelOwnerRange& r : upd.owners) {
+        if ((uint64_t)r.first + r.count > ac->host.book.nTris) return fail("rdx_tlas_update: owner range [%u, +%u) beyond %u triangle slots", r.first, r.count, ac->host.book.nTris);
+        total += r.count;
+    }
+    if (rc == 0 && (ac->host.tnodes.size() > ac->topCap || (size_t)upd.wideTailFirst + upd.wideTail.size() > ac->wideCap || total > 0xffffffffull)) rc = 1;
+    if (rc == 1) {                  // the full derivation (it replaces the cache: nothing of the old one is kept)
+        st.path = 2;
+        st.top_nodes_before = topBefore;
+        if (derive_accel(tb)) return -1;
+        st.top_nodes_after = (uint32_t)acc(tb)->host.tnodes.size();
+        return 0;
+    }
+    st.path = std::max(st.path, 1u);
+    st.top_nodes_before = topBefore; st.top_nodes_after = (uint32_t)ac->host.tnodes.size();
+    const AccelLayout& L = ac->host;
+    auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        st.bytes_h2d += bytes;
+        return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, g.stream) : hipSuccess;
+    };
+    if (upd.tnodes) HIP_OK(h2d(ac->tnodes, L.tnodes.data(), L.tnodes.size() * sizeof(DNode)));
+    if (upd.ctnodes) HIP_OK(h2d(ac->ctnodes, L.ctnodes.data(), L.ctnodes.size() * sizeof(DNode)));
+    if (upd.insts) HIP_OK(h2d(ac->insts, L.insts.data(), L.insts.size() * sizeof(DInst)));
+    if (upd.groupBits) HIP_OK(h2d(ac->groupBits, L.groupBits, sizeof L.groupBits));
+    if (upd.wideTailChanged) HIP_OK(h2d(ac->wide + upd.wideTailFirst, upd.wideTail.data(), upd.wideTail.size() * sizeof(DWide)));
+    std::vector<uint4> table;
+    if (!upd.owners.empty()) {
+        uint32_t before = 0;
+        for (const AccelOwnerRange& r : upd.owners) { table.push_back(uint4{r.first, r.count, r.owner, before}); before += r.count; }
+        if (table.size() > ac->ownerCap) {
+            if (ac->ownerTable) HIP_IGN(hipFree(ac->ownerTable));
+            ac->ownerTable = nullptr; ac->ownerCap = 0;
+            HIP_OK(hipMalloc(reinterpret_cast<void**>(&ac->ownerTable), std::max<size_t>(table.size(), L.book.blocks.size()) * sizeof(uint4)));
+            ac->ownerCap = std::max<size_t>(table.size(), L.book.blocks.size());
+        }
+        HIP_OK(h2d(ac->ownerTable, table.data(), table.size() * sizeof(uint4)));
+        HIP_OK(hipEventRecord(g.evA, g.stream));
+        launch_tri_owner_fill(g.stream, ac->tris, L.book.nTris, ac->ownerTable, (uint32_t)table.size(), (uint32_t)total);
+        HIP_OK(hipEventRecord(g.evB, g.stream));
+        HIP_OK(hipGetLastError());
+    }
+    HIP_OK(hipStreamSynchronize(g.stream));          // (the host arrays above go out of scope / may change with the next update)
+    if (!table.empty()) { float ms = 0; HIP_OK(hipEventElapsedTime(&ms, g.evA, g.evB)); st.ms_device += ms; }
+    st.tri_slots_rewritten += total;
+    ac->s = L.s;
+    ac->s.coopOK = runtime_coop_ok(L.s);
+    ac->version = tb->version;
+    return 0;
+}
+}
+
+extern "C" int rdx_tlas_update(rdx_buffer tb, const rdx_instance* inst, uint32_t n)
+{
+    if (!g0.initialized) return fail("rdx_init has not been called");
+    if (!tb || !known_buffer(tb)) return fail("rdx_tlas_update: invalid TLAS handle");
+    if (!tb->owned || tb->tlasBlas.empty()) return fail("rdx_tlas_update: the buffer is not a TLAS built by rdx_tlas_build (wrapped memory, a cache file and plain buffers cannot be updated)");
+    if (tb->shadowVersion != tb->version) return fail("rdx_tlas_update: the TLAS buffer has been written to since it was built");
+    if (!inst) return fail("rdx_tlas_update: no instances");
+    if (n != tb->tlasBlas.size()) return fail("rdx_tlas_update: %u instances, the TLAS was built from %zu", n, tb->tlasBlas.size());
+    for (uint32_t i = 0; i < n; ++i)       // (handles are compared, not followed: BLAS handles live until rdx_shutdown)
+        if (inst[i].bottomAccelStruct != tb->tlasBlas[i]) return fail("rdx_tlas_update: instance %u refers to another BLAS than the TLAS was built with", i);
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint8_t> top;
+    int depth = 0;
+    if (!tlas_blob(inst, n, top, depth, true)) return -1;
+    const auto* oh = reinterpret_cast<const BlobTopHeader*>(tb->shadow.data());
+    const size_t oldTop = (size_t)oh->instByteOffset + (size_t)n * sizeof(BlobInst), newTop = top.size();
+    if (oldTop > tb->shadow.size()) return fail("rdx_tlas_update: the TLAS blob is malformed");
+    const size_t region = tb->shadow.size() - oldTop, newSize = newTop + region, oldSize = tb->size;
+    if (reinterpret_cast<const BlobTopHeader*>(top.data())->totalBufferSize != newSize) return fail("rdx_tlas_update: the builder's top part does not fit the BLAS region");
+
+    rdx_tlas_update_stats st{};
+    // the blob on every device
+    for (int d = 0; d < g_ndev; ++d) {
+        void*& ptr = d == 0 ? tb->dptr : tb->rep[d];
+        HIP_OK(hipSetDevice(g_phys[d]));
+        hipError_t e = hipSuccess;
+        if (newTop == oldTop) e = hipMemcpy(ptr, top.data(), newTop, hipMemcpyHostToDevice);
+        else {
+            // the region moves: into a second allocation (an overlapping copy inside one buffer is not defined), the old one is freed
+            void* fresh = nullptr;
+            e = hipMalloc(&fresh, std::max<size_t>(newSize, 16));
+            if (e == hipSuccess) e = hipMemcpy(fresh, top.data(), newTop, hipMemcpyHostToDevice);
+            if (e == hipSuccess && region) e = hipMemcpy(static_cast<uint8_t*>(fresh) + newTop, static_cast<const uint8_t*>(ptr) + oldTop, region, hipMemcpyDeviceToDevice);
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e == hipSuccess) { HIP_IGN(hipFree(ptr)); ptr = fresh; st.bytes_d2d += region; }
+            else if (fresh) HIP_IGN(hipFree(fresh));
+        }
+        HIP_IGN(hipSetDevice(g_phys[0]));
+        HIP_OK(e);
+        st.bytes_h2d += newTop;
+    }
+    // the host shadow, kept equal to the device blob without reading it back
+    if (newTop < oldTop) { std::memmove(tb->shadow.data() + newTop, tb->shadow.data() + oldTop, region); tb->shadow.resize(newSize); }
+    else if (newTop > oldTop) { tb->shadow.resize(newSize); std::memmove(tb->shadow.data() + newTop, tb->shadow.data() + oldTop, region); }
+    std::memcpy(tb->shadow.data(), top.data(), newTop);
+    (void)oldSize;
+    tb->size = newSize;
+    const uint64_t oldVersion = tb->version++;
+    tb->shadowVersion = tb->version;
+    st.top_nodes_before = (uint32_t)((oldTop - (size_t)n * sizeof(BlobInst) - 16) / sizeof(BlobNode));
+    st.top_nodes_after = (uint32_t)((newTop - (size_t)n * sizeof(BlobInst) - 16) / sizeof(BlobNode));
+    const auto t1 = std::chrono::steady_clock::now();
+    // the traversal layout on every device that had derived one
+    for (int d = 0; d < g_ndev; ++d) {
+        if (d) g_dev[d]->opt = g0.opt;
+        tl_ctx = g_dev[d]; tl_dev = d;
+        hipError_t e = hipSetDevice(g_phys[d]);
+        const int rc = e == hipSuccess ? update_accel(tb, oldVersion, st) : -1;
+        const std::string msg = g.err;
+        tl_ctx = &g0; tl_dev = 0;
+        HIP_IGN(hipSetDevice(g_phys[0]));
+        if (rc) return fail("rdx_tlas_update: device %d: %s", d, e == hipSuccess ? msg.c_str() : hipGetErrorString(e));
+    }
+    const auto t2 = std::chrono::steady_clock::now();
+    (void)t1;
+    st.ms_host = std::chrono::duration<float, std::milli>(t2 - t0).count() - st.ms_device;
+    g0.updStats = st;
+    return 0;
+}
+
+extern "C" int rdx_get_tlas_update_stats(rdx_tlas_update_stats* out)
+{
+    if (!out) return fail("rdx_get_tlas_update_stats: null argument");
+    *out = g0.updStats;
+    return 0;
 }
 
 // radiance.cpp:428-448: raw dump of the TLAS buffer, size from header word 3
@@ -1985,6 +2154,8 @@ extern "C" int rdx_pcg3d_batch(const uint32_t* in3, float* out3, uint32_t n)
     return 0;
 }
 
+static int export_layout(const AccelLayout& L, rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes);
+
 extern "C" int rdx_debug_accel_layout(const void* blob, size_t size, int quad, int cull, rdx_accel_scalars* scalars,
                                       void* const* arrays, size_t* bytes)
 {
@@ -1993,6 +2164,46 @@ extern "C" int rdx_debug_accel_layout(const void* blob, size_t size, int quad, i
     AccelLayout L;
     std::string err;
     if (derive_accel_layout(blob, size, AccelOptions{quad, cull}, L, err)) return fail_str(err);
+    return export_layout(L, scalars, arrays, bytes);
+}
+
+// blobs[0] derived afresh, then updated through blobs[1 ..] the way rdx_tlas_update updates a device's layout -- with the owner words
+// and the wide tail written into the host arrays.  A step the update hands back (return 1), or whose blob does not keep the
+// previous one's BLAS region, is derived in full.  path_per_step (optional, count - 1 entries): 1 incremental, 2 full.
+extern "C" int rdx_debug_accel_layout_update(const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull,
+                                             rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes, uint32_t* path_per_step)
+{
+    if (!blobs || !sizes || !count) return fail("rdx_debug_accel_layout_update: no blobs");
+    if (arrays && !bytes) return fail("rdx_debug_accel_layout_update: arrays need their capacities in bytes[]");
+    for (uint32_t i = 0; i < count; ++i) if (!blobs[i] || sizes[i] < 16) return fail("rdx_debug_accel_layout_update: blob %u is missing", i);
+    AccelLayout L;
+    std::string err;
+    const AccelOptions opt{quad, cull};
+    if (derive_accel_layout(blobs[0], sizes[0], opt, L, err)) return fail_str(err);
+    auto region = [&](uint32_t i, uint32_t nInst, const uint8_t*& p, size_t& n) {
+        const auto* h = static_cast<const BlobTopHeader*>(blobs[i]);
+        const size_t start = (size_t)h->instByteOffset + (size_t)nInst * sizeof(BlobInst);
+        if (start > sizes[i] || h->totalBufferSize > sizes[i] || h->totalBufferSize < start) return false;
+        p = static_cast<const uint8_t*>(blobs[i]) + start; n = h->totalBufferSize - start;
+        return true;
+    };
+    for (uint32_t i = 1; i < count; ++i) {
+        const uint8_t* a = nullptr; const uint8_t* b = nullptr; size_t na = 0, nb = 0;
+        int rc = 1;
+        if (region(i - 1, L.s.nInst, a, na) && region(i, L.s.nInst, b, nb) && na == nb && std::memcmp(a, b, na) == 0) {
+            AccelUpdate upd;
+            rc = update_accel_layout(blobs[i], sizes[i], opt, L, upd, err);
+            if (rc < 0) return fail_str(err);
+            if (rc == 0) apply_accel_update(L, upd);
+        }
+        if (rc == 1 && derive_accel_layout(blobs[i], sizes[i], opt, L, err)) return fail_str(err);
+        if (path_per_step) path_per_step[i - 1] = rc == 0 ? 1u : 2u;
+    }
+    return export_layout(L, scalars, arrays, bytes);
+}
+
+static int export_layout(const AccelLayout& L, rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes)
+{
     if (scalars) *scalars = L.s;
     auto view = [](const auto& v) { return std::make_pair(static_cast<const void*>(v.data()), v.size() * sizeof(v[0])); };
     const std::pair<const void*, size_t> arr[8] = {view(L.tnodes), view(L.ctnodes), view(L.insts), view(L.bnodes), view(L.tris), view(L.wide),

@@ -210,6 +210,27 @@ def _instance_array(instances):
     return arr
 
 
+def UpdateAccelStruct(platform, tlas, instances):
+    """Extension (rdx_tlas_update): other transforms / SBT offsets / custom ids for the instances `tlas` was built from -- same
+    count, same BLAS at every index.  Afterwards `tlas` holds what BuildAccelStruct(platform, instances) would have built; the
+    Buffer stays bound, its `size` (refreshed here) and `device_ptr` may change."""
+    if not isinstance(tlas, Buffer):
+        raise RadianceError("UpdateAccelStruct: tlas must be the Buffer BuildAccelStruct returned")
+    L = _lib.lib()
+    insts = list(instances)
+    _check(L.rdx_tlas_update(tlas.handle, _instance_array(insts), len(insts)))
+    tlas.size = L.rdx_buffer_size(tlas.handle)
+    return tlas
+
+
+def GetTlasUpdateStats():
+    """rdx_tlas_update_stats of the last UpdateAccelStruct: path (0 blob only, 1 incremental, 2 full re-derivation), top-level
+    node counts, bytes moved, owner words rewritten, host / device milliseconds"""
+    st = _lib.rdx_tlas_update_stats()
+    _check(_lib.lib().rdx_get_tlas_update_stats(C.byref(st)))
+    return st
+
+
 def BuildTopAccelStructBlob(instances):
     """Host-only TLAS build (no GPU): returns (blob bytes, max depth).  Extension used by the CPU tests."""
     L = _lib.lib()
@@ -463,12 +484,34 @@ def DebugAccelLayout(blob, quad=1, cull=-1, lib=None):
     Platform) -> (dict of the rdx_accel_scalars members, dict name -> structured array).  `lib`: another build of the library."""
     L = lib if lib is not None else _lib.lib()
     blob = bytes(blob)
-    sc = _lib.rdx_accel_scalars()
-    sizes = (C.c_size_t * 8)()
 
     def call(*args):
         if L.rdx_debug_accel_layout(blob, len(blob), int(quad), int(cull), *args) != 0:
             raise RadianceError(L.rdx_last_error().decode("utf-8", "replace"))
+    return _layout_from(call)
+
+
+def DebugAccelLayoutUpdate(blobs, quad=1, cull=-1):
+    """Test seam (rdx_debug_accel_layout_update): blobs[0] derived afresh, then updated through blobs[1:] the way UpdateAccelStruct
+    updates a device's layout -> (scalars, arrays, [path per step: 1 incremental, 2 full derivation]) of the last blob."""
+    L = _lib.lib()
+    blobs = [bytes(b) for b in blobs]
+    n = len(blobs)
+    ptrs = (C.c_char_p * n)(*blobs)
+    lens = (C.c_size_t * n)(*[len(b) for b in blobs])
+    paths = (C.c_uint32 * max(n - 1, 1))()
+
+    def call(*args):
+        if L.rdx_debug_accel_layout_update(ptrs, lens, n, int(quad), int(cull), *args, paths) != 0:
+            raise RadianceError(L.rdx_last_error().decode("utf-8", "replace"))
+    scalars, arrays = _layout_from(call)
+    return scalars, arrays, [int(paths[i]) for i in range(n - 1)]
+
+
+def _layout_from(call):
+    """(scalars, arrays) through a seam with the output convention of rdx_debug_accel_layout: a size query, then the arrays"""
+    sc = _lib.rdx_accel_scalars()
+    sizes = (C.c_size_t * 8)()
     call(C.byref(sc), None, sizes)
     arrays = {}
     for (name, dt), n in zip(ACCEL_ARRAYS, sizes):

@@ -6,13 +6,16 @@
 //
 // build: g++ -std=c++17 -Iinclude samples/cornell_rd.cpp -Lradiance-ray-tracing_amd -lrdx
 //            -Wl,-rpath,$PWD/radiance-ray-tracing_amd -o cornell_rd
-// run:   ./cornell_rd 320 180 8 out.ppm [frames per view = 2] [views = 1]
+// run:   ./cornell_rd 320 180 8 out.ppm [frames per view = 2] [views = 1] [--spin]
 //
 // With views > 1 it plays the host loop of the reference's interactive sample (samples/sample1.cpp:447-548) without a window:
 // every view is an "edit" -- the camera is moved, the camera buffer rewritten and totalSamples reset to 0, which is what the
 // reference's inspector does when a property changes -- followed by `frames` progressive frames (TraceRays; totalSamples +=
 // batchSize); the last frame of each view is written to <out minus .ppm>_<view>.ppm and the frame time is printed.
+// --spin: every frame first turns the tall box by 3 degrees about its own axis through RD::UpdateAccelStruct (the TLAS is
+// updated in place, not rebuilt) and restarts the accumulation, like an animated scene would.
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -50,6 +53,9 @@ static RD::Mesh makeBox(std::vector<RD::Vec3>& nrm, RD::Vec3 lo, RD::Vec3 hi)
 
 int main(int argc, char** argv)
 {
+    bool spin = false;
+    for (int i = 1; i < argc; ++i)
+        if (!strcmp(argv[i], "--spin")) { spin = true; for (int k = i; k + 1 < argc; ++k) argv[k] = argv[k + 1]; --argc; --i; }
     const int W = argc > 1 ? atoi(argv[1]) : 320, H = argc > 2 ? atoi(argv[2]) : 180;
     const unsigned spp = argc > 3 ? (unsigned)atoi(argv[3]) : 8;
     const std::string out = argc > 4 ? argv[4] : "cornell_rd.ppm";
@@ -173,6 +179,15 @@ int main(int argc, char** argv)
         }
         const auto t0 = std::chrono::steady_clock::now();
         for (int frame = 0; frame < framesPerView; ++frame) {
+            if (spin) {          // the tall box turns about its own vertical axis; the accumulation restarts
+                const float a = 0.309f + 0.0523599f * (float)(view * framesPerView + frame + 1), c = cosf(a), sn = sinf(a);
+                instances[5].transform = RD::Mat4x4(c, 0, sn, -1.2f, 0, 1, 0, 0, -sn, 0, c, 1.0f, 0, 0, 0, 1);
+                RD::UpdateAccelStruct(plt, rdTopAS, instances);
+                RD::RayTraceProperties p;
+                RD::ReadBuffer(plt, rdRTProp, sizeof p, &p);
+                p.totalSamples = 0;
+                RD::WriteBuffer(plt, rdRTProp, sizeof p, &p);
+            }
             RD::TraceRays(plt, 0, 0, 0, W, H);
             RD::ReadBuffer(plt, rdImage, imageSize, image.data());
             RD::RayTraceProperties p;
