@@ -159,6 +159,18 @@ inline void UpdateAccelStruct(Platform*, TopAccelStruct accelStruct, std::vector
 inline void TopAccelStructToFile(Platform*, TopAccelStruct accelStruct, const char* path) { if (rdx_tlas_to_file(accelStruct, path)) detail::fatal("TopAccelStructToFile"); }
 inline void FileToTopAccelStruct(Platform*, const char* path, TopAccelStruct* accelStruct) { *accelStruct = detail::need(rdx_tlas_from_file(path), "FileToTopAccelStruct"); }
 
+// Extension (no reference counterpart; rdx_resolve_hits): surface records (rdx_surface: world-space hit point, normal, the two
+// offset origins, uv, material number) for the `n` records `hits` that rdx_query_rays(..., RDX_QUERY_CLOSEST, ...) wrote for `rays`,
+// device memory in and out.  `scene` = the buffers bound to descriptor slots 5, 7, 8, 9.  Returns the number of records the bounds
+// rule refused (they are written as zeros).
+inline uint32_t ResolveHits(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer hits, uint32_t n, const rdx_surface_buffers& scene,
+                            Buffer out, size_t raysOffset = 0, size_t hitsOffset = 0, size_t outOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_resolve_hits(accelStruct, rays, raysOffset, hits, hitsOffset, n, &scene, out, outOffset, &invalid)) detail::fatal("ResolveHits");
+    return invalid;
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

@@ -279,6 +279,46 @@ typedef struct rdx_ray_hit { float t, b1, b2; uint32_t hit;
 int         rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, uint32_t n, int kind,
                            rdx_buffer hits, size_t hits_offset);
 
+/* Surface records for the hits of a ray query, on the device: what secondary work needs beyond the ids of an rdx_ray_hit -- the
+ * world-space hit point, the surface normal, the origins of the next ray on either side of the surface, the uv and the material
+ * number.  `rays` / `hits` are the buffers of an rdx_query_rays(..., RDX_QUERY_CLOSEST, ...) call (record i belongs to ray i;
+ * records the caller filled in are equally allowed), `scene` the buffers bound to descriptor slots 5, 7, 8, 9; one 64-byte
+ * rdx_surface per ray goes to `out` at byte `out_offset`.  For a hit (`hit` == 1) every field holds the bits the reference's
+ * closest-hit shader computes for that HitData under the floating-point contract of DESIGN.md 2: hitPoint = inv (o, 1) +
+ * inv (d, 0) * t with the instance's inverse as the traversal layout holds it, barycentric = ((1 - b1) - b2, b1, b2), MeshInfo taken
+ * by instanceIndex, normal = getFaceNormal (samples/shader.cl:338-367), above / below = getHitPosition(hitData, +-normal)
+ * (shader.cl:453-468: the stock shader's nextRayOrigin is one of the two), (u, v) = getUV (shader.cl:322-336).  Every other record
+ * -- a miss, any other value of `hit` -- is 64 zero bytes.  Shading normals from normal maps and material parameters are not
+ * resolved here.
+ * No record makes the kernel read outside a buffer: a hit is INVALID when instanceIndex is not below the TLAS's instance count and
+ * the number of MeshInfo records, or one of its three index reads, nine normal reads or six uv reads falls outside its buffer
+ * (MeshInfo offsets are int32 and may be negative; the positions are computed in 64 bits), or no instance of the TLAS carries that
+ * instanceIndex.  An invalid hit writes the zero record and is counted; the call still returns 0 and *invalid_out (optional)
+ * receives the count.  Nothing is staged and nothing is allocated per call; the call blocks like every call of this ABI, accepts
+ * every TLAS buffer rdx_query_rays accepts, derives the traversal layout if none exists yet, sees the transforms of the last
+ * rdx_tlas_update, and runs on logical device 0 in multi-device mode.  rdx_get_trace_stats().ms_shade is the kernel time of the
+ * call.  Refused, before anything is launched: an uninitialised library, an unknown or NULL handle, `scene` NULL or meshInfo /
+ * index / normal NULL in it, an offset that is not a multiple of 16, offset + 32 * n (rays, hits) or offset + 64 * n (out) beyond
+ * its buffer, `out` overlapping the ray range or the hit range.  n == 0 succeeds and touches nothing. */
+typedef struct rdx_surface_buffers { rdx_buffer meshInfo, index, uv, normal; } rdx_surface_buffers;
+    /* the buffers of descriptor slots 5, 7, 8, 9; uv may be NULL (u = v = 0) */
+typedef struct rdx_surface {                    /* 64 B, four float4 */
+    float position[3]; uint32_t hit;            /* HitData.transform * (HitData.hitPoint, 1), xyz; hit: 1 / 0 */
+    float normal[3];   uint32_t materialIndex;  /* getFaceNormal (samples/shader.cl:338-367); MeshInfo.materialIndex */
+    float above[3];    float u;                 /* getHitPosition(hitData,  normal) (shader.cl:453-468); getUV().x */
+    float below[3];    float v;                 /* getHitPosition(hitData, -normal);                     getUV().y */
+} rdx_surface;
+int         rdx_resolve_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset,
+                             uint32_t n, const rdx_surface_buffers* scene, rdx_buffer out, size_t out_offset,
+                             uint32_t* invalid_out /* optional */);
+/* Test seam: the bounds rule above for one record, on the host (needs no device and no initialised library) -> 1 = may be
+ * resolved, 0 = invalid.  mi = the MeshInfo records (nmeshinfo of them; read only if instanceIndex is inside), idx3 = the
+ * triangle's three vertex numbers (NULL: the rule ends after the index range, which is what must hold before they may be read),
+ * nindex / nnormal / nuv = elements of the three streams, nuv == 0: no uv stream, nothing of it is checked. */
+int         rdx_debug_surface_in_bounds(const rdx_mesh_info* mi, uint32_t ninst, uint32_t nmeshinfo, uint32_t instanceIndex,
+                                        uint32_t primitiveIndex, const uint32_t idx3[3], uint64_t nindex, uint64_t nnormal,
+                                        uint64_t nuv);
+
 /* Test seams: run single stages on caller-supplied batches (device or host pointers are NOT
  * accepted -- plain host arrays in, host arrays out; the library stages them through HBM). */
 typedef struct rdx_hit {

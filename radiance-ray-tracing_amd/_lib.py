@@ -66,6 +66,15 @@ class rdx_ray_hit(C.Structure):
                 ("instanceIndex", C.c_uint32), ("instanceCustomIndex", C.c_uint32), ("instanceSBTOffset", C.c_uint32)]
 
 
+class rdx_surface_buffers(C.Structure):
+    _fields_ = [("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p)]
+
+
+class rdx_surface(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("hit", C.c_uint32), ("normal", C.c_float * 3), ("materialIndex", C.c_uint32),
+                ("above", C.c_float * 3), ("u", C.c_float), ("below", C.c_float * 3), ("v", C.c_float)]
+
+
 class rdx_payload(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("hit", C.c_uint32), ("nextFactor", C.c_float * 3),
                 ("nextRayOrigin", C.c_float * 3), ("nextRayDirection", C.c_float * 3)]
@@ -124,6 +133,10 @@ SIGNATURES = {
     "rdx_set_profiling": (C.c_int, [C.c_int]),
     "rdx_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
     "rdx_query_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t]),
+    "rdx_resolve_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(rdx_surface_buffers),
+                                   C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rdx_debug_surface_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                              C.c_uint64, C.c_uint64, C.c_uint64]),
     "rdx_trace_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     "rdx_material_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -6,6 +6,7 @@
 
 #include "../../include/rdx.h"
 #include "rdx_types.h"
+#include "surface.h"
 #include "texture.h"
 
 namespace rdx {
@@ -154,5 +155,9 @@ void launch_pcg3d_batch(hipStream_t st, const uint32_t* in3, float* out3, uint32
 // TLAS update: tris[first + k]._p0 = owner for every range of `table` = {first, count, owner, slots in the ranges before}; `total`
 // = slots of all ranges (device table; ranges inside [0, nTris))
 void launch_tri_owner_fill(hipStream_t st, DTri* tris, uint32_t nTris, const uint4* table, uint32_t nRanges, uint32_t total);
+// rdx_resolve_hits (surface.hip): surface records of n closest-hit query records; slotOf[instanceIndex] = the instance's slot in
+// `insts` or 0xffffffff (nInst words); *invalid += records that fail surface_in_bounds (surface.h)
+void launch_resolve_hits(hipStream_t st, const DInst* insts, const uint32_t* slotOf, uint32_t nInst, const float4* rays, const float4* hits,
+                         uint32_t n, const SurfaceScene& sc, float4* out, uint32_t* invalid);
 
 } // namespace rdx

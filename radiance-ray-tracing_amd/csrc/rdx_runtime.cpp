@@ -61,6 +61,7 @@ struct AccelCache {                // derived traversal layout of one TLAS buffe
     DWide* wide = nullptr;
     DQuad* quad = nullptr;             // null: the quad records were not built
     uint32_t* groupBits = nullptr;     // 9 words
+    uint32_t* slotOf = nullptr;        // rdx_resolve_hits: slotOf[instanceIndex] = slot in `insts`, 0xffffffff = no such instance (nInst words)
     rdx_accel_scalars s{};             // coopOK: ... and the engines' LDS footprint fits (derive_accel)
     // rdx_tlas_update: the host side of the layout without its four large arrays (small arrays, scalars, per-BLAS book), the
     // elements tnodes / ctnodes and wide were allocated for, and the device table of the owner-fill kernel
@@ -69,10 +70,10 @@ struct AccelCache {                // derived traversal layout of one TLAS buffe
     uint4* ownerTable = nullptr; size_t ownerCap = 0;
     void release()
     {
-        for (void* p : {(void*)tnodes, (void*)ctnodes, (void*)insts, (void*)bnodes, (void*)tris, (void*)wide, (void*)quad, (void*)groupBits, (void*)ownerTable})
+        for (void* p : {(void*)tnodes, (void*)ctnodes, (void*)insts, (void*)bnodes, (void*)tris, (void*)wide, (void*)quad, (void*)groupBits, (void*)ownerTable, (void*)slotOf})
             if (p) HIP_IGN(hipFree(p));
         tnodes = nullptr; ctnodes = nullptr; insts = nullptr; bnodes = nullptr; tris = nullptr; wide = nullptr; quad = nullptr; groupBits = nullptr;
-        ownerTable = nullptr; ownerCap = 0;
+        ownerTable = nullptr; ownerCap = 0; slotOf = nullptr;
     }
 };
 
@@ -145,6 +146,7 @@ struct Context {
     uint32_t* hStatus = nullptr;            // pinned, device-mapped: bit 0 = a traversal wave hit its iteration bound
     uint32_t* dStatus = nullptr;            // its device address
     unsigned long long* dVisit = nullptr;   // 8 words
+    uint32_t* dSurfaceInvalid = nullptr;    // rdx_resolve_hits: records that failed the bounds rule, one word
     unsigned long long* hVisit = nullptr;   // pinned
     // everything rdx_set_option / rdx_set_profiling write, except the builder's knobs below: handed to the other devices'
     // contexts as a whole (rdx_trace_rays)
@@ -233,6 +235,17 @@ bool runtime_coop_ok(const rdx_accel_scalars& S)
            pool_lds_words(std::max(S.topNeed, S.topFlatNeed), std::max({S.blasNeed, S.blasNeedAny, S.quadNeed, S.quadUnifiedNeed})) <= RDX_LDS_WORDS_PER_WAVE_MAX;
 }
 
+// HitData.instanceIndex is the instance's number in the caller's array (BlobInst.instanceID); the layout's instance records are
+// ordered by slot, the order of the top-level leaves.  rdx_resolve_hits finds the record through this table.  An index no instance
+// carries (blobs this library did not build may hold anything) maps to 0xffffffff; of two instances with one index the first slot.
+std::vector<uint32_t> slot_table(const std::vector<DInst>& insts)
+{
+    std::vector<uint32_t> t(insts.size(), 0xffffffffu);
+    for (size_t k = insts.size(); k-- > 0;)
+        if (insts[k].instanceID < t.size()) t[insts[k].instanceID] = (uint32_t)k;
+    return t;
+}
+
 // accel_layout.cpp derives it on the host; here it is uploaded to the calling thread's device
 int derive_accel(rdx_buffer_s* tb)
 {
@@ -265,6 +278,8 @@ int derive_accel(rdx_buffer_s* tb)
     HIP_OK(up(ac->wide, L.wide.data(), L.wide.size()));
     if (!L.quad.empty()) HIP_OK(up(ac->quad, L.quad.data(), L.quad.size()));
     HIP_OK(up(ac->groupBits, L.groupBits, 9));
+    const std::vector<uint32_t> slots = slot_table(L.insts);
+    HIP_OK(up(ac->slotOf, slots.data(), slots.size()));
     const rdx_accel_scalars& S = ac->s;
     ac->s.coopOK = runtime_coop_ok(S);
     if (std::getenv("RDX_VERBOSE"))
@@ -540,6 +555,7 @@ static int init_device_state(int device)
     HIP_OK(hipHostGetDevicePointer(reinterpret_cast<void**>(&g.dStatus), g.hStatus, 0));
     HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dVisit), 64 * 8 * sizeof(unsigned long long)));     // [bounce][class*4 + kind]
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&g.hVisit), 64 * 8 * sizeof(unsigned long long), hipHostMallocDefault));
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dSurfaceInvalid), sizeof(uint32_t)));
     g.initialized = true;
     return 0;
 }
@@ -575,6 +591,8 @@ static void release_device_state()
     g.hStatus = nullptr; g.dStatus = nullptr;
     if (g.dVisit) HIP_IGN(hipFree(g.dVisit));
     if (g.hVisit) HIP_IGN(hipHostFree(g.hVisit));
+    if (g.dSurfaceInvalid) HIP_IGN(hipFree(g.dSurfaceInvalid));
+    g.dSurfaceInvalid = nullptr;
     HIP_IGN(hipEventDestroy(g.evA)); HIP_IGN(hipEventDestroy(g.evB)); HIP_IGN(hipEventDestroy(g.evChunk));
     HIP_IGN(hipStreamDestroy(g.stream));
 }
@@ -1065,7 +1083,11 @@ int update_accel(rdx_buffer_s* tb, uint64_t oldVersion, rdx_tlas_update_stats& s
     };
     if (upd.tnodes) HIP_OK(h2d(ac->tnodes, L.tnodes.data(), L.tnodes.size() * sizeof(DNode)));
     if (upd.ctnodes) HIP_OK(h2d(ac->ctnodes, L.ctnodes.data(), L.ctnodes.size() * sizeof(DNode)));
-    if (upd.insts) HIP_OK(h2d(ac->insts, L.insts.data(), L.insts.size() * sizeof(DInst)));
+    const std::vector<uint32_t> slots = slot_table(L.insts);        // (lives until the synchronisation below)
+    if (upd.insts) {
+        HIP_OK(h2d(ac->insts, L.insts.data(), L.insts.size() * sizeof(DInst)));
+        HIP_OK(h2d(ac->slotOf, slots.data(), slots.size() * sizeof(uint32_t)));     // another top-level tree orders the slots anew
+    }
     if (upd.groupBits) HIP_OK(h2d(ac->groupBits, L.groupBits, sizeof L.groupBits));
     if (upd.wideTailChanged) HIP_OK(h2d(ac->wide + upd.wideTailFirst, upd.wideTail.data(), upd.wideTail.size() * sizeof(DWide)));
     std::vector<uint4> table;
@@ -2107,6 +2129,74 @@ extern "C" int rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offs
     std::memset(&g.stats, 0, sizeof g.stats);
     HIP_OK(hipEventElapsedTime(&g.stats.ms_extend, g.evA, g.evB));      // kernel time of this call
     return 0;
+}
+
+// Surface records of a query's hits (surface.hip): the checks and the steps around the launch are those of rdx_query_rays
+extern "C" int rdx_resolve_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, uint32_t n,
+                                const rdx_surface_buffers* scene, rdx_buffer out, size_t out_offset, uint32_t* invalid_out)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_resolve_hits: invalid TLAS handle");
+    if (!rays || !known_buffer(rays)) return fail("rdx_resolve_hits: invalid ray buffer handle");
+    if (!hits || !known_buffer(hits)) return fail("rdx_resolve_hits: invalid hit buffer handle");
+    if (!out || !known_buffer(out)) return fail("rdx_resolve_hits: invalid output buffer handle");
+    if (!scene) return fail("rdx_resolve_hits: no scene buffers");
+    if (!scene->meshInfo || !known_buffer(scene->meshInfo)) return fail("rdx_resolve_hits: invalid meshInfo buffer handle");
+    if (!scene->index || !known_buffer(scene->index)) return fail("rdx_resolve_hits: invalid index buffer handle");
+    if (!scene->normal || !known_buffer(scene->normal)) return fail("rdx_resolve_hits: invalid normal buffer handle");
+    if (scene->uv && !known_buffer(scene->uv)) return fail("rdx_resolve_hits: invalid uv buffer handle");
+    if ((rays_offset & 15u) || (hits_offset & 15u) || (out_offset & 15u))
+        return fail("rdx_resolve_hits: offsets must be multiples of 16 bytes (rays_offset %zu, hits_offset %zu, out_offset %zu)", rays_offset, hits_offset, out_offset);
+    static_assert(sizeof(rdx_surface) == 64 && sizeof(MeshInfo) == sizeof(rdx_mesh_info), "four float4 per surface record");
+    const size_t bytes = (size_t)n * sizeof(rdx_ray), outBytes = (size_t)n * sizeof(rdx_surface);
+    if (rays_offset > rays->size || bytes > rays->size - rays_offset)
+        return fail("rdx_resolve_hits: %u rays at offset %zu run past the ray buffer (%zu bytes)", n, rays_offset, rays->size);
+    if (hits_offset > hits->size || bytes > hits->size - hits_offset)
+        return fail("rdx_resolve_hits: %u records at offset %zu run past the hit buffer (%zu bytes)", n, hits_offset, hits->size);
+    if (out_offset > out->size || outBytes > out->size - out_offset)
+        return fail("rdx_resolve_hits: %u surface records at offset %zu run past the output buffer (%zu bytes)", n, out_offset, out->size);
+    if (invalid_out) *invalid_out = 0;
+    if (!n) return 0;
+    if ((reinterpret_cast<uintptr_t>(rays->dptr) & 15u) || (reinterpret_cast<uintptr_t>(hits->dptr) & 15u) || (reinterpret_cast<uintptr_t>(out->dptr) & 15u))
+        return fail("rdx_resolve_hits: wrapped device memory must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(scene->meshInfo->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->index->dptr) & 3u) ||
+        (reinterpret_cast<uintptr_t>(scene->normal->dptr) & 3u) || (scene->uv && (reinterpret_cast<uintptr_t>(scene->uv->dptr) & 3u)))
+        return fail("rdx_resolve_hits: wrapped scene streams must be 4-byte aligned");
+    {   // the output must not overlap what the kernel reads of the rays and of the records, in one buffer or in several that wrap the same memory
+        const uintptr_t r0 = reinterpret_cast<uintptr_t>(rays->dptr) + rays_offset, h0 = reinterpret_cast<uintptr_t>(hits->dptr) + hits_offset,
+                        o0 = reinterpret_cast<uintptr_t>(out->dptr) + out_offset;
+        if (o0 < r0 + bytes && r0 < o0 + outBytes) return fail("rdx_resolve_hits: the output range and the ray range overlap");
+        if (o0 < h0 + bytes && h0 < o0 + outBytes) return fail("rdx_resolve_hits: the output range and the hit range overlap");
+    }
+    if (derive_accel(tlas)) return -1;
+    const AccelCache& ac = *acc(tlas);
+    SurfaceScene sc{};
+    sc.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
+    sc.index = static_cast<const uint32_t*>(scene->index->dptr); sc.nIndex = scene->index->size / sizeof(uint32_t);
+    sc.normal = static_cast<const float*>(scene->normal->dptr); sc.nNormal = scene->normal->size / sizeof(float);
+    if (scene->uv && scene->uv->size >= sizeof(float)) { sc.uv = static_cast<const float*>(scene->uv->dptr); sc.nUv = scene->uv->size / sizeof(float); }
+    HIP_OK(hipMemsetAsync(g.dSurfaceInvalid, 0, sizeof(uint32_t), g.stream));
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_resolve_hits(g.stream, ac.insts, ac.slotOf, ac.s.nInst, reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset),
+                        reinterpret_cast<const float4*>(static_cast<const char*>(hits->dptr) + hits_offset), n, sc,
+                        reinterpret_cast<float4*>(static_cast<char*>(out->dptr) + out_offset), g.dSurfaceInvalid);
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    ++out->version; out->mirrorValid = false;      // device code wrote it
+    uint32_t invalid = 0;
+    HIP_OK(hipMemcpy(&invalid, g.dSurfaceInvalid, sizeof invalid, hipMemcpyDeviceToHost));
+    if (invalid_out) *invalid_out = invalid;
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
+    return 0;
+}
+
+extern "C" int rdx_debug_surface_in_bounds(const rdx_mesh_info* mi, uint32_t ninst, uint32_t nmeshinfo, uint32_t instanceIndex,
+                                           uint32_t primitiveIndex, const uint32_t idx3[3], uint64_t nindex, uint64_t nnormal, uint64_t nuv)
+{
+    if (!mi) return fail("rdx_debug_surface_in_bounds: no MeshInfo records");
+    return surface_in_bounds(reinterpret_cast<const MeshInfo*>(mi), ninst, nmeshinfo, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv) ? 1 : 0;
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,

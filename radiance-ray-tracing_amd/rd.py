@@ -465,6 +465,93 @@ def QueryRaysTorch(tlas, rays_tensor, kind=QUERY_CLOSEST, out=None):
     return out
 
 
+# ---- surface records of a query's hits (rdx_resolve_hits) ----------------------------------------------------------
+SURFACE_DTYPE = np.dtype([("position", "<f4", 3), ("hit", "<u4"), ("normal", "<f4", 3), ("materialIndex", "<u4"),
+                          ("above", "<f4", 3), ("u", "<f4"), ("below", "<f4", 3), ("v", "<f4")])
+assert SURFACE_DTYPE.itemsize == C.sizeof(_lib.rdx_surface) == 64
+
+
+class SurfaceBuffers:
+    """rdx_surface_buffers: the Buffers bound to descriptor slots 5, 7, 8, 9; uv may be None (u = v = 0)"""
+
+    def __init__(self, meshInfo, index, uv, normal):
+        self.meshInfo, self.index, self.uv, self.normal = meshInfo, index, uv, normal
+
+    def _struct(self):
+        for name in ("meshInfo", "index", "normal"):
+            if not isinstance(getattr(self, name), Buffer):
+                raise RadianceError("ResolveHits: scene_buffers.%s must be a Buffer" % name)
+        if self.uv is not None and not isinstance(self.uv, Buffer):
+            raise RadianceError("ResolveHits: scene_buffers.uv must be a Buffer or None")
+        return _lib.rdx_surface_buffers(self.meshInfo.handle, self.index.handle, self.uv.handle if self.uv is not None else None,
+                                        self.normal.handle)
+
+
+def ResolveHits(tlas, rays, hits, n, scene_buffers, out=None, rays_offset=0, hits_offset=0, out_offset=0):
+    """Extension: one SURFACE_DTYPE record per ray -- world-space hit point, normal, the offset origins on either side of the
+    surface, uv, material number -- for the `n` RAY_HIT_DTYPE records QueryRays(..., QUERY_CLOSEST) wrote to `hits` for `rays`;
+    device buffers in, device buffer out (created when None: out_offset + 64 n bytes).  scene_buffers: a SurfaceBuffers, or a
+    (meshInfo, index, uv, normal) tuple of Buffers.  Misses are 64 zero bytes; so are hits that would read outside a scene
+    buffer, which are counted.  Returns (out, invalid)."""
+    if not (isinstance(tlas, Buffer) and isinstance(rays, Buffer) and isinstance(hits, Buffer)):
+        raise RadianceError("ResolveHits: tlas, rays and hits must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    if not isinstance(scene_buffers, SurfaceBuffers):
+        try:
+            scene_buffers = SurfaceBuffers(*scene_buffers)
+        except TypeError:
+            raise RadianceError("ResolveHits: scene_buffers must be a SurfaceBuffers or a (meshInfo, index, uv, normal) tuple")
+    sb = scene_buffers._struct()
+    if out is None:
+        out = CreateBuffer(None, max(int(out_offset) + SURFACE_DTYPE.itemsize * int(n), 1))
+    elif not isinstance(out, Buffer):
+        raise RadianceError("ResolveHits: out must be a Buffer or None")
+    invalid = C.c_uint32(0)
+    _check(_lib.lib().rdx_resolve_hits(tlas.handle, rays.handle, int(rays_offset), hits.handle, int(hits_offset), int(n), C.byref(sb),
+                                       out.handle, int(out_offset), C.byref(invalid)))
+    return out, int(invalid.value)
+
+
+def ResolveHitsTorch(tlas, rays_tensor, hits_tensor, scene_buffers, out=None):
+    """Extension: ResolveHits on CUDA tensors -- rays a contiguous float32 (n, 8) tensor, hits the contiguous int32 / float32 (n, 8)
+    tensor QueryRaysTorch returned for them; the records land in `out`, a contiguous float32 CUDA tensor of shape (n, 16)
+    (created when None; `.view(torch.int32)` shows hit and materialIndex in columns 3 and 7).  The library cannot see torch's
+    stream, so the current stream is synchronised first; the call blocks.  Returns (out, invalid)."""
+    import torch
+    r, h = rays_tensor, hits_tensor
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
+        raise RadianceError("ResolveHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(r.shape[0])
+    if not (isinstance(h, torch.Tensor) and h.is_cuda and h.dtype in (torch.int32, torch.float32) and tuple(h.shape) == (n, 8)
+            and h.is_contiguous() and h.device == r.device):
+        raise RadianceError("ResolveHitsTorch: hits must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
+    if out is None:
+        out = torch.empty((n, 16), dtype=torch.float32, device=r.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 16)
+              and out.is_contiguous() and out.device == r.device):
+        raise RadianceError("ResolveHitsTorch: out must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device")
+    torch.cuda.current_stream(r.device).synchronize()
+    invalid = 0
+    if n:
+        rays = WrapDeviceMemory(None, r.data_ptr(), n * 32, keepalive=r)
+        hits = WrapDeviceMemory(None, h.data_ptr(), n * 32, keepalive=h)
+        dst = WrapDeviceMemory(None, out.data_ptr(), n * 64, keepalive=out)
+        _, invalid = ResolveHits(tlas, rays, hits, n, scene_buffers, dst)
+    return out, invalid
+
+
+def DebugSurfaceInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv, nmeshinfo=None):
+    """Test seam (rdx_debug_surface_in_bounds): the bounds rule of ResolveHits for one record, on the host -> bool.  meshInfo: a
+    MeshInfo array (nmeshinfo defaults to its length), idx3: the triangle's three vertex numbers or None."""
+    mi = np.ascontiguousarray(meshInfo, MeshInfo).reshape(-1)
+    nm = mi.shape[0] if nmeshinfo is None else int(nmeshinfo)
+    iv = None if idx3 is None else (C.c_uint32 * 3)(*[int(x) & 0xffffffff for x in idx3])
+    rc = _lib.lib().rdx_debug_surface_in_bounds(mi.ctypes.data_as(C.POINTER(_lib.rdx_mesh_info)), int(ninst), nm, int(instanceIndex) & 0xffffffff,
+                                                int(primitiveIndex) & 0xffffffff, iv, int(nindex), int(nnormal), int(nuv))
+    if rc < 0:
+        raise RadianceError(_lib.last_error())
+    return rc == 1
+
+
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
 _DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
 _DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),

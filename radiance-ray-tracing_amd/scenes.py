@@ -314,6 +314,10 @@ class DeviceScene:
         self.pipeline = rd.CreatePipeline(rd.PipelineCreateInfo(1, layout, [shader], []))
         self.bind()
 
+    def surface_buffers(self):
+        """the four scene streams rd.ResolveHits reads (descriptor slots 5, 7, 8, 9)"""
+        return rd.SurfaceBuffers(self.meshInfoData, self.indexData, self.uvData, self.normalData)
+
     def bind(self):
         rd.BindPipeline(self.plt, self.pipeline)
         rd.BindDescriptorSet(self.plt, self.descSet)
