@@ -239,7 +239,10 @@ int         rdx_set_profiling(int on);
  * stage functions runs those functions on the wavefront pipeline; 0 = every user program is a megakernel; 2 = the
  * caller asserts eligibility for a program written from scratch, whose raygen is then ignored.  Read by
  * rdx_shader_module_create), "group_instances" (1 (default) / 0: instances whose inverse matrices are bit-identical share one
- * object-space ray and are walked concurrently, traverse_pool.h), "top_flat" (1 (default) / 0: the pool kernel evaluates a top-level tree of <= 64 nodes all at once per
+ * object-space ray and are walked concurrently, traverse_pool.h), "group_entry_items" (1 (default) / 0: over quad records a ray
+ * enters all pending instances of that group in one step, as pool items that point at per-instance entry records -- the root
+ * test is the pool step's; 0 = one instance record and one root test per instance step; results do not depend
+ * on it), "top_flat" (1 (default) / 0: the pool kernel evaluates a top-level tree of <= 64 nodes all at once per
  * ray instead of walking it), "inline_leaf_roots" (1 (default) / 0: ... and tests the triangles of single-leaf BLASes
  * right there), "pipeline" (0 = staged
  * wavefront: one launch per stage per bounce; 1 = whole paths -- camera ray to path end -- in one persistent launch per
@@ -383,6 +386,14 @@ int         rdx_debug_accel_layout(const void* blob, size_t size, int quad, int 
  * path_per_step (optional, count - 1 entries): 1 = that step was incremental, 2 = it took the full derivation.  Needs no device. */
 int         rdx_debug_accel_layout_update(const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull,
                                           rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes, uint32_t* path_per_step);
+
+
+/* Test seam: the entry records of the layout of blobs[count - 1], reached like rdx_debug_accel_layout_update reaches it (count 1: a
+ * plain derivation) -- one 128-byte quad record per instance slot (csrc/accel_layout.h AccelLayout::entries; none without quad
+ * records), which the runtime keeps behind the quad records on the device -- and, in *need (optional), the pool need of a walk
+ * that starts at one.  *bytes: in, the capacity of `entries` (ignored when `entries` is NULL: a size query); out, their size. */
+int         rdx_debug_accel_entries(const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull,
+                                    void* entries, size_t* bytes, uint32_t* need);
 
 #ifdef __cplusplus
 }

@@ -147,6 +147,8 @@ SIGNATURES = {
     "rdx_debug_accel_layout_update": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_int,
                                                 C.POINTER(rdx_accel_scalars), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                 C.POINTER(C.c_uint32)]),
+    "rdx_debug_accel_entries": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_int, C.c_void_p,
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "rdx_obj_load": (C.c_int, [C.c_char_p, C.POINTER(rdx_obj_scene)]),
     "rdx_obj_free": (None, [C.POINTER(rdx_obj_scene)]),
 }

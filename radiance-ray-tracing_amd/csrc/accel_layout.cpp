@@ -188,7 +188,9 @@ void quad_order(int arr, int ord[4])
 struct BlasInfo { uint32_t nodeBase; uint32_t need; uint32_t coopNeed; uint32_t anyNeed; uint32_t triBase; uint32_t rootDesc0, rootDesc1; float rootMin[3], rootMax[3];
                   uint32_t nTris; uint32_t users;
                   uint32_t quadNeed;        // pool-stack need of the quad walk from its root (0: leaf root, or no quad records)
-                  uint32_t owner; };        // DTri._p0 of its triangles: the slot of its one instance (group / unified tree), or 0xffffffff
+                  uint32_t owner;           // DTri._p0 of its triangles: the slot of its one instance (group / unified tree), or 0xffffffff
+                  DQuad entry;              // entry record of its root (step 6b) and the pool need of a walk that starts there;
+                  uint32_t entryNeed; };    // need 0 and an inert record: leaf root, or no quad records
 
 // one derivation: the steps below run in the order of derive_accel_layout and share this state
 struct Deriver {
@@ -240,6 +242,7 @@ struct Deriver {
     void unified_tree();
     void write_owners();
     int quad_records();
+    void entry_records();
     void make_book();
     int top_level_needs();
 };
@@ -334,6 +337,7 @@ int Deriver::import_blas(uint32_t byteOffset, BlasInfo& info)
         d.e2[0] = v2[0] - v0[0]; d.e2[1] = v2[1] - v0[1]; d.e2[2] = v2[2] - v0[2]; d._p1 = triBase;       // radiance.cl:216; _p1: first triangle slot of this BLAS
     }
     info = BlasInfo{};
+    for (int hh = 0; hh < 2; ++hh) { info.entry.half[hh].ld1 = WIDE_LEAF; info.entry.half[hh].rd1 = WIDE_LEAF; }
     info.nodeBase = nodeBase; info.triBase = triBase; info.nTris = nTris; info.users = 0; info.owner = 0xffffffffu;
     if (blas_wide_records(bn, nNodes, triBase, info)) return -1;
     if (nTris > RDX_COOP_MAX_BLAS_TRIS) { coopOK = false; coopBlasOK = false; }
@@ -637,6 +641,32 @@ int Deriver::quad_records()
         }
         if (!pair) { out[0] = c; empty(out[1]); }
     };
+    // the four entries of a record whose targets are done, in the order of the smallest need -> the record and that need
+    auto place = [&](const QE e[4], DQuad& q) -> uint32_t {
+        auto nd = [&](const QE& x) -> int { return (x.d1 & WIDE_LEAF) ? -1 : (int)qneed[x.d0]; };
+        uint32_t bestNeed = ~0u; int bestArr = 0;
+        int ord[4];
+        for (int arr = 0; arr < 8; ++arr) {
+            quad_order(arr, ord);
+            uint32_t inner = 0, need = 0;
+            for (int j = 3; j >= 0; --j) {          // j = pop position; `inner` = inner entries popped after j
+                const int n = nd(e[ord[j]]);
+                if (n < 0) continue;
+                need = std::max(need, inner + (uint32_t)n);
+                ++inner;
+            }
+            need = std::max(need, inner);
+            if (need < bestNeed) { bestNeed = need; bestArr = arr; }
+        }
+        quad_order(bestArr, ord);
+        for (int hh = 0; hh < 2; ++hh) {
+            const QE& a = e[ord[2 * hh]]; const QE& b = e[ord[2 * hh + 1]];
+            DWide& w = q.half[hh];
+            for (int k = 0; k < 3; ++k) { w.lmin[k] = a.mn[k]; w.lmax[k] = a.mx[k]; w.rmin[k] = b.mn[k]; w.rmax[k] = b.mx[k]; }
+            w.ld0 = a.d0; w.ld1 = a.d1; w.rd0 = b.d0; w.rd1 = b.d1;
+        }
+        return bestNeed;
+    };
     // children first: explicit DFS over the records (BLAS records have larger-index children, unified records smaller ones)
     std::vector<uint8_t> state(dW.size(), 0);       // 0 new, 1 open, 2 done
     std::vector<uint32_t> stk;
@@ -659,37 +689,47 @@ int Deriver::quad_records()
                 if (wait) continue;
             }
             // all targets done: order the entries and store the record
-            auto nd = [&](const QE& x) -> int { return (x.d1 & WIDE_LEAF) ? -1 : (int)qneed[x.d0]; };
-            uint32_t bestNeed = ~0u; int bestArr = 0;
-            int ord[4];
-            for (int arr = 0; arr < 8; ++arr) {
-                quad_order(arr, ord);
-                uint32_t inner = 0, need = 0;
-                for (int j = 3; j >= 0; --j) {          // j = pop position; `inner` = inner entries popped after j
-                    const int n = nd(e[ord[j]]);
-                    if (n < 0) continue;
-                    need = std::max(need, inner + (uint32_t)n);
-                    ++inner;
-                }
-                need = std::max(need, inner);
-                if (need < bestNeed) { bestNeed = need; bestArr = arr; }
-            }
-            quad_order(bestArr, ord);
-            DQuad& q = dQ[i];
-            for (int hh = 0; hh < 2; ++hh) {
-                const QE& a = e[ord[2 * hh]]; const QE& b = e[ord[2 * hh + 1]];
-                DWide& w = q.half[hh];
-                for (int k = 0; k < 3; ++k) { w.lmin[k] = a.mn[k]; w.lmax[k] = a.mx[k]; w.rmin[k] = b.mn[k]; w.rmax[k] = b.mx[k]; }
-                w.ld0 = a.d0; w.ld1 = a.d1; w.rd0 = b.d0; w.rd1 = b.d1;
-            }
-            qneed[i] = bestNeed;
+            qneed[i] = place(e, dQ[i]);
             state[i] = 2;
             stk.pop_back();
         }
     }
     for (auto& kv : blasAt) kv.second.quadNeed = (kv.second.rootDesc1 & WIDE_LEAF) ? 0u : qneed[kv.second.rootDesc0];
     unifiedQuadNeed = L.s.unifiedRoot ? qneed[L.s.unifiedRoot] : 0u;
+    // Entry records (step 6b): the half for a "child" that is the BLAS root R itself -- its two children under R's box when
+    // that box is their union, else R with its own box -- and an empty second half.  A pool item that points there decides the
+    // root test of radiance.cl:61-63 (and, in the pair form, one level below it) by the quad records' own inclusion argument.
+    for (auto& kv : blasAt) {
+        BlasInfo& bi = kv.second;
+        if (bi.rootDesc1 & WIDE_LEAF) continue;
+        DWide N{};
+        for (int k = 0; k < 3; ++k) { N.lmin[k] = bi.rootMin[k]; N.lmax[k] = bi.rootMax[k]; }
+        N.ld0 = bi.rootDesc0; N.ld1 = bi.rootDesc1;
+        QE e[4];
+        half_of(N, 0, e); empty(e[2]); empty(e[3]);
+        bi.entryNeed = place(e, bi.entry);
+    }
     return 0;
+}
+
+// ---- step 6b: entry records ----------------------------------------------------------------------------------------------------
+// One per instance slot, behind the quad records on the device (pool item index = quad records + slot): the entry record of the
+// instance's BLAS, or an inert record (four empty entries) for a leaf root -- which the engine never addresses.  They depend on
+// the instance's BLAS alone, so an update only re-orders them.
+void Deriver::entry_records()
+{
+    DQuad inert{};
+    for (int hh = 0; hh < 2; ++hh) { inert.half[hh].ld1 = WIDE_LEAF; inert.half[hh].rd1 = WIDE_LEAF; }
+    L.entries.assign(want_quad() ? nInst : 0u, inert);
+    L.entryNeed = 0;
+    L.groupFirst = 0;
+    for (uint32_t k = std::min(nInst, 256u); k-- > 0;) if (L.groupBits[k >> 5] & (1u << (k & 31u))) L.groupFirst = k;
+    for (size_t k = 0; k < L.entries.size(); ++k) {
+        const BlasInfo& bi = blasAt[binst[k].instanceOffset];
+        if (bi.rootDesc1 & WIDE_LEAF) continue;
+        L.entries[k] = bi.entry;
+        L.entryNeed = std::max(L.entryNeed, bi.entryNeed);
+    }
 }
 
 // ---- step 7: top-level needs and the scalars ---------------------------------------------------------------------------------
@@ -779,6 +819,7 @@ void Deriver::make_book()
         b.rootDesc0 = bi.rootDesc0; b.rootDesc1 = bi.rootDesc1;
         for (int k = 0; k < 3; ++k) { b.rootMin[k] = bi.rootMin[k]; b.rootMax[k] = bi.rootMax[k]; }
         b.owner = bi.owner;
+        b.entry = bi.entry; b.entryNeed = bi.entryNeed;
         B.blocks.push_back(b);
     }
 }
@@ -795,6 +836,7 @@ int derive_accel_layout(const void* blob, size_t size, const AccelOptions& opt, 
     d.unified_tree();
     d.write_owners();
     if (d.quad_records() || d.top_level_needs()) return -1;
+    d.entry_records();
     d.make_book();
     return 0;
 }
@@ -818,6 +860,7 @@ int update_accel_layout(const void* blob, size_t size, const AccelOptions& opt, 
         bi.rootDesc0 = b.rootDesc0; bi.rootDesc1 = b.rootDesc1;
         for (int k = 0; k < 3; ++k) { bi.rootMin[k] = b.rootMin[k]; bi.rootMax[k] = b.rootMax[k]; }
         bi.users = 0; bi.owner = 0xffffffffu;
+        bi.entry = b.entry; bi.entryNeed = b.entryNeed;
         d.blasAt.emplace((uint32_t)(regionStart + b.relOffset), bi);
     }
     d.maxLeafChunks = B.maxLeafChunks; d.maxLeafTris = B.maxLeafTris; d.hugeLeaf = B.hugeLeaf;
@@ -830,11 +873,13 @@ int update_accel_layout(const void* blob, size_t size, const AccelOptions& opt, 
     if (d.want_quad() != B.quadBuilt) return 1;
     if ((N.s.unifiedRoot != 0) != (inout.s.unifiedRoot != 0)) return 1;
     if (d.top_level_needs()) return -1;
+    d.entry_records();
 
     // what changed
     auto differs = [](const auto& a, const auto& b) { return a.size() != b.size() || (a.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) != 0); };
     what.tnodes = differs(N.tnodes, inout.tnodes); what.ctnodes = differs(N.ctnodes, inout.ctnodes); what.insts = differs(N.insts, inout.insts);
     what.groupBits = std::memcmp(N.groupBits, inout.groupBits, sizeof N.groupBits) != 0;
+    what.entries = differs(N.entries, inout.entries);
     size_t bi = 0;
     for (auto& kv : d.blasAt) {     // (the map's order is the blocks' order: both ascend by byte offset)
         const AccelBlasBlock& old = B.blocks[bi++];
@@ -847,6 +892,7 @@ int update_accel_layout(const void* blob, size_t size, const AccelOptions& opt, 
     d.make_book();
     inout.tnodes = std::move(N.tnodes); inout.ctnodes = std::move(N.ctnodes); inout.insts = std::move(N.insts);
     std::memcpy(inout.groupBits, N.groupBits, sizeof N.groupBits);
+    inout.entries = std::move(N.entries); inout.entryNeed = N.entryNeed; inout.groupFirst = N.groupFirst;
     inout.s = N.s;
     inout.book = std::move(N.book);
     return 0;

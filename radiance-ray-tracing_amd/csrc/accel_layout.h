@@ -29,6 +29,8 @@ struct AccelBlasBlock {
     uint32_t rootDesc0, rootDesc1;     // root of its wide records, as in DInst
     float rootMin[3], rootMax[3];
     uint32_t owner;                    // DTri._p0 of its triangles as the arrays stand: an instance slot, or 0xffffffff
+    DQuad entry;                       // entry record of its root and the pool need of a walk from there (AccelLayout::entries)
+    uint32_t entryNeed;
 };
 struct AccelBook {
     bool valid = false;                // false: the blob does not keep its BLASes behind the instance records (foreign blob)
@@ -47,6 +49,11 @@ struct AccelLayout {
     std::vector<DTri> tris;
     std::vector<DWide> wide;           // one record per inner BLAS node, then the unified tree's records
     std::vector<DQuad> quad;           // index = DWide index; empty unless the exhaustive pool walk will use them
+    std::vector<DQuad> entries;        // index = instance slot; empty unless `quad` is built.  Entry record of the instance's BLAS root R:
+                                       // first half = the half quad_records() makes for a skipped child R (R's two children under
+                                       // R's box, or R itself with its own box), second half empty; a leaf root has an inert record
+    uint32_t entryNeed = 0;            // pool need of a walk that starts at an entry record (same recurrence as the quad records')
+    uint32_t groupFirst = 0;           // lowest instance slot of the shared-transform group (0 without one)
     uint32_t groupBits[9] = {};        // instance slots of the shared-transform group (bitmap of 8 words; the 9th stays 0)
     rdx_accel_scalars s{};             // need numbers and engine flags (include/rdx.h)
     AccelBook book;
@@ -58,7 +65,7 @@ int derive_accel_layout(const void* blob, size_t size, const AccelOptions& opt, 
 // What update_accel_layout changed, for whoever keeps a copy of the arrays (the runtime: on a device).
 struct AccelOwnerRange { uint32_t first, count, owner; };      // DTri._p0 = owner for triangle slots [first, first + count)
 struct AccelUpdate {
-    bool tnodes = false, ctnodes = false, insts = false, groupBits = false;      // small arrays whose bytes changed
+    bool tnodes = false, ctnodes = false, insts = false, groupBits = false, entries = false;      // small arrays whose bytes changed
     std::vector<AccelOwnerRange> owners;
     uint32_t wideTailFirst = 0;        // the wide array is now [0, wideTailFirst) as before, then wideTail
     std::vector<DWide> wideTail;
@@ -68,7 +75,7 @@ struct AccelUpdate {
 // The layout of `blob` -- the blob `inout` was derived from with other transforms, SBT offsets or custom ids of its instances: same
 // instance count, byte-identical BLAS region -- from the top-level steps alone.  The per-BLAS blocks of bnodes / tris / wide / quad
 // stay where they are (a fresh derivation would order them by instance slot), so `inout` may come without those four arrays (the
-// runtime drops them after the upload); tnodes, ctnodes, insts, groupBits, the scalars and the book are replaced.  Triangle owner
+// runtime drops them after the upload); tnodes, ctnodes, insts, groupBits, entries, the scalars and the book are replaced.  Triangle owner
 // words and the tail of `wide` are only REPORTED in `what_changed`: apply_accel_update writes them into host arrays.
 // 0 = done; 1 = this change needs the full derivation (quad records or the unified tree would appear or vanish, the blob does not
 // match the book): `inout` is untouched; -1 = error, reason in `err`.

@@ -32,6 +32,9 @@ struct AccelView {                 // derived traversal layout (see rdx_types.h)
     uint32_t unifiedRoot;          // pool engine: > 0 = wide index of the super-root of the unified tree (accel_layout.cpp): rays start there
     uint32_t quadWaves;            // ... its kernels' waves per SIMD: 6, or 7 for full-size frames (kernels.hip k_*_pool_q)
     const DQuad* quad;             // pool engine, exhaustive walk: two tree levels per record (rdx_types.h); null = walk the DWide records
+    uint32_t entryBase;            // ... > 0 = the group's instances enter the pool as entry items: quad[entryBase + slot] is the entry
+                                   // record of instance `slot` (accel_layout.h AccelLayout::entries), 0 = one root per instance step
+    uint32_t groupFirst;           // ... and the lowest slot of the group (every member has the same inverse matrix)
 };
 
 // (the limits of the cooperative engines' packed words, RDX_COOP_MAX_*, are in rdx_types.h)

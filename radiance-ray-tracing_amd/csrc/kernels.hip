@@ -1100,23 +1100,23 @@ k_fused_pool(AccelView A, SceneArgs sc, PathStreams psShadow, PathStreams psExte
 #ifndef POOL_WPE_QUAD
 #define POOL_WPE_QUAD 6
 #endif
-template <bool INL, int W>
+template <bool INL, int W, bool ENT = false>
 __global__ void __launch_bounds__(RDX_BLOCK, W)
 k_extend_pool_q(AccelView A, PathStreams ps, const uint32_t* __restrict__ nPtr, uint32_t* __restrict__ counter, float tmin, float tmax)
 {
     ExtendPolicy pol{A, ps};
-    traverse_pool<1, INL, false, ExtendPolicy, true>(A, pol, *nPtr, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
+    traverse_pool<1, INL, false, ExtendPolicy, true, ENT>(A, pol, *nPtr, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
 }
-template <bool INL, int W>
+template <bool INL, int W, bool ENT = false>
 __global__ void __launch_bounds__(RDX_BLOCK, W)
 k_shadow_pool_q(AccelView A, SceneArgs sc, PathStreams ps, const uint32_t* __restrict__ nPtr, uint32_t* __restrict__ counter,
                 uint32_t lastBounce, uint32_t nPixels, uint32_t sampleBase, float tmin, float tmax)
 {
     const float* ld = sc.scene->lights[0].direction;
     ShadowPolicy pol{A, ps, normalize3(mk3(-ld[0], -ld[1], -ld[2])), lastBounce, nPixels, sampleBase};
-    traverse_pool<2, INL, false, ShadowPolicy, true>(A, pol, *nPtr, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
+    traverse_pool<2, INL, false, ShadowPolicy, true, ENT>(A, pol, *nPtr, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
 }
-template <bool INL, int W>
+template <bool INL, int W, bool ENT = false>
 __global__ void __launch_bounds__(RDX_BLOCK, W)
 k_fused_pool_q(AccelView A, SceneArgs sc, PathStreams psShadow, PathStreams psExtend, const uint32_t* __restrict__ mPtr,
                uint32_t* __restrict__ counter, uint32_t nPixels, uint32_t sampleBase, float tmin, float tmax)
@@ -1125,7 +1125,7 @@ k_fused_pool_q(AccelView A, SceneArgs sc, PathStreams psShadow, PathStreams psEx
     const uint32_t m = *mPtr;
     FusedPolicy pol{ShadowPolicy{A, psShadow, normalize3(mk3(-ld[0], -ld[1], -ld[2])), 0u, nPixels, sampleBase},
                     ExtendPolicy{A, psExtend}, m};
-    traverse_pool<3, INL, false, FusedPolicy, true>(A, pol, 2u * m, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
+    traverse_pool<3, INL, false, FusedPolicy, true, ENT>(A, pol, 2u * m, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1326,21 +1326,21 @@ k_trace_batch_pool2(AccelView A, const float* __restrict__ o, const float* __res
 }
 
 // (the same over quad records: the test seam walks what the frames walk)
-template <bool INL, int W>
+template <bool INL, int W, bool ENT = false>
 __global__ void __launch_bounds__(RDX_BLOCK, W)
 k_trace_batch_pool1_q(AccelView A, const float* __restrict__ o, const float* __restrict__ d, uint32_t n, uint32_t* __restrict__ counter,
                       float tmin, float tmax, rdx_hit* __restrict__ out)
 {
     BatchPolicy pol{A, o, d, out};
-    traverse_pool<1, INL, false, BatchPolicy, true>(A, pol, n, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
+    traverse_pool<1, INL, false, BatchPolicy, true, ENT>(A, pol, n, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
 }
-template <bool INL, int W>
+template <bool INL, int W, bool ENT = false>
 __global__ void __launch_bounds__(RDX_BLOCK, W)
 k_trace_batch_pool2_q(AccelView A, const float* __restrict__ o, const float* __restrict__ d, uint32_t n, uint32_t* __restrict__ counter,
                       float tmin, float tmax, rdx_hit* __restrict__ out)
 {
     BatchPolicy pol{A, o, d, out};
-    traverse_pool<2, INL, false, BatchPolicy, true>(A, pol, n, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
+    traverse_pool<2, INL, false, BatchPolicy, true, ENT>(A, pol, n, counter, tmin, tmax, s_stack + (threadIdx.x >> 6) * pool_words_per_wave(A.topNeed, A.blasNeed));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1400,19 +1400,19 @@ k_query_pool2(AccelView A, const float4* __restrict__ rays, uint32_t n, uint32_t
     traverse_pool<2, INL, CULL>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
 }
 // (the same over quad records, as the frames and the test seam walk them)
-template <bool INL, int W>
+template <bool INL, int W, bool ENT = false>
 __global__ void __launch_bounds__(RDX_BLOCK, W)
 k_query_pool1_q(AccelView A, const float4* __restrict__ rays, uint32_t n, uint32_t* __restrict__ counter, float4* __restrict__ hits)
 {
     QueryPolicy<false> pol{A, rays, hits};
-    traverse_pool<1, INL, false, QueryPolicy<false>, true>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
+    traverse_pool<1, INL, false, QueryPolicy<false>, true, ENT>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
 }
-template <bool INL, int W>
+template <bool INL, int W, bool ENT = false>
 __global__ void __launch_bounds__(RDX_BLOCK, W)
 k_query_pool2_q(AccelView A, const float4* __restrict__ rays, uint32_t n, uint32_t* __restrict__ counter, float4* __restrict__ hits)
 {
     QueryPolicy<true> pol{A, rays, hits};
-    traverse_pool<2, INL, false, QueryPolicy<true>, true>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
+    traverse_pool<2, INL, false, QueryPolicy<true>, true, ENT>(A, pol, n, counter, 0.0f, 0.0f, RDX_QUERY_LDS(A));
 }
 #undef RDX_QUERY_LDS
 
@@ -1599,7 +1599,12 @@ void launch_extend(hipStream_t st, const AccelView& av, const PathStreams& ps, c
             const uint32_t wq = (av.quadWaves == 7u && !av.leafRoots) ? 7u : (uint32_t)POOL_WPE_QUAD;                    \
             size_t ldsq; const uint32_t thq = coop_threads_words(pool_words_per_wave(av.topNeed, av.blasNeed), ldsq, wq);  \
             const dim3 gq(coop_blocks(N, thq, ldsq, wq));                                                                \
-            if (av.leafRoots) hipLaunchKernelGGL((K<true, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, __VA_ARGS__);           \
+            if (av.entryBase) {      /* the group's instances enter the pool as entry items (traverse_pool.h ENT) */        \
+                if (av.leafRoots) hipLaunchKernelGGL((K<true, POOL_WPE_QUAD, true>), gq, dim3(thq), ldsq, st, __VA_ARGS__);  \
+                else if (wq == 7u) hipLaunchKernelGGL((K<false, 7, true>), gq, dim3(thq), ldsq, st, __VA_ARGS__);            \
+                else hipLaunchKernelGGL((K<false, POOL_WPE_QUAD, true>), gq, dim3(thq), ldsq, st, __VA_ARGS__);              \
+            }                                                                                                             \
+            else if (av.leafRoots) hipLaunchKernelGGL((K<true, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, __VA_ARGS__);      \
             else if (wq == 7u) hipLaunchKernelGGL((K<false, 7>), gq, dim3(thq), ldsq, st, __VA_ARGS__);                     \
             else hipLaunchKernelGGL((K<false, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, __VA_ARGS__);                       \
         } while (0)
@@ -1783,7 +1788,9 @@ void launch_query_rays(hipStream_t st, const AccelView& av, const float4* rays, 
             // (the 6-wave build only: a seventh wave would need LDS the interval table takes)
             size_t ldsq; const uint32_t thq = coop_threads_words(words, ldsq, POOL_WPE_QUAD);
             const dim3 gq(coop_blocks(n, thq, ldsq, POOL_WPE_QUAD));
-#define RDX_QQ(K) do { if (av.leafRoots) hipLaunchKernelGGL((K<true, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, av, rays, n, counter, hits); \
+#define RDX_QQ(K) do { if (av.entryBase) { if (av.leafRoots) hipLaunchKernelGGL((K<true, POOL_WPE_QUAD, true>), gq, dim3(thq), ldsq, st, av, rays, n, counter, hits); \
+                                           else hipLaunchKernelGGL((K<false, POOL_WPE_QUAD, true>), gq, dim3(thq), ldsq, st, av, rays, n, counter, hits); } \
+                       else if (av.leafRoots) hipLaunchKernelGGL((K<true, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, av, rays, n, counter, hits); \
                        else hipLaunchKernelGGL((K<false, POOL_WPE_QUAD>), gq, dim3(thq), ldsq, st, av, rays, n, counter, hits); } while (0)
             if (rec == 2) RDX_QQ(k_query_pool2_q); else RDX_QQ(k_query_pool1_q);
 #undef RDX_QQ

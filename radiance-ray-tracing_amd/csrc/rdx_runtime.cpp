@@ -60,6 +60,8 @@ struct AccelCache {                // derived traversal layout of one TLAS buffe
     DNode* tnodes = nullptr; DNode* ctnodes = nullptr; DInst* insts = nullptr; DNode* bnodes = nullptr; DTri* tris = nullptr;
     DWide* wide = nullptr;
     DQuad* quad = nullptr;             // null: the quad records were not built
+    uint32_t nQuad = 0;                // quad records in `quad`; with `entriesUp` the entry records of the instance slots follow them
+    bool entriesUp = false;            // (AccelLayout::entries: a pool item addresses the one of slot i as nQuad + i)
     uint32_t* groupBits = nullptr;     // 9 words
     uint32_t* slotOf = nullptr;        // rdx_resolve_hits: slotOf[instanceIndex] = slot in `insts`, 0xffffffff = no such instance (nInst words)
     rdx_accel_scalars s{};             // coopOK: ... and the engines' LDS footprint fits (derive_accel)
@@ -163,6 +165,7 @@ struct Context {
         int sortRays = -1;                      // option "sort": per-bounce ray sort: 1 on, 0 off, -1 automatic
         int topFlat = 1;                        // pool engine: evaluate small top-level trees all at once (option "top_flat")
         int groupInstances = 1;                 // pool engine: instances with bit-identical inverse matrices share one ray slot (option "group_instances")
+        int groupEntryItems = 1;                // ... and enter the pool as entry items, all pending ones in one instance step (option "group_entry_items")
         int userStages = 1;                     // user programs that differ from the stock one only inside stage functions run on the wavefront pipeline (option "user_stages")
         int64_t sortMinPaths = 3ll << 19;       // chunks of more paths than this (1.5 M) sort the rays of mid-size scenes and use the 7-wave quad kernels (option
                                                 // "sort_min_paths"; 4.7 M / 3 M / 1.5 M: 1/2 frame 13.6 / 12.4 / 12.4 ms, 1/4 frame 7.57 / 7.57 / 7.35 ms, Sponza-class)
@@ -276,7 +279,13 @@ int derive_accel(rdx_buffer_s* tb)
     HIP_OK(up(ac->bnodes, L.bnodes.data(), L.bnodes.size()));
     HIP_OK(up(ac->tris, L.tris.data(), L.tris.size()));
     HIP_OK(up(ac->wide, L.wide.data(), L.wide.size()));
-    if (!L.quad.empty()) HIP_OK(up(ac->quad, L.quad.data(), L.quad.size()));
+    if (!L.quad.empty()) {
+        // the entry records sit behind the quad records, where a pool item's index reaches them -- unless that index would not fit
+        ac->nQuad = (uint32_t)L.quad.size();
+        ac->entriesUp = !L.entries.empty() && L.quad.size() + L.entries.size() < RDX_COOP_MAX_WIDE;
+        HIP_OK(up(ac->quad, L.quad.data(), L.quad.size(), L.quad.size() + (ac->entriesUp ? L.entries.size() : 0)));
+        if (ac->entriesUp) HIP_OK(hipMemcpy(ac->quad + ac->nQuad, L.entries.data(), L.entries.size() * sizeof(DQuad), hipMemcpyHostToDevice));
+    }
     HIP_OK(up(ac->groupBits, L.groupBits, 9));
     const std::vector<uint32_t> slots = slot_table(L.insts);
     HIP_OK(up(ac->slotOf, slots.data(), slots.size()));
@@ -326,14 +335,23 @@ AccelView view_of(const rdx_buffer_s* tb, bool smallChunk = false)
     // (not for the unified tree: its always-entered fan-outs gain nothing from a second level per item -- 39.4 vs 35.4 ms on the
     // 400-instance scene)
     v.quadWaves = 6u;
-    if (v.kernel == 3 && !v.cull && acc(tb)->quad && !v.unifiedRoot && (g.opt.quad > 0 || (g.opt.quad < 0 && smallChunk))) {
-        v.quad = acc(tb)->quad;
-        v.quadWaves = (!smallChunk && pool_lds_words(v.topNeed, std::max(acc(tb)->s.quadNeed, v.blasNeed)) <= 1462u) ? 7u : 6u;      // (7 waves: 160 KB / 28)
-        // (launches without a quad variant walk the wide records on the same view)
-        v.blasNeed = std::max(acc(tb)->s.quadNeed, v.blasNeed);
-    }
     v.groupCount = (v.topFlat && !v.unifiedRoot && g.opt.groupInstances) ? acc(tb)->s.groupCount : 0u;
     v.groupBits = acc(tb)->groupBits;
+    v.entryBase = 0u; v.groupFirst = 0u;
+    if (v.kernel == 3 && !v.cull && acc(tb)->quad && !v.unifiedRoot && (g.opt.quad > 0 || (g.opt.quad < 0 && smallChunk))) {
+        v.quad = acc(tb)->quad;
+        uint32_t need = std::max(acc(tb)->s.quadNeed, v.blasNeed);
+        // the group's instances enter the pool as entry items (option "group_entry_items"; traverse_pool.h): the pool is sized
+        // for a walk that starts at an entry record, too
+        if (g.opt.groupEntryItems && v.groupCount && acc(tb)->entriesUp) {
+            v.entryBase = acc(tb)->nQuad;
+            v.groupFirst = acc(tb)->host.groupFirst;
+            need = std::max(need, acc(tb)->host.entryNeed);
+        }
+        v.quadWaves = (!smallChunk && pool_lds_words(v.topNeed, need) <= 1462u) ? 7u : 6u;      // (7 waves: 160 KB / 28)
+        // (launches without a quad variant walk the wide records on the same view)
+        v.blasNeed = need;
+    }
     return v;
 }
 
@@ -1089,6 +1107,7 @@ int update_accel(rdx_buffer_s* tb, uint64_t oldVersion, rdx_tlas_update_stats& s
         HIP_OK(h2d(ac->slotOf, slots.data(), slots.size() * sizeof(uint32_t)));     // another top-level tree orders the slots anew
     }
     if (upd.groupBits) HIP_OK(h2d(ac->groupBits, L.groupBits, sizeof L.groupBits));
+    if (upd.entries && ac->entriesUp) HIP_OK(h2d(ac->quad + ac->nQuad, L.entries.data(), L.entries.size() * sizeof(DQuad)));   // (same count: one per slot)
     if (upd.wideTailChanged) HIP_OK(h2d(ac->wide + upd.wideTailFirst, upd.wideTail.data(), upd.wideTail.size() * sizeof(DWide)));
     std::vector<uint4> table;
     if (!upd.owners.empty()) {
@@ -1580,6 +1599,7 @@ extern "C" int rdx_set_option(const char* name, int64_t value)
     if (!strcmp(name, "cull")) { g.opt.cull = value < 0 ? -1 : (value != 0); return 0; }
     if (!strcmp(name, "top_flat")) { g.opt.topFlat = value != 0; return 0; }
     if (!strcmp(name, "group_instances")) { g.opt.groupInstances = value != 0; return 0; }
+    if (!strcmp(name, "group_entry_items")) { g.opt.groupEntryItems = value != 0; return 0; }
     if (!strcmp(name, "unified_tree")) { g.opt.unifiedTree = value != 0; return 0; }
     if (!strcmp(name, "gpu_build") || !strcmp(name, "gpu_build_min")) {
         if (!strcmp(name, "gpu_build")) g0.gpuBuild = value != 0; else g0.gpuBuildMin = value > 0 ? value : 32768;
@@ -2260,13 +2280,11 @@ extern "C" int rdx_debug_accel_layout(const void* blob, size_t size, int quad, i
 // blobs[0] derived afresh, then updated through blobs[1 ..] the way rdx_tlas_update updates a device's layout -- with the owner words
 // and the wide tail written into the host arrays.  A step the update hands back (return 1), or whose blob does not keep the
 // previous one's BLAS region, is derived in full.  path_per_step (optional, count - 1 entries): 1 incremental, 2 full.
-extern "C" int rdx_debug_accel_layout_update(const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull,
-                                             rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes, uint32_t* path_per_step)
+static int layout_chain(const char* who, const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull, AccelLayout& L,
+                        uint32_t* path_per_step)
 {
-    if (!blobs || !sizes || !count) return fail("rdx_debug_accel_layout_update: no blobs");
-    if (arrays && !bytes) return fail("rdx_debug_accel_layout_update: arrays need their capacities in bytes[]");
-    for (uint32_t i = 0; i < count; ++i) if (!blobs[i] || sizes[i] < 16) return fail("rdx_debug_accel_layout_update: blob %u is missing", i);
-    AccelLayout L;
+    if (!blobs || !sizes || !count) return fail("%s: no blobs", who);
+    for (uint32_t i = 0; i < count; ++i) if (!blobs[i] || sizes[i] < 16) return fail("%s: blob %u is missing", who, i);
     std::string err;
     const AccelOptions opt{quad, cull};
     if (derive_accel_layout(blobs[0], sizes[0], opt, L, err)) return fail_str(err);
@@ -2289,7 +2307,32 @@ extern "C" int rdx_debug_accel_layout_update(const void* const* blobs, const siz
         if (rc == 1 && derive_accel_layout(blobs[i], sizes[i], opt, L, err)) return fail_str(err);
         if (path_per_step) path_per_step[i - 1] = rc == 0 ? 1u : 2u;
     }
+    return 0;
+}
+
+extern "C" int rdx_debug_accel_layout_update(const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull,
+                                             rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes, uint32_t* path_per_step)
+{
+    if (arrays && !bytes) return fail("rdx_debug_accel_layout_update: arrays need their capacities in bytes[]");
+    AccelLayout L;
+    if (layout_chain("rdx_debug_accel_layout_update", blobs, sizes, count, quad, cull, L, path_per_step)) return -1;
     return export_layout(L, scalars, arrays, bytes);
+}
+
+extern "C" int rdx_debug_accel_entries(const void* const* blobs, const size_t* sizes, uint32_t count, int quad, int cull,
+                                       void* entries, size_t* bytes, uint32_t* need)
+{
+    if (!bytes) return fail("rdx_debug_accel_entries: the capacity of `entries` goes in *bytes");
+    AccelLayout L;
+    if (layout_chain("rdx_debug_accel_entries", blobs, sizes, count, quad, cull, L, nullptr)) return -1;
+    const size_t n = L.entries.size() * sizeof(DQuad);
+    if (entries) {
+        if (*bytes < n) return fail("rdx_debug_accel_entries: the entry records need %zu bytes", n);
+        if (n) std::memcpy(entries, L.entries.data(), n);
+    }
+    *bytes = n;
+    if (need) *need = L.entryNeed;
+    return 0;
 }
 
 static int export_layout(const AccelLayout& L, rdx_accel_scalars* scalars, void* const* arrays, size_t* bytes)

@@ -278,7 +278,9 @@ __device__ __forceinline__ bool pool_load_ray(const Policy& pol, uint32_t idx, f
 // A.blasNeed must be the any-order stack need (the host passes that one when the option is on).
 // QUAD: the exhaustive walk over quad records (rdx_types.h DQuad; never with CULL): separate kernels (kernels.hip k_*_pool_q), so
 // that neither walk carries the other's registers.
-template <int REC, bool INL, bool CULL, class Policy, bool QUAD = false>
+// ENT (QUAD only): the instances of the shared-transform group enter the pool as entry items ("instance entry" below; the host
+// launches it iff A.entryBase != 0) -- a separate instantiation like INL: the quad kernels sit at their register budget.
+template <int REC, bool INL, bool CULL, class Policy, bool QUAD = false, bool ENT = false>
 __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& pol, uint32_t n, uint32_t* __restrict__ counter,
                                               float tmin, float tmax, uint32_t* __restrict__ lds)
 {
@@ -337,6 +339,10 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
 #define POOL_GLEFT ((tsp >> 10) & 0x3ffu)
 #define POOL_SLOTGROUP (1u << 31)
     const bool grouping = flatTop && A.groupCount != 0u;
+    // Entry items (ENT; A.entryBase != 0, which the host sets only with a group): a lane enters ALL its pending group instances in
+    // one instance step, as pool items that point at the instances' entry records (accel_layout.h) -- the root test is then the
+    // pool step's, at its occupancy, and the instance step loads no instance record.
+    static_assert(!ENT || (QUAD && !CULL), "entry records are quad records");
     if (flatTop) for (uint32_t w = 0; w < A.topNeed; ++w) tstack[w * 64u] = 0u;
 #define POOL_INSTBITS (TAG_INST | IDX_MASK)            // top-level cursor in flat mode: "take the next instance from the bitmap"
 #define POOL_TPOP() do {                                                                               \
@@ -736,13 +742,70 @@ __device__ __forceinline__ void traverse_pool(const AccelView& A, const Policy& 
         if (chainInst || (nInst > 0 && nInst * POOL_W_INST >= nPool * 4 && PCAP - poolTop >= 64u + RESERVE)) {
             // a lane with instances of the shared-transform group pending enters one whatever it has in the pool or in the test queue
             // (same ray slot); any other instance waits for the queued tests of the instance left before (`markPrev`)
-            const bool grpNext = grouping && POOL_GLEFT != 0u;
-            const bool ready = isInst && (grpNext || (int32_t)(qHead - markPrev) >= 0);
+            const bool grpStep = grouping && POOL_GLEFT != 0u;
+            const bool ready = isInst && (grpStep || (int32_t)(qHead - markPrev) >= 0);
             if (__ballot(ready) == 0ull) { POOL_TEST(); continue; }
             COOP_STAT(5, __popcll(__ballot(ready)));
             if (REC != 1) { if (anyHit && ready && L.best[lane] != ~0ull) POOL_DROP(); }
             uint32_t cntE = 0, stE = 0, rootNode = COOP_NONE;
-            if (ready && tcur != COOP_NONE && tcur != POOL_INBLAS) {
+            if constexpr (ENT) {
+                // Every ready lane, of the group or not, may push up to `quota` items: room / ready lanes >= 1 (the step runs with
+                // room >= 64), so the pool keeps RESERVE free and a lane enters at least one instance whenever the step runs.
+                // (the lane count is rounded up to a power of two -- a shift instead of a division, which the hardware has not: in a
+                // step of 33 ready lanes up to half of the room stays unused, and lanes may keep instances pending for the next
+                // step that would have fitted)
+                const uint32_t quota = (PCAP - poolTop - RESERVE) >> (32u - (uint32_t)__clz((int)__popcll(__ballot(ready)) - 1));
+                const bool viaEntries = ready && grpStep && tcur != COOP_NONE && tcur != POOL_INBLAS;
+                uint32_t take = 0;
+                if (viaEntries) {
+                    if (!(tsp & POOL_SLOTGROUP)) {
+                        // the group's ray goes into the slot (a ray's first instance: no queued test reads the slot); the matrix is
+                        // the same for every member -- one wave-uniform address
+                        const float4* gp = reinterpret_cast<const float4*>(A.insts + A.groupFirst);
+                        float m[16];
+                        *reinterpret_cast<float4*>(m + 0) = gp[0];
+                        *reinterpret_cast<float4*>(m + 4) = gp[1];
+                        *reinterpret_cast<float4*>(m + 8) = gp[2];
+                        *reinterpret_cast<float4*>(m + 12) = gp[3];
+                        const f3 ro = mat4_mul3(m, o.x, o.y, o.z, 1.0f), rdv = mat4_mul3(m, d.x, d.y, d.z, 0.0f);
+                        const f3 rc = mk3(__builtin_amdgcn_rcpf(rdv.x), __builtin_amdgcn_rcpf(rdv.y), __builtin_amdgcn_rcpf(rdv.z));
+                        const float amin = fminf(fminf(fabsf(rdv.x), fabsf(rdv.y)), fabsf(rdv.z));
+                        const float amax = fmaxf(fmaxf(fabsf(rc.x), fabsf(rc.y)), fabsf(rc.z));
+                        const bool exactOnly = !(amin > 1e-20f) || !(amax < 1e20f);
+                        POOL_RA(rays, lane) = make_float4(ro.x, ro.y, ro.z, __uint_as_float(A.groupFirst));
+                        POOL_RB(rays, lane) = make_float4(rdv.x, rdv.y, rdv.z, __uint_as_float(((exactOnly ? 1u : 0u) | (anyHit ? 4u : 0u)) << 29));
+                        tsp |= POOL_SLOTGROUP;
+                    }
+                    take = min(POOL_GLEFT, quota);
+                }
+                // one prefix sum over the lanes' counts (pool_enqueue), bit by bit up to the largest count
+                uint32_t pre = 0, total = 0;
+                for (uint32_t b = 0; b < 10u; ++b) {
+                    if (__ballot((take >> b) != 0u) == 0ull) break;
+                    const unsigned long long m = __ballot((take >> b) & 1u);
+                    pre += lanes_below(m) << b;
+                    total += (uint32_t)__popcll(m) << b;
+                }
+                if (viaEntries) {
+                    uint32_t at = poolTop + pre, left = take;
+                    for (uint32_t w_ = 0; w_ < A.topNeed && left != 0u; ++w_) {
+                        uint32_t v_ = tstack[w_ * 64u], c_ = v_ & A.groupBits[w_];
+                        if (c_ == 0u) continue;
+                        while (c_ != 0u && left != 0u) {
+                            const uint32_t b_ = (uint32_t)__ffs((int)c_) - 1u;
+                            c_ &= c_ - 1u; v_ &= ~(1u << b_); --left;
+                            pool[at++] = (lane << POOL_LANE_SHIFT) | ((A.entryBase + w_ * 32u + b_) & POOL_NODE_MASK);
+                        }
+                        tstack[w_ * 64u] = v_;
+                    }
+                    pendN[lane] += take;
+                    tsp -= take * 0x401u;
+                    if (POOL_GLEFT == 0u) tcur = POOL_INBLAS;      // (take >= 1: the lane has items in the pool)
+                }
+                poolTop += total;
+            }
+            if (ready && tcur != COOP_NONE && tcur != POOL_INBLAS && !(ENT && grpStep)) {      // (ENT: the group's lanes are done)
+                const bool grpNext = ENT ? false : grpStep;
                 uint32_t ci = tcur & COOP_IFIRST_MASK;
                 if (flatTop) {       // the lowest pending instance of the bitmap (of the group first)
                     ci = 0;

@@ -595,6 +595,25 @@ def DebugAccelLayoutUpdate(blobs, quad=1, cull=-1):
     return scalars, arrays, [int(paths[i]) for i in range(n - 1)]
 
 
+def DebugAccelEntries(blobs, quad=1, cull=-1):
+    """Test seam (rdx_debug_accel_entries): the entry records of the layout of blobs[-1] -- one quad record per instance slot, which
+    the runtime uploads behind the quad records -- and the pool need of a walk that starts at one -> (structured array, need).
+    `blobs`: one blob, or a list that is derived and then updated like DebugAccelLayoutUpdate's."""
+    L = _lib.lib()
+    blobs = [bytes(blobs)] if isinstance(blobs, (bytes, bytearray, memoryview)) else [bytes(b) for b in blobs]
+    n = len(blobs)
+    ptrs = (C.c_char_p * n)(*blobs)
+    lens = (C.c_size_t * n)(*[len(b) for b in blobs])
+    size, need = C.c_size_t(0), C.c_uint32(0)
+    dt = dict(ACCEL_ARRAYS)["quad"]
+    if L.rdx_debug_accel_entries(ptrs, lens, n, int(quad), int(cull), None, C.byref(size), C.byref(need)) != 0:
+        raise RadianceError(L.rdx_last_error().decode("utf-8", "replace"))
+    out = np.zeros(size.value // dt.itemsize, dt)
+    if L.rdx_debug_accel_entries(ptrs, lens, n, int(quad), int(cull), out.ctypes.data if out.size else None, C.byref(size), C.byref(need)) != 0:
+        raise RadianceError(L.rdx_last_error().decode("utf-8", "replace"))
+    return out, int(need.value)
+
+
 def _layout_from(call):
     """(scalars, arrays) through a seam with the output convention of rdx_debug_accel_layout: a size query, then the arrays"""
     sc = _lib.rdx_accel_scalars()
