@@ -171,6 +171,24 @@ inline uint32_t ResolveHits(Platform*, TopAccelStruct accelStruct, Buffer rays, 
     return invalid;
 }
 
+// Extension (no reference counterpart; rdx_shade_hits): the stock closest-hit / miss shaders on the `n` records `hits` that
+// rdx_query_rays(..., RDX_QUERY_CLOSEST, ...) wrote for `rays`, with `keys` (rdx_shade_key) as the RNG inputs; device memory in and out.
+// `scene` = the buffers bound to descriptor slots 4, 5, 7, 8, 9, 10, 11, 12.  One rdx_shade per ray goes to `shade`; `next` / `shadow`
+// (each may be nullptr) receive the next ray and the shadow ray of every surviving ray, `src` (may be nullptr) switches compaction
+// on and receives the surviving rays' numbers.  Returns the number of surviving rays; *invalid (optional): records the bounds rule
+// refused.
+inline uint32_t ShadeHits(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer hits, Buffer keys, uint32_t n, const rdx_shading_buffers& scene,
+                          Buffer shade, Buffer next, Buffer shadow, Buffer src, uint32_t* invalid = nullptr, size_t raysOffset = 0,
+                          size_t hitsOffset = 0, size_t keysOffset = 0, size_t shadeOffset = 0, size_t nextOffset = 0, size_t shadowOffset = 0,
+                          size_t srcOffset = 0)
+{
+    uint32_t live = 0;
+    if (rdx_shade_hits(accelStruct, rays, raysOffset, hits, hitsOffset, keys, keysOffset, n, &scene, shade, shadeOffset, next, nextOffset, shadow,
+                       shadowOffset, src, srcOffset, &live, invalid))
+        detail::fatal("ShadeHits");
+    return live;
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

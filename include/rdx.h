@@ -292,7 +292,7 @@ int         rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset,
  * by instanceIndex, normal = getFaceNormal (samples/shader.cl:338-367), above / below = getHitPosition(hitData, +-normal)
  * (shader.cl:453-468: the stock shader's nextRayOrigin is one of the two), (u, v) = getUV (shader.cl:322-336).  Every other record
  * -- a miss, any other value of `hit` -- is 64 zero bytes.  Shading normals from normal maps and material parameters are not
- * resolved here.
+ * resolved here (rdx_shade_hits runs the stock closest-hit shader on the same records).
  * No record makes the kernel read outside a buffer: a hit is INVALID when instanceIndex is not below the TLAS's instance count and
  * the number of MeshInfo records, or one of its three index reads, nine normal reads or six uv reads falls outside its buffer
  * (MeshInfo offsets are int32 and may be negative; the positions are computed in 64 bits), or no instance of the TLAS carries that
@@ -321,6 +321,65 @@ int         rdx_resolve_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offse
 int         rdx_debug_surface_in_bounds(const rdx_mesh_info* mi, uint32_t ninst, uint32_t nmeshinfo, uint32_t instanceIndex,
                                         uint32_t primitiveIndex, const uint32_t idx3[3], uint64_t nindex, uint64_t nnormal,
                                         uint64_t nuv);
+
+/* The stock closest-hit shader on the hits of a ray query, on the device: what rdx_trace_rays does between two traversal stages,
+ * for the caller's own rays.  `rays` / `hits` are the buffers of an rdx_query_rays(..., RDX_QUERY_CLOSEST, ...) call (record i
+ * belongs to ray i; records the caller filled in are equally allowed), `keys` one rdx_shade_key per ray, `scene` the buffers
+ * bound to descriptor slots 4, 5, 7, 8, 9, 10, 11, 12.  One 48-byte rdx_shade per ray goes to `shade`.
+ * Record with hit == 1: the closest-hit row of the library's shader binding table runs, dispatched as the frame path dispatches
+ * it (row instanceSBTOffset + 1; samples/sbt.json: `material`, samples/shader.cl:482-541), on the HitData rdx_resolve_hits derives
+ * (hitPoint = inv (o, 1) + inv (d, 0) * t, barycentric = ((1 - b1) - b2, b1, b2), transform by instanceIndex), with rayDir = the
+ * ray's direction and (frameID, pixel, depth) of the key as the input of the next direction's random numbers.  The shader traces
+ * its shadow ray in the middle of the function; here both outcomes are handed back: `color` is payload.color if the shadow ray
+ * is NOT occluded, `colorOccluded` if it is, `nextFactor` is payload.nextFactor -- all with the bits the frame path computes.  The
+ * ray SURVIVES and gets a record number k: next[k] = (payload.nextRayOrigin | 0.001, payload.nextRayDirection | 1000), shadow[k]
+ * = (the shadow ray's origin | 0.001, normalize(-lights[0].direction) | 1000) -- both ready for rdx_query_rays with the reference's
+ * interval -- src[k] = i and shade[i].slot = k.  What the shader of the row does not write keeps the payload's state on entry,
+ * which is the frame path's: nextFactor 1, the next ray = the ray itself, no shadow query (a shadow record of zeros: tmax 0
+ * accepts nothing, so `color` is chosen) -- so `next` NULL, with which the next direction is not sampled (the last bounce),
+ * leaves nextFactor 1.  Any other record: the miss row 3 runs (`environment`: colour (0.2, 0.2, 0.5) in both colour fields), hit = 0, nextFactor
+ * = 0, slot = 0xffffffff; the ray does not survive.
+ * Without `src`, k = i and record i of a ray that does not survive is 32 zero bytes in `next` / `shadow` (tmax = 0: such a ray
+ * accepts nothing).  With `src`, the survivors are packed into records 0 .. live - 1: the survivors among input rays 64 j .. 64 j
+ * + 63 occupy consecutive records in input order; the order of these groups among each other is unspecified and may differ from
+ * call to call; records from `live` on are left untouched.  *live_out (optional) receives the survivor count either way.
+ * Textures follow the stock shader's rule: texels are read, through `sampler` (NULL: repeat, nearest), only when option
+ * "textures" is 1 and `textureArray` is given -- `uv` is required then; otherwise a material with a texture index sees texel 0.
+ * No record makes the kernel read outside a buffer: a hit is INVALID when rdx_resolve_hits would call it invalid (the uv stream
+ * counting only when texels are read), when 3 * primitiveIndex + 2 or 3 * vertex + 2 does not fit 32 bits, when its
+ * MeshInfo.materialIndex is not below the number of Material records, or -- texels read -- when one of the Material's four texture
+ * indices is neither -1 nor below the layer count.  An invalid hit writes 48 zero bytes except slot = 0xffffffff, does not
+ * survive and is counted in *invalid_out (optional); the call still returns 0.
+ * Nothing is staged and nothing is allocated per call; the call blocks, derives the traversal layout if none exists yet, sees
+ * the transforms of the last rdx_tlas_update, and runs on logical device 0 in multi-device mode.  rdx_get_trace_stats().ms_shade
+ * is the kernel time of the call.  Refused, before anything is launched: an uninitialised library; a NULL or unknown handle among
+ * tlas / rays / hits / keys / shade / scene / scene->scene, meshInfo, index, normal, material, an unknown one among the optional
+ * ones; a scene buffer smaller than a SceneProperties; an offset that is not a multiple of 16; a range that does not hold n
+ * records (32 n for rays / hits / next / shadow, 16 n for keys, 48 n for shade, 4 n for src: the worst case); an output range
+ * that overlaps an input range or another output range; wrapped memory that is misaligned.  n == 0 succeeds and touches nothing. */
+typedef struct rdx_shade_key { uint32_t frameID, pixel, depth, _0; } rdx_shade_key;   /* 16 B: the RNG input pcg3d(frameID, pixel, depth), shader.cl:205 */
+typedef struct rdx_shade {                      /* 48 B, three float4 */
+    float color[3];         uint32_t hit;           /* payload.color if the shadow ray is NOT occluded; 1 = closest-hit ran, 0 = miss shader ran */
+    float colorOccluded[3]; uint32_t materialIndex; /* payload.color if it is occluded */
+    float nextFactor[3];    uint32_t slot;          /* record number of this ray's next / shadow ray in `next` / `shadow`, 0xffffffff = none */
+} rdx_shade;
+typedef struct rdx_shading_buffers { rdx_buffer scene, meshInfo, index, uv, normal, material, textureArray; rdx_sampler sampler; } rdx_shading_buffers;
+    /* descriptor slots 4, 5, 7, 8, 9, 10, 11, 12; uv / textureArray / sampler may be NULL */
+int         rdx_shade_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset,
+                           rdx_buffer keys, size_t keys_offset, uint32_t n, const rdx_shading_buffers* scene,
+                           rdx_buffer shade, size_t shade_offset,
+                           rdx_buffer next, size_t next_offset,        /* optional: rdx_ray per surviving ray */
+                           rdx_buffer shadow, size_t shadow_offset,    /* optional: rdx_ray per surviving ray */
+                           rdx_buffer src, size_t src_offset,          /* optional uint32 per survivor: switches compaction on */
+                           uint32_t* live_out, uint32_t* invalid_out); /* both optional */
+/* Test seam: the bounds rule above for one record, on the host (needs no device and no initialised library) -> 1 = may be shaded,
+ * 0 = invalid.  Arguments up to nuv as rdx_debug_surface_in_bounds (nuv is ignored unless `textures`); materials = the Material
+ * records (nmaterials of them; read only if `textures` and the materialIndex is inside), textures = 1: texels are read, layers =
+ * layers of the image array. */
+int         rdx_debug_shade_in_bounds(const rdx_mesh_info* mi, uint32_t ninst, uint32_t nmeshinfo, uint32_t instanceIndex,
+                                      uint32_t primitiveIndex, const uint32_t idx3[3], uint64_t nindex, uint64_t nnormal,
+                                      uint64_t nuv, const rdx_material* materials, uint32_t nmaterials, int textures,
+                                      uint32_t layers);
 
 /* Test seams: run single stages on caller-supplied batches (device or host pointers are NOT
  * accepted -- plain host arrays in, host arrays out; the library stages them through HBM). */

@@ -75,6 +75,20 @@ class rdx_surface(C.Structure):
                 ("above", C.c_float * 3), ("u", C.c_float), ("below", C.c_float * 3), ("v", C.c_float)]
 
 
+class rdx_shade_key(C.Structure):
+    _fields_ = [("frameID", C.c_uint32), ("pixel", C.c_uint32), ("depth", C.c_uint32), ("_0", C.c_uint32)]
+
+
+class rdx_shade(C.Structure):
+    _fields_ = [("color", C.c_float * 3), ("hit", C.c_uint32), ("colorOccluded", C.c_float * 3), ("materialIndex", C.c_uint32),
+                ("nextFactor", C.c_float * 3), ("slot", C.c_uint32)]
+
+
+class rdx_shading_buffers(C.Structure):
+    _fields_ = [("scene", C.c_void_p), ("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p),
+                ("material", C.c_void_p), ("textureArray", C.c_void_p), ("sampler", C.c_void_p)]
+
+
 class rdx_payload(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("hit", C.c_uint32), ("nextFactor", C.c_float * 3),
                 ("nextRayOrigin", C.c_float * 3), ("nextRayDirection", C.c_float * 3)]
@@ -137,6 +151,11 @@ SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "rdx_debug_surface_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                               C.c_uint64, C.c_uint64, C.c_uint64]),
+    "rdx_shade_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                 C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
+                                            C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),
     "rdx_trace_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int,
                                   C.c_void_p, C.c_void_p]),
     "rdx_material_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -38,6 +38,7 @@
 #include "device_math.h"
 #include "kernels.h"
 #include "rdx_types.h"
+#include "shade.h"
 #include "user_shader.h"
 
 using namespace rdx;
@@ -149,6 +150,7 @@ struct Context {
     uint32_t* dStatus = nullptr;            // its device address
     unsigned long long* dVisit = nullptr;   // 8 words
     uint32_t* dSurfaceInvalid = nullptr;    // rdx_resolve_hits: records that failed the bounds rule, one word
+    uint32_t* dShadeCounts = nullptr;       // rdx_shade_hits: [0] = surviving rays (the compaction cursor), [1] = records that failed the bounds rule
     unsigned long long* hVisit = nullptr;   // pinned
     // everything rdx_set_option / rdx_set_profiling write, except the builder's knobs below: handed to the other devices'
     // contexts as a whole (rdx_trace_rays)
@@ -574,6 +576,7 @@ static int init_device_state(int device)
     HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dVisit), 64 * 8 * sizeof(unsigned long long)));     // [bounce][class*4 + kind]
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&g.hVisit), 64 * 8 * sizeof(unsigned long long), hipHostMallocDefault));
     HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dSurfaceInvalid), sizeof(uint32_t)));
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dShadeCounts), 2 * sizeof(uint32_t)));
     g.initialized = true;
     return 0;
 }
@@ -611,6 +614,8 @@ static void release_device_state()
     if (g.hVisit) HIP_IGN(hipHostFree(g.hVisit));
     if (g.dSurfaceInvalid) HIP_IGN(hipFree(g.dSurfaceInvalid));
     g.dSurfaceInvalid = nullptr;
+    if (g.dShadeCounts) HIP_IGN(hipFree(g.dShadeCounts));
+    g.dShadeCounts = nullptr;
     HIP_IGN(hipEventDestroy(g.evA)); HIP_IGN(hipEventDestroy(g.evB)); HIP_IGN(hipEventDestroy(g.evChunk));
     HIP_IGN(hipStreamDestroy(g.stream));
 }
@@ -2217,6 +2222,113 @@ extern "C" int rdx_debug_surface_in_bounds(const rdx_mesh_info* mi, uint32_t nin
 {
     if (!mi) return fail("rdx_debug_surface_in_bounds: no MeshInfo records");
     return surface_in_bounds(reinterpret_cast<const MeshInfo*>(mi), ninst, nmeshinfo, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv) ? 1 : 0;
+}
+
+// The stock closest-hit / miss shaders on a query's records (shade.hip): the checks and the steps around the launch are those of
+// rdx_resolve_hits
+extern "C" int rdx_shade_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, rdx_buffer keys,
+                              size_t keys_offset, uint32_t n, const rdx_shading_buffers* scene, rdx_buffer shade, size_t shade_offset,
+                              rdx_buffer next, size_t next_offset, rdx_buffer shadow, size_t shadow_offset, rdx_buffer src, size_t src_offset,
+                              uint32_t* live_out, uint32_t* invalid_out)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_shade_hits: invalid TLAS handle");
+    if (!rays || !known_buffer(rays)) return fail("rdx_shade_hits: invalid ray buffer handle");
+    if (!hits || !known_buffer(hits)) return fail("rdx_shade_hits: invalid hit buffer handle");
+    if (!keys || !known_buffer(keys)) return fail("rdx_shade_hits: invalid key buffer handle");
+    if (!shade || !known_buffer(shade)) return fail("rdx_shade_hits: invalid shade buffer handle");
+    if (next && !known_buffer(next)) return fail("rdx_shade_hits: invalid next-ray buffer handle");
+    if (shadow && !known_buffer(shadow)) return fail("rdx_shade_hits: invalid shadow-ray buffer handle");
+    if (src && !known_buffer(src)) return fail("rdx_shade_hits: invalid src buffer handle");
+    if (!scene) return fail("rdx_shade_hits: no scene buffers");
+    if (!scene->scene || !known_buffer(scene->scene)) return fail("rdx_shade_hits: invalid scene (SceneProperties) buffer handle");
+    if (!scene->meshInfo || !known_buffer(scene->meshInfo)) return fail("rdx_shade_hits: invalid meshInfo buffer handle");
+    if (!scene->index || !known_buffer(scene->index)) return fail("rdx_shade_hits: invalid index buffer handle");
+    if (!scene->normal || !known_buffer(scene->normal)) return fail("rdx_shade_hits: invalid normal buffer handle");
+    if (!scene->material || !known_buffer(scene->material)) return fail("rdx_shade_hits: invalid material buffer handle");
+    if (scene->uv && !known_buffer(scene->uv)) return fail("rdx_shade_hits: invalid uv buffer handle");
+    if (scene->textureArray && !known_buffer(scene->textureArray)) return fail("rdx_shade_hits: invalid textureArray handle");
+    uint32_t samplerBits = TEX_ADDR_REPEAT << TEX_ADDR_SHIFT;      // no sampler: repeat + nearest, as scene_args
+    if (scene->sampler && !sampler_bits(scene->sampler, samplerBits)) return fail("rdx_shade_hits: invalid sampler handle");
+    if (scene->scene->size < sizeof(SceneProperties))
+        return fail("rdx_shade_hits: the scene buffer (%zu bytes) does not hold a SceneProperties (%zu bytes)", scene->scene->size, sizeof(SceneProperties));
+    static_assert(sizeof(rdx_shade) == 48 && sizeof(rdx_shade_key) == 16 && sizeof(rdx_shading_buffers) == 8 * sizeof(void*), "three float4 per shade record, one uint4 per key");
+    // every range the kernel touches: {buffer, offset, bytes per record, name}; the first three are read, the others written
+    struct Range { rdx_buffer b; size_t off, rec; const char* name; };
+    const Range R[7] = {{rays, rays_offset, sizeof(rdx_ray), "ray"}, {hits, hits_offset, sizeof(rdx_ray_hit), "hit"}, {keys, keys_offset, sizeof(rdx_shade_key), "key"},
+                        {shade, shade_offset, sizeof(rdx_shade), "shade"}, {next, next_offset, sizeof(rdx_ray), "next-ray"},
+                        {shadow, shadow_offset, sizeof(rdx_ray), "shadow-ray"}, {src, src_offset, sizeof(uint32_t), "src"}};
+    for (const Range& r : R)
+        if (r.b && (r.off & 15u)) return fail("rdx_shade_hits: offsets must be multiples of 16 bytes (%s offset %zu)", r.name, r.off);
+    for (const Range& r : R)
+        if (r.b && (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off))
+            return fail("rdx_shade_hits: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
+    if (live_out) *live_out = 0;
+    if (invalid_out) *invalid_out = 0;
+    if (!n) return 0;
+    for (const Range& r : R)
+        if (r.b && (reinterpret_cast<uintptr_t>(r.b->dptr) & 15u)) return fail("rdx_shade_hits: wrapped device memory must be 16-byte aligned (%s buffer)", r.name);
+    if ((reinterpret_cast<uintptr_t>(scene->scene->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->meshInfo->dptr) & 3u) ||
+        (reinterpret_cast<uintptr_t>(scene->index->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->normal->dptr) & 3u) ||
+        (reinterpret_cast<uintptr_t>(scene->material->dptr) & 3u) || (scene->uv && (reinterpret_cast<uintptr_t>(scene->uv->dptr) & 3u)) ||
+        (scene->textureArray && (reinterpret_cast<uintptr_t>(scene->textureArray->dptr) & 3u)))
+        return fail("rdx_shade_hits: wrapped scene streams must be 4-byte aligned");
+    // no output range may overlap an input range or another output range, in one buffer or in several that wrap the same memory
+    for (int o = 3; o < 7; ++o)
+        for (int k = 0; k < o; ++k) {
+            if (!R[o].b || !R[k].b) continue;
+            const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[o].b->dptr) + R[o].off, a1 = a0 + (size_t)n * R[o].rec,
+                            b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
+            if (a0 < b1 && b0 < a1) return fail("rdx_shade_hits: the %s range and the %s range overlap", R[o].name, R[k].name);
+        }
+    ShadeScene sc{};
+    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
+    sc.s.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.s.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
+    sc.s.index = static_cast<const uint32_t*>(scene->index->dptr); sc.s.nIndex = scene->index->size / sizeof(uint32_t);
+    sc.s.normal = static_cast<const float*>(scene->normal->dptr); sc.s.nNormal = scene->normal->size / sizeof(float);
+    sc.materials = static_cast<const Material*>(scene->material->dptr); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
+    sc.tex = TexView{nullptr, 0, 0, 0, 0};
+    // the stock shader's rule (scene_args): texels are read only when option "textures" is 1 and an image array is given
+    if (g.opt.textures && scene->textureArray) {
+        const rdx_buffer_s* img = scene->textureArray;
+        if (!img->imgW || !img->imgH || !img->imgLayers) return fail("rdx_shade_hits: textureArray is not an image array (rdx_image_array_create)");
+        if (img->size / 4 / img->imgW / img->imgH < img->imgLayers) return fail("rdx_shade_hits: textureArray is smaller than its %u layers", img->imgLayers);
+        if (!scene->uv || scene->uv->size < sizeof(float)) return fail("rdx_shade_hits: option \"textures\" is 1 and a textureArray is given, but no uv buffer");
+        sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float);
+        sc.tex = TexView{static_cast<const uint8_t*>(img->dptr), img->imgW, img->imgH, img->imgLayers, TEX_ENABLED | samplerBits};
+    }
+    if (derive_accel(tlas)) return -1;
+    const AccelCache& ac = *acc(tlas);
+    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
+    HIP_OK(hipMemsetAsync(g.dShadeCounts, 0, 2 * sizeof(uint32_t), g.stream));
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_shade_hits(g.stream, ac.insts, ac.slotOf, ac.s.nInst, reinterpret_cast<const float4*>(at(rays, rays_offset)),
+                      reinterpret_cast<const float4*>(at(hits, hits_offset)), reinterpret_cast<const uint4*>(at(keys, keys_offset)), n, sc,
+                      reinterpret_cast<float4*>(at(shade, shade_offset)), reinterpret_cast<float4*>(at(next, next_offset)),
+                      reinterpret_cast<float4*>(at(shadow, shadow_offset)), reinterpret_cast<uint32_t*>(at(src, src_offset)), g.dShadeCounts,
+                      g.dShadeCounts + 1);
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    for (rdx_buffer b : {shade, next, shadow, src}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    uint32_t counts[2] = {0, 0};
+    HIP_OK(hipMemcpy(counts, g.dShadeCounts, sizeof counts, hipMemcpyDeviceToHost));
+    if (live_out) *live_out = counts[0];
+    if (invalid_out) *invalid_out = counts[1];
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
+    return 0;
+}
+
+extern "C" int rdx_debug_shade_in_bounds(const rdx_mesh_info* mi, uint32_t ninst, uint32_t nmeshinfo, uint32_t instanceIndex,
+                                         uint32_t primitiveIndex, const uint32_t idx3[3], uint64_t nindex, uint64_t nnormal, uint64_t nuv,
+                                         const rdx_material* materials, uint32_t nmaterials, int textures, uint32_t layers)
+{
+    if (!mi) return fail("rdx_debug_shade_in_bounds: no MeshInfo records");
+    if (!materials && nmaterials) return fail("rdx_debug_shade_in_bounds: no Material records");
+    static_assert(sizeof(Material) == sizeof(rdx_material), "Material layout");
+    return shade_in_bounds(reinterpret_cast<const MeshInfo*>(mi), ninst, nmeshinfo, instanceIndex, primitiveIndex, idx3, nindex, nnormal,
+                           textures ? nuv : 0u, reinterpret_cast<const Material*>(materials), nmaterials, textures != 0, layers) ? 1 : 0;
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,

@@ -552,6 +552,133 @@ def DebugSurfaceInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, n
     return rc == 1
 
 
+# ---- the stock closest-hit shader on a query's hits (rdx_shade_hits) --------------------------------------------------
+SHADE_KEY_DTYPE = np.dtype([("frameID", "<u4"), ("pixel", "<u4"), ("depth", "<u4"), ("_0", "<u4")])
+SHADE_DTYPE = np.dtype([("color", "<f4", 3), ("hit", "<u4"), ("colorOccluded", "<f4", 3), ("materialIndex", "<u4"),
+                        ("nextFactor", "<f4", 3), ("slot", "<u4")])
+assert SHADE_DTYPE.itemsize == C.sizeof(_lib.rdx_shade) == 48 and SHADE_KEY_DTYPE.itemsize == C.sizeof(_lib.rdx_shade_key) == 16
+assert C.sizeof(_lib.rdx_shading_buffers) == 8 * C.sizeof(C.c_void_p)
+NO_SLOT = 0xffffffff
+
+
+class ShadingBuffers:
+    """rdx_shading_buffers: the Buffers bound to descriptor slots 4, 5, 7, 8, 9, 10, the image array of slot 11 and the Sampler of
+    slot 12; uv, textureArray and sampler may be None"""
+    _REQUIRED = ("scene", "meshInfo", "index", "normal", "material")
+
+    def __init__(self, scene, meshInfo, index, uv, normal, material, textureArray=None, sampler=None):
+        self.scene, self.meshInfo, self.index, self.uv, self.normal, self.material = scene, meshInfo, index, uv, normal, material
+        self.textureArray, self.sampler = textureArray, sampler
+
+    def _struct(self):
+        for name in self._REQUIRED:
+            if not isinstance(getattr(self, name), Buffer):
+                raise RadianceError("ShadeHits: scene_buffers.%s must be a Buffer" % name)
+        for name in ("uv", "textureArray"):
+            if getattr(self, name) is not None and not isinstance(getattr(self, name), Buffer):
+                raise RadianceError("ShadeHits: scene_buffers.%s must be a Buffer or None" % name)
+        if self.sampler is not None and not isinstance(self.sampler, Sampler):
+            raise RadianceError("ShadeHits: scene_buffers.sampler must be a Sampler or None")
+        h = lambda x: x.handle if x is not None else None
+        return _lib.rdx_shading_buffers(self.scene.handle, self.meshInfo.handle, self.index.handle, h(self.uv), self.normal.handle,
+                                        self.material.handle, h(self.textureArray), h(self.sampler))
+
+
+def ShadeHits(tlas, rays, hits, keys, n, scene_buffers, shade=None, next=True, shadow=True, src=None, compact=False, rays_offset=0,
+              hits_offset=0, keys_offset=0, shade_offset=0, next_offset=0, shadow_offset=0, src_offset=0):
+    """Extension: the stock closest-hit / miss shaders on the `n` RAY_HIT_DTYPE records QueryRays(..., QUERY_CLOSEST) wrote to `hits`
+    for `rays`, with the SHADE_KEY_DTYPE records of `keys` as the RNG inputs (frameID, pixel, depth); device buffers in, device
+    buffers out.  scene_buffers: a ShadingBuffers or a tuple of its constructor's arguments.  One SHADE_DTYPE record per ray goes
+    to `shade`: `color` if the ray's shadow ray is not occluded, `colorOccluded` if it is, `nextFactor`, and `slot` = the record
+    number k of the ray's next ray in `next` and of its shadow ray in `shadow` (RAY_DTYPE records, ready for QueryRays), NO_SLOT
+    for a ray that does not survive.  shade: a Buffer, or None (created).  next / shadow: a Buffer, True (created: n records) or
+    None / False (not wanted; without `next` the next direction is not sampled).  src: a Buffer, or None -- then compact=True
+    creates it.  With `src`, the survivors are packed into records 0 .. live - 1 (those of 64 consecutive input rays contiguous and
+    in input order, the groups in no fixed order), src[k] = the ray's number, and records from `live` on are untouched; without,
+    k = i and the record of a ray that does not survive is zeros.  Returns (shade, next, shadow, src, live, invalid): `live`
+    survivors; `invalid` hits that would read outside a scene buffer, zeroed and counted."""
+    if not all(isinstance(b, Buffer) for b in (tlas, rays, hits, keys)):
+        raise RadianceError("ShadeHits: tlas, rays, hits and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    if not isinstance(scene_buffers, ShadingBuffers):
+        try:
+            scene_buffers = ShadingBuffers(*scene_buffers)
+        except TypeError:
+            raise RadianceError("ShadeHits: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
+                                "[, textureArray, sampler]) tuple")
+    sb = scene_buffers._struct()
+    n = int(n)
+
+    def out(buf, offset, rec, what, optional):
+        if buf is True or (buf is None and not optional):
+            return CreateBuffer(None, max(int(offset) + rec * n, 1))
+        if buf is None or buf is False:
+            return None
+        if not isinstance(buf, Buffer):
+            raise RadianceError("ShadeHits: %s must be a Buffer%s" % (what, ", True or None" if optional else " or None"))
+        return buf
+    shade = out(shade, shade_offset, SHADE_DTYPE.itemsize, "shade", False)
+    next = out(next, next_offset, RAY_DTYPE.itemsize, "next", True)
+    shadow = out(shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
+    src = out(True if (src is None and compact) else src, src_offset, 4, "src", True)
+    live, invalid = C.c_uint32(0), C.c_uint32(0)
+    h = lambda b: b.handle if b is not None else None
+    _check(_lib.lib().rdx_shade_hits(tlas.handle, rays.handle, int(rays_offset), hits.handle, int(hits_offset), keys.handle, int(keys_offset), n,
+                                     C.byref(sb), shade.handle, int(shade_offset), h(next), int(next_offset), h(shadow), int(shadow_offset),
+                                     h(src), int(src_offset), C.byref(live), C.byref(invalid)))
+    return shade, next, shadow, src, int(live.value), int(invalid.value)
+
+
+def ShadeHitsTorch(tlas, rays_t, hits_t, keys_t, scene_buffers, compact=True, sample_next=True):
+    """Extension: ShadeHits on CUDA tensors -- rays a contiguous float32 (n, 8) tensor, hits the contiguous int32 / float32 (n, 8)
+    tensor QueryRaysTorch returned for them, keys a contiguous int32 (n, 4) tensor (frameID, pixel, depth, 0).  Returns (shade,
+    next, shadow, src, live, invalid): shade float32 (n, 12) (`.view(torch.int32)` shows hit, materialIndex and slot in columns 3,
+    7, 11), next / shadow float32 (live, 8) when compacting -- already sliced to the survivors -- else (n, 8), src int32 (live,)
+    or None; next is None without sample_next.  The library cannot see torch's stream, so the current stream is synchronised
+    first; the call blocks."""
+    import torch
+    r, h, k = rays_t, hits_t, keys_t
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
+        raise RadianceError("ShadeHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(r.shape[0])
+    if not (isinstance(h, torch.Tensor) and h.is_cuda and h.dtype in (torch.int32, torch.float32) and tuple(h.shape) == (n, 8)
+            and h.is_contiguous() and h.device == r.device):
+        raise RadianceError("ShadeHitsTorch: hits must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
+    if not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
+            and k.device == r.device):
+        raise RadianceError("ShadeHitsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
+    shade = torch.empty((n, 12), dtype=torch.float32, device=r.device)
+    nxt = torch.empty((n, 8), dtype=torch.float32, device=r.device) if sample_next else None
+    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device)
+    src = torch.empty((n,), dtype=torch.int32, device=r.device) if compact else None
+    torch.cuda.current_stream(r.device).synchronize()
+    live = invalid = 0
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+        _, _, _, _, live, invalid = ShadeHits(tlas, wrap(r, 32), wrap(h, 32), wrap(k, 16), n, scene_buffers, wrap(shade, 48), wrap(nxt, 32),
+                                              wrap(shadow, 32), wrap(src, 4))
+    if compact:
+        nxt, shadow, src = (nxt[:live] if nxt is not None else None), shadow[:live], src[:live]
+    return shade, nxt, shadow, src, live, invalid
+
+
+def DebugShadeInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv, materials, textures=False, layers=0,
+                       nmeshinfo=None, nmaterials=None):
+    """Test seam (rdx_debug_shade_in_bounds): the bounds rule of ShadeHits for one record, on the host -> bool.  As
+    DebugSurfaceInBounds, plus `materials`: a Material array (nmaterials defaults to its length), textures: texels are read,
+    layers: layers of the image array."""
+    mi = np.ascontiguousarray(meshInfo, MeshInfo).reshape(-1)
+    mt = np.ascontiguousarray(materials, Material).reshape(-1)
+    nm = mi.shape[0] if nmeshinfo is None else int(nmeshinfo)
+    nmat = mt.shape[0] if nmaterials is None else int(nmaterials)
+    iv = None if idx3 is None else (C.c_uint32 * 3)(*[int(x) & 0xffffffff for x in idx3])
+    rc = _lib.lib().rdx_debug_shade_in_bounds(mi.ctypes.data_as(C.POINTER(_lib.rdx_mesh_info)), int(ninst), nm, int(instanceIndex) & 0xffffffff,
+                                              int(primitiveIndex) & 0xffffffff, iv, int(nindex), int(nnormal), int(nuv),
+                                              mt.ctypes.data_as(C.POINTER(_lib.rdx_material)), nmat, 1 if textures else 0, int(layers))
+    if rc < 0:
+        raise RadianceError(_lib.last_error())
+    return rc == 1
+
+
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
 _DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
 _DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),

@@ -318,6 +318,11 @@ class DeviceScene:
         """the four scene streams rd.ResolveHits reads (descriptor slots 5, 7, 8, 9)"""
         return rd.SurfaceBuffers(self.meshInfoData, self.indexData, self.uvData, self.normalData)
 
+    def shading_buffers(self, textureArray=None, sampler=None):
+        """the scene buffers rd.ShadeHits reads (descriptor slots 4, 5, 7, 8, 9, 10; this scene binds nothing to slots 11 / 12)"""
+        return rd.ShadingBuffers(self.rdSceneData, self.meshInfoData, self.indexData, self.uvData, self.normalData, self.materialData,
+                                 textureArray, sampler)
+
     def bind(self):
         rd.BindPipeline(self.plt, self.pipeline)
         rd.BindDescriptorSet(self.plt, self.descSet)

@@ -1,8 +1,8 @@
 #!/bin/bash
 # kernel_resources.sh [extra -D flags] -- register / scratch use of every kernel of kernels.hip as the compiler reports it
-# (no GPU needed): VGPRs, SGPRs, scratch bytes per lane, waves per SIMD
+# (no GPU needed): VGPRs, SGPRs, scratch bytes per lane, waves per SIMD.  RDX_KERNEL_SOURCE=shade.hip: another unit of csrc/
 cd "$(dirname "$0")/../radiance-ray-tracing_amd/csrc"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -x hip -c kernels.hip -o /dev/null \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -x hip -c "${RDX_KERNEL_SOURCE:-kernels.hip}" -o /dev/null \
   -Rpass-analysis=kernel-resource-usage "$@" 2>&1 | python3 -c '
 import re, sys, subprocess
 rows, cur = [], {}
