@@ -189,6 +189,32 @@ inline uint32_t ShadeHits(Platform*, TopAccelStruct accelStruct, Buffer rays, Bu
     return live;
 }
 
+// Extension (no reference counterpart; rdx_generate_rays): `n` camera rays of the PhysicalCamera in `camera` (the contents of
+// descriptor slot 3) as rdx_ray records in `rays`, and -- `keys` may be nullptr -- their rdx_shade_key records of depth 0; device
+// memory in and out.  Ray i is pixel firstPixel + i, or pixels[i]; its random input is pcg3d(frameID, totalSamples, pixel), or
+// pcg3d of seeds[i] (rdx_raygen_seed).  pixels / seeds may be nullptr.
+inline void GenerateRays(Platform*, Buffer camera, uint32_t n, uint32_t frameID, uint32_t totalSamples, Buffer rays, Buffer keys,
+                         uint32_t firstPixel = 0, Buffer pixels = nullptr, Buffer seeds = nullptr, float tmin = 0.001f, float tmax = 1000.0f,
+                         size_t pixelsOffset = 0, size_t seedsOffset = 0, size_t raysOffset = 0, size_t keysOffset = 0)
+{
+    if (rdx_generate_rays(camera, n, firstPixel, pixels, pixelsOffset, frameID, totalSamples, seeds, seedsOffset, tmin, tmax, rays, raysOffset,
+                          keys, keysOffset))
+        detail::fatal("GenerateRays");
+}
+
+// Extension (no reference counterpart; rdx_accumulate): sample `frameID` of `n` distinct pixels (firstPixel + i, or pixels[i]),
+// float4 colours in `colors`, folded into imageScratch by the reference's running mean; `image` (may be nullptr) receives the
+// tone-mapped RGBA8 of those pixels (debug: no ACES, no gamma).  Returns the samples whose pixel lies outside the frame.
+inline uint32_t Accumulate(Platform*, Buffer colors, uint32_t n, uint32_t frameID, Buffer imageScratch, Image image = nullptr,
+                           uint32_t firstPixel = 0, Buffer pixels = nullptr, bool debug = false, size_t colorsOffset = 0, size_t pixelsOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_accumulate(colors, colorsOffset, n, firstPixel, pixels, pixelsOffset, frameID, imageScratch, image, debug ? RDX_ACCUMULATE_DEBUG : 0u,
+                       &invalid))
+        detail::fatal("Accumulate");
+    return invalid;
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

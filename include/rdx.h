@@ -381,6 +381,54 @@ int         rdx_debug_shade_in_bounds(const rdx_mesh_info* mi, uint32_t ninst, u
                                       uint64_t nuv, const rdx_material* materials, uint32_t nmaterials, int textures,
                                       uint32_t layers);
 
+/* The two ends of a frame, on the device: the camera rays a loop over rdx_query_rays / rdx_shade_hits starts from, and the step
+ * that folds its finished samples into the frame rdx_trace_rays would have written.
+ * rdx_generate_rays: ray i is generateRay (samples/shader.cl:111-173) for pixel_i = pixels ? pixels[i] : first_pixel + i, with
+ * the random input pcg3d(seed_i) (math.cl:10-23), seed_i = seeds ? seeds[i].in : (frameID, totalSamples, pixel_i) -- the three
+ * inputs of shader.cl:205, where frameID = totalSamples + the sample's number in the batch.  Origin and direction carry the bits
+ * the frame path's own generate stage computes under the floating-point contract of DESIGN.md 2, thin lens (fStop != 0)
+ * included; tmin / tmax are written into every ray as passed (the reference's are 0.001f / 1000.0f): the records are ready for
+ * rdx_query_rays.  `keys` (optional) receives the rdx_shade_key {frameID, pixel_i, 0, 0} of every ray: the key of depth 0 for
+ * rdx_shade_hits.  `camera` holds a PhysicalCamera -- the contents of descriptor slot 3; it need not be bound -- and is read on
+ * the device by every call: cos / sin of its angles are evaluated there, per call, by the OCML functions the reference links, so
+ * a camera written between two calls is seen by the second.  A pixel number only enters arithmetic; none is refused.
+ * rdx_accumulate: sample i, colors[i] (float4: rgb, w ignored), belongs to pixel_i as above and is sample `frameID` of that
+ * pixel's running mean in `scratch` (imageScratch, slot 1: float4 per pixel): rgb = colour when frameID == 0, otherwise
+ * (float(frameID) * rgb + colour) / float(frameID + 1), the reference's expression (shader.cl:262-270) operation for operation;
+ * w stays as it is.  `image` (optional; slot 2: RGBA8) receives that pixel's (unsigned char)(int)(c * 255) | 255 of c =
+ * pow(ACES(mean), 0.7f) (shader.cl:272-304), or of c = mean with flags bit 0 (RTProp.debug).  One call is one frameID: the
+ * samples of a batch are a loop of calls, in sample order.  The frame has min(size(scratch) / 16, size(image) / 4) pixels; a
+ * pixel number not below that writes nothing and is counted in *invalid_out (optional), and the call still returns 0.  The
+ * pixels of one call must be distinct: for a pixel named twice the result is that of ONE of its samples, unspecified which
+ * (never an access outside the buffers).
+ * Both: device memory in and out (rdx_buffer_create, or rdx_buffer_wrap around e.g. a torch tensor), nothing staged through the
+ * host, nothing allocated per call; the call blocks, and runs on logical device 0 in multi-device mode.
+ * rdx_get_trace_stats().ms_generate / .ms_accumulate is the kernel time of the call (for rdx_generate_rays including the one
+ * thread that prepares the camera).  Refused, before anything is launched: an uninitialised library; a NULL or unknown camera /
+ * rays / colors / scratch handle, an unknown one among the optional ones; a camera buffer smaller than a PhysicalCamera; an
+ * offset that is not a multiple of 16 (4 for `pixels`); a range that does not hold n records (32 n rays, 16 n keys / seeds /
+ * colors, 4 n pixels); first_pixel + n beyond 2^32 when `pixels` is NULL; an output range (rays, keys; the whole of scratch and
+ * image) that overlaps an input range or the other output range; flags other than bit 0; wrapped memory that is misaligned.
+ * n == 0 succeeds and touches nothing. */
+typedef struct rdx_raygen_seed { uint32_t in[3]; uint32_t _0; } rdx_raygen_seed;   /* 16 B: the three inputs of pcg3d (shader.cl:205) */
+int         rdx_generate_rays(rdx_buffer camera,                       /* a PhysicalCamera (descriptor slot 3 contents); need not be bound */
+                              uint32_t n, uint32_t first_pixel,
+                              rdx_buffer pixels, size_t pixels_offset, /* optional uint32 per ray; NULL: ray i is pixel first_pixel + i */
+                              uint32_t frameID, uint32_t totalSamples,
+                              rdx_buffer seeds, size_t seeds_offset,   /* optional rdx_raygen_seed per ray; NULL: (frameID, totalSamples, pixel) */
+                              float tmin, float tmax,                  /* written into every ray; the reference's are 0.001f / 1000.0f */
+                              rdx_buffer rays, size_t rays_offset,     /* out: rdx_ray per ray */
+                              rdx_buffer keys, size_t keys_offset);    /* optional out: rdx_shade_key {frameID, pixel, 0, 0} per ray */
+#define RDX_ACCUMULATE_DEBUG 1u   /* flags bit 0: RTProp.debug (skip ACES and gamma) */
+int         rdx_accumulate(rdx_buffer colors, size_t colors_offset,   /* float4 per sample: rgb, w ignored */
+                           uint32_t n, uint32_t first_pixel,
+                           rdx_buffer pixels, size_t pixels_offset,   /* optional uint32 per sample; NULL: first_pixel + i */
+                           uint32_t frameID,
+                           rdx_buffer scratch,                        /* imageScratch: float4 per pixel (slot 1) */
+                           rdx_buffer image,                          /* optional RGBA8 (slot 2): NULL = no tone map */
+                           uint32_t flags,                            /* bit 0: RTProp.debug (skip ACES and gamma) */
+                           uint32_t* invalid_out);                    /* optional */
+
 /* Test seams: run single stages on caller-supplied batches (device or host pointers are NOT
  * accepted -- plain host arrays in, host arrays out; the library stages them through HBM). */
 typedef struct rdx_hit {

@@ -79,6 +79,10 @@ class rdx_shade_key(C.Structure):
     _fields_ = [("frameID", C.c_uint32), ("pixel", C.c_uint32), ("depth", C.c_uint32), ("_0", C.c_uint32)]
 
 
+class rdx_raygen_seed(C.Structure):
+    _fields_ = [("in_", C.c_uint32 * 3), ("_0", C.c_uint32)]      # `in` of include/rdx.h (a Python keyword)
+
+
 class rdx_shade(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("hit", C.c_uint32), ("colorOccluded", C.c_float * 3), ("materialIndex", C.c_uint32),
                 ("nextFactor", C.c_float * 3), ("slot", C.c_uint32)]
@@ -154,6 +158,10 @@ SIGNATURES = {
     "rdx_shade_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
                                  C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rdx_generate_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                    C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rdx_accumulate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,
+                                 C.c_uint32, C.POINTER(C.c_uint32)]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),
     "rdx_trace_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int,

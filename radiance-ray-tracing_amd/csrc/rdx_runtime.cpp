@@ -37,6 +37,7 @@
 #include "bvh_build.h"
 #include "device_math.h"
 #include "kernels.h"
+#include "raygen.h"
 #include "rdx_types.h"
 #include "shade.h"
 #include "user_shader.h"
@@ -151,6 +152,8 @@ struct Context {
     unsigned long long* dVisit = nullptr;   // 8 words
     uint32_t* dSurfaceInvalid = nullptr;    // rdx_resolve_hits: records that failed the bounds rule, one word
     uint32_t* dShadeCounts = nullptr;       // rdx_shade_hits: [0] = surviving rays (the compaction cursor), [1] = records that failed the bounds rule
+    CameraArgs* dRaygenArgs = nullptr;      // rdx_generate_rays: the camera's per-call constants, written by its first kernel
+    uint32_t* dAccumInvalid = nullptr;      // rdx_accumulate: samples whose pixel number is outside the frame, one word
     unsigned long long* hVisit = nullptr;   // pinned
     // everything rdx_set_option / rdx_set_profiling write, except the builder's knobs below: handed to the other devices'
     // contexts as a whole (rdx_trace_rays)
@@ -577,6 +580,8 @@ static int init_device_state(int device)
     HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&g.hVisit), 64 * 8 * sizeof(unsigned long long), hipHostMallocDefault));
     HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dSurfaceInvalid), sizeof(uint32_t)));
     HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dShadeCounts), 2 * sizeof(uint32_t)));
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dRaygenArgs), sizeof(CameraArgs)));
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.dAccumInvalid), sizeof(uint32_t)));
     g.initialized = true;
     return 0;
 }
@@ -616,6 +621,10 @@ static void release_device_state()
     g.dSurfaceInvalid = nullptr;
     if (g.dShadeCounts) HIP_IGN(hipFree(g.dShadeCounts));
     g.dShadeCounts = nullptr;
+    if (g.dRaygenArgs) HIP_IGN(hipFree(g.dRaygenArgs));
+    g.dRaygenArgs = nullptr;
+    if (g.dAccumInvalid) HIP_IGN(hipFree(g.dAccumInvalid));
+    g.dAccumInvalid = nullptr;
     HIP_IGN(hipEventDestroy(g.evA)); HIP_IGN(hipEventDestroy(g.evB)); HIP_IGN(hipEventDestroy(g.evChunk));
     HIP_IGN(hipStreamDestroy(g.stream));
 }
@@ -2329,6 +2338,111 @@ extern "C" int rdx_debug_shade_in_bounds(const rdx_mesh_info* mi, uint32_t ninst
     static_assert(sizeof(Material) == sizeof(rdx_material), "Material layout");
     return shade_in_bounds(reinterpret_cast<const MeshInfo*>(mi), ninst, nmeshinfo, instanceIndex, primitiveIndex, idx3, nindex, nnormal,
                            textures ? nuv : 0u, reinterpret_cast<const Material*>(materials), nmaterials, textures != 0, layers) ? 1 : 0;
+}
+
+// ---- the two ends of a frame on device memory (raygen.hip) ---------------------------------------------------------------------
+namespace {
+// a byte range a kernel touches: {buffer, offset, bytes, name, required alignment of offset and address}
+struct FrameRange { rdx_buffer b; size_t off, bytes; const char* name; uint32_t align; };
+bool ranges_overlap(const FrameRange& a, const FrameRange& b)
+{
+    if (!a.b || !b.b || !a.bytes || !b.bytes) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.b->dptr) + a.off, a1 = a0 + a.bytes,
+                    b0 = reinterpret_cast<uintptr_t>(b.b->dptr) + b.off, b1 = b0 + b.bytes;
+    return a0 < b1 && b0 < a1;
+}
+// offsets, sizes and -- n != 0 -- addresses of R[0 .. count); outputs are R[firstOut ..]: none may overlap a range before it
+int check_frame_ranges(const char* who, const FrameRange* R, int count, int firstOut, uint32_t n)
+{
+    for (int k = 0; k < count; ++k)
+        if (R[k].b && (R[k].off & (R[k].align - 1u))) return fail("%s: the %s offset must be a multiple of %u bytes (offset %zu)", who, R[k].name, R[k].align, R[k].off);
+    for (int k = 0; k < count; ++k)
+        if (R[k].b && (R[k].off > R[k].b->size || R[k].bytes > R[k].b->size - R[k].off))
+            return fail("%s: %u records at offset %zu run past the %s buffer (%zu bytes)", who, n, R[k].off, R[k].name, R[k].b->size);
+    if (!n) return 0;
+    for (int k = 0; k < count; ++k)
+        if (R[k].b && (reinterpret_cast<uintptr_t>(R[k].b->dptr) & (R[k].align - 1u)))
+            return fail("%s: wrapped device memory must be %u-byte aligned (%s buffer)", who, R[k].align, R[k].name);
+    for (int o = firstOut; o < count; ++o)
+        for (int k = 0; k < o; ++k)
+            if (ranges_overlap(R[o], R[k])) return fail("%s: the %s range and the %s range overlap", who, R[o].name, R[k].name);
+    return 0;
+}
+} // namespace
+
+// Primary rays of the camera in `camera`, as rdx_ray / rdx_shade_key records on the device (include/rdx.h)
+extern "C" int rdx_generate_rays(rdx_buffer camera, uint32_t n, uint32_t first_pixel, rdx_buffer pixels, size_t pixels_offset, uint32_t frameID,
+                                 uint32_t totalSamples, rdx_buffer seeds, size_t seeds_offset, float tmin, float tmax, rdx_buffer rays,
+                                 size_t rays_offset, rdx_buffer keys, size_t keys_offset)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!camera || !known_buffer(camera)) return fail("rdx_generate_rays: invalid camera buffer handle");
+    if (!rays || !known_buffer(rays)) return fail("rdx_generate_rays: invalid ray buffer handle");
+    if (pixels && !known_buffer(pixels)) return fail("rdx_generate_rays: invalid pixel buffer handle");
+    if (seeds && !known_buffer(seeds)) return fail("rdx_generate_rays: invalid seed buffer handle");
+    if (keys && !known_buffer(keys)) return fail("rdx_generate_rays: invalid key buffer handle");
+    if (camera->size < sizeof(PhysicalCamera))
+        return fail("rdx_generate_rays: the camera buffer (%zu bytes) does not hold a PhysicalCamera (%zu bytes)", camera->size, sizeof(PhysicalCamera));
+    static_assert(sizeof(rdx_raygen_seed) == 16 && sizeof(rdx_shade_key) == 16 && sizeof(rdx_ray) == 32, "one uint4 per seed and key, two float4 per ray");
+    if (!pixels && (uint64_t)first_pixel + n > 0x100000000ull)
+        return fail("rdx_generate_rays: first_pixel + n (%u + %u) does not fit 32 bits", first_pixel, n);
+    const FrameRange R[5] = {{camera, 0, sizeof(PhysicalCamera), "camera", 4}, {pixels, pixels_offset, (size_t)n * sizeof(uint32_t), "pixel", 4},
+                             {seeds, seeds_offset, (size_t)n * sizeof(rdx_raygen_seed), "seed", 16},
+                             {rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16}};
+    if (check_frame_ranges("rdx_generate_rays", R, 5, 3, n)) return -1;
+    if (!n) return 0;
+    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_generate_rays(g.stream, static_cast<const PhysicalCamera*>(camera->dptr), g.dRaygenArgs, n, first_pixel,
+                         reinterpret_cast<const uint32_t*>(at(pixels, pixels_offset)), frameID, totalSamples,
+                         reinterpret_cast<const uint4*>(at(seeds, seeds_offset)), tmin, tmax, reinterpret_cast<float4*>(at(rays, rays_offset)),
+                         reinterpret_cast<uint4*>(at(keys, keys_offset)));
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    for (rdx_buffer b : {rays, keys}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_generate, g.evA, g.evB));      // kernel time of this call (the camera's one-thread kernel included)
+    return 0;
+}
+
+// One sample per pixel folded into imageScratch, and the RGBA8 image of the new mean (include/rdx.h)
+extern "C" int rdx_accumulate(rdx_buffer colors, size_t colors_offset, uint32_t n, uint32_t first_pixel, rdx_buffer pixels, size_t pixels_offset,
+                              uint32_t frameID, rdx_buffer scratch, rdx_buffer image, uint32_t flags, uint32_t* invalid_out)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!colors || !known_buffer(colors)) return fail("rdx_accumulate: invalid colour buffer handle");
+    if (!scratch || !known_buffer(scratch)) return fail("rdx_accumulate: invalid scratch (imageScratch) buffer handle");
+    if (pixels && !known_buffer(pixels)) return fail("rdx_accumulate: invalid pixel buffer handle");
+    if (image && !known_buffer(image)) return fail("rdx_accumulate: invalid image buffer handle");
+    if (flags & ~1u) return fail("rdx_accumulate: unknown flags 0x%x (bit 0 = debug)", flags);
+    if (!pixels && (uint64_t)first_pixel + n > 0x100000000ull)
+        return fail("rdx_accumulate: first_pixel + n (%u + %u) does not fit 32 bits", first_pixel, n);
+    // the frame: whole pixels both buffers hold
+    size_t npix = scratch->size / sizeof(float4);
+    if (image) npix = std::min(npix, image->size / 4);
+    npix = std::min<size_t>(npix, 0xffffffffu);
+    const FrameRange R[4] = {{colors, colors_offset, (size_t)n * sizeof(float4), "colour", 16}, {pixels, pixels_offset, (size_t)n * sizeof(uint32_t), "pixel", 4},
+                             {scratch, 0, scratch->size, "scratch", 16}, {image, 0, image ? image->size : 0, "image", 4}};
+    if (check_frame_ranges("rdx_accumulate", R, 4, 2, n)) return -1;
+    if (invalid_out) *invalid_out = 0;
+    if (!n) return 0;
+    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
+    HIP_OK(hipMemsetAsync(g.dAccumInvalid, 0, sizeof(uint32_t), g.stream));
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_accumulate_samples(g.stream, reinterpret_cast<const float4*>(at(colors, colors_offset)), n, first_pixel,
+                              reinterpret_cast<const uint32_t*>(at(pixels, pixels_offset)), frameID, static_cast<float4*>(scratch->dptr),
+                              image ? static_cast<uchar4*>(image->dptr) : nullptr, (uint32_t)npix, flags & 1u, g.dAccumInvalid);
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    for (rdx_buffer b : {scratch, image}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    uint32_t invalid = 0;
+    HIP_OK(hipMemcpy(&invalid, g.dAccumInvalid, sizeof invalid, hipMemcpyDeviceToHost));
+    if (invalid_out) *invalid_out = invalid;
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_accumulate, g.evA, g.evB));      // kernel time of this call
+    return 0;
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,

@@ -679,6 +679,123 @@ def DebugShadeInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nin
     return rc == 1
 
 
+# ---- the two ends of a frame on device memory (rdx_generate_rays, rdx_accumulate) ---------------------------------------
+RAYGEN_SEED_DTYPE = np.dtype([("in", "<u4", 3), ("_0", "<u4")])
+assert RAYGEN_SEED_DTYPE.itemsize == C.sizeof(_lib.rdx_raygen_seed) == 16
+ACCUMULATE_DEBUG = 1
+
+
+def _optional_buffer(who, buf, what):
+    if buf is not None and not isinstance(buf, Buffer):
+        raise RadianceError("%s: %s must be a Buffer or None" % (who, what))
+    return buf.handle if buf is not None else None
+
+
+def GenerateRays(camera, n, frame_id, total_samples, first_pixel=0, pixels=None, seeds=None, tmin=0.001, tmax=1000.0, rays=None, keys=True,
+                 pixels_offset=0, seeds_offset=0, rays_offset=0, keys_offset=0):
+    """Extension: `n` camera rays of the PhysicalCamera in the device buffer `camera` (the contents of descriptor slot 3; it need
+    not be bound, and is read on the device by every call), as RAY_DTYPE records in `rays` -- ready for QueryRays -- and
+    SHADE_KEY_DTYPE records (frame_id, pixel, 0, 0) in `keys` -- the keys of depth 0 for ShadeHits.  Ray i belongs to pixel
+    first_pixel + i, or pixels[i] (`pixels`: a Buffer of uint32); its random input is pcg3d(frame_id, total_samples, pixel) as in
+    the reference's raygen, or pcg3d of seeds[i] (`seeds`: a Buffer of RAYGEN_SEED_DTYPE).  Every ray has the bits of the frame
+    path's generateRay; tmin / tmax are written as given.  rays: a Buffer, or None (created).  keys: a Buffer, True (created) or
+    None / False (not wanted).  Nothing passes through the host.  Returns (rays, keys)."""
+    if not isinstance(camera, Buffer):
+        raise RadianceError("GenerateRays: camera must be a Buffer (CreateBuffer / WrapDeviceMemory)")
+    n = int(n)
+    if rays is None:
+        rays = CreateBuffer(None, max(int(rays_offset) + RAY_DTYPE.itemsize * n, 1))
+    elif not isinstance(rays, Buffer):
+        raise RadianceError("GenerateRays: rays must be a Buffer or None")
+    if keys is True:
+        keys = CreateBuffer(None, max(int(keys_offset) + SHADE_KEY_DTYPE.itemsize * n, 1))
+    elif keys is False:
+        keys = None
+    hp, hs, hk = (_optional_buffer("GenerateRays", b, w) for b, w in ((pixels, "pixels"), (seeds, "seeds"), (keys, "keys")))
+    _check(_lib.lib().rdx_generate_rays(camera.handle, n, int(first_pixel), hp, int(pixels_offset), int(frame_id), int(total_samples), hs,
+                                        int(seeds_offset), float(tmin), float(tmax), rays.handle, int(rays_offset), hk, int(keys_offset)))
+    return rays, keys
+
+
+def GenerateRaysTorch(camera, n_or_pixels, frame_id, total_samples, seeds=None):
+    """Extension: GenerateRays into CUDA tensors.  n_or_pixels: an int n (pixels 0 .. n - 1), or a contiguous int32 CUDA tensor of
+    pixel numbers, shape (n,).  seeds: None, or a contiguous int32 CUDA tensor of shape (n, 4) (the three inputs of pcg3d, 0).
+    Returns (rays float32 (n, 8): origin, tmin = 0.001, direction, tmax = 1000 per row -- what QueryRaysTorch takes; keys int32
+    (n, 4): frame_id, pixel, 0, 0 -- what ShadeHitsTorch takes at depth 0).  The library cannot see torch's stream, so the
+    current stream is synchronised first; the call blocks."""
+    import torch
+    px = None
+    if isinstance(n_or_pixels, torch.Tensor):
+        px = n_or_pixels
+        if not (px.is_cuda and px.dtype == torch.int32 and px.dim() == 1 and px.is_contiguous()):
+            raise RadianceError("GenerateRaysTorch: pixels must be a contiguous int32 CUDA tensor of shape (n,)")
+        n, device = int(px.shape[0]), px.device
+    elif isinstance(n_or_pixels, (int, np.integer)) and not isinstance(n_or_pixels, bool) and n_or_pixels >= 0:
+        n, device = int(n_or_pixels), torch.device("cuda", torch.cuda.current_device())
+    else:
+        raise RadianceError("GenerateRaysTorch: the second argument is a ray count or an int32 CUDA tensor of pixel numbers")
+    if seeds is not None and not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and tuple(seeds.shape) == (n, 4)
+                                  and seeds.is_contiguous() and seeds.device == device):
+        raise RadianceError("GenerateRaysTorch: seeds must be a contiguous int32 CUDA tensor of shape (n, 4) on the pixels' device")
+    rays = torch.empty((n, 8), dtype=torch.float32, device=device)
+    keys = torch.empty((n, 4), dtype=torch.int32, device=device)
+    torch.cuda.current_stream(device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+        GenerateRays(camera, n, frame_id, total_samples, 0, wrap(px, 4), wrap(seeds, 16), rays=wrap(rays, 32), keys=wrap(keys, 16))
+    return rays, keys
+
+
+def Accumulate(colors, n, frame_id, scratch, image=None, first_pixel=0, pixels=None, debug=False, colors_offset=0, pixels_offset=0):
+    """Extension: the end of a frame's sample on the device.  colors: a Buffer of `n` float4 records (rgb, w ignored), sample
+    `frame_id` of pixels first_pixel + i, or pixels[i] (`pixels`: a Buffer of uint32).  scratch (imageScratch, float4 per pixel)
+    takes the reference's running mean -- rgb = colour for frame_id 0, else (frame_id * rgb + colour) / (frame_id + 1) in
+    float32, w kept -- and image (RGBA8, optional) the tone-mapped mean of those pixels (debug: no ACES, no gamma).  One call is
+    one frame_id; its pixels must be distinct (of two samples of one pixel one wins, unspecified which).  Returns `invalid`:
+    the samples whose pixel number is not below min(scratch.size / 16, image.size / 4); they write nothing."""
+    if not isinstance(colors, Buffer) or not isinstance(scratch, Buffer):
+        raise RadianceError("Accumulate: colors and scratch must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    hi, hp = _optional_buffer("Accumulate", image, "image"), _optional_buffer("Accumulate", pixels, "pixels")
+    invalid = C.c_uint32(0)
+    _check(_lib.lib().rdx_accumulate(colors.handle, int(colors_offset), int(n), int(first_pixel), hp, int(pixels_offset), int(frame_id),
+                                     scratch.handle, hi, ACCUMULATE_DEBUG if debug else 0, C.byref(invalid)))
+    return int(invalid.value)
+
+
+def AccumulateTorch(colors, frame_id, scratch, image=None, pixels=None, debug=False):
+    """Extension: Accumulate on CUDA tensors.  colors: contiguous float32 (n, 4); pixels: None (pixels 0 .. n - 1) or a contiguous
+    int32 (n,) tensor; scratch / image: Buffers (e.g. a DeviceScene's rdImageScratch / rdImage), or contiguous tensors of shape
+    (npix, 4), float32 / uint8, which are updated in place.  Returns `invalid`.  The library cannot see torch's stream, so the
+    current stream is synchronised first; the call blocks."""
+    import torch
+    c = colors
+    if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dtype == torch.float32 and c.dim() == 2 and c.shape[1] == 4 and c.is_contiguous()):
+        raise RadianceError("AccumulateTorch: colors must be a contiguous float32 CUDA tensor of shape (n, 4)")
+    n = int(c.shape[0])
+    if pixels is not None and not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int32 and tuple(pixels.shape) == (n,)
+                                   and pixels.is_contiguous() and pixels.device == c.device):
+        raise RadianceError("AccumulateTorch: pixels must be a contiguous int32 CUDA tensor of shape (n,) on the colours' device")
+
+    def frame(t, dtype, what):
+        if t is None or isinstance(t, Buffer):
+            return t
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 4 and t.is_contiguous()
+                and t.device == c.device):
+            raise RadianceError("AccumulateTorch: %s must be a Buffer or a contiguous %s CUDA tensor of shape (npix, 4) on the colours' device"
+                                % (what, str(dtype).replace("torch.", "")))
+        return WrapDeviceMemory(None, t.data_ptr(), t.numel() * t.element_size(), keepalive=t) if t.numel() else None
+    if scratch is None:
+        raise RadianceError("AccumulateTorch: scratch must be a Buffer or a float32 CUDA tensor of shape (npix, 4)")
+    bs, bi = frame(scratch, torch.float32, "scratch"), frame(image, torch.uint8, "image")
+    torch.cuda.current_stream(c.device).synchronize()
+    if not n:
+        return 0
+    if bs is None or (image is not None and bi is None):       # a frame of no pixels: every sample is outside it
+        return n
+    wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+    return Accumulate(wrap(c, 16), n, frame_id, bs, bi, 0, wrap(pixels, 4), debug)
+
+
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
 _DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
 _DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),

@@ -323,6 +323,10 @@ class DeviceScene:
         return rd.ShadingBuffers(self.rdSceneData, self.meshInfoData, self.indexData, self.uvData, self.normalData, self.materialData,
                                  textureArray, sampler)
 
+    def frame_buffers(self):
+        """(camera, imageScratch, image): the buffers of descriptor slots 3, 1, 2 -- what rd.GenerateRays reads and rd.Accumulate writes"""
+        return self.rdCamData, self.rdImageScratch, self.rdImage
+
     def bind(self):
         rd.BindPipeline(self.plt, self.pipeline)
         rd.BindDescriptorSet(self.plt, self.descSet)
