@@ -215,6 +215,19 @@ inline uint32_t Accumulate(Platform*, Buffer colors, uint32_t n, uint32_t frameI
     return invalid;
 }
 
+// Extension (no reference counterpart; rdx_trace_paths): radiance along `n` rays of the caller's own -- the reference's raygen
+// loop from ray i (rdx_ray, its own tmin / tmax for the first segment) with keys[i] (rdx_shade_key: frameID, pixel) to the depth
+// `maxDepth`, on the frame path's stages; one float4 (rgb, 0) per ray goes to `radiance`, the first segment's rdx_ray_hit records
+// to `hits` (may be nullptr); device memory in and out.  `scene` = the buffers bound to descriptor slots 4, 5, 7, 8, 9, 10, 11, 12;
+// they must describe the scene of `accelStruct` (rdx.h).
+inline void TracePaths(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer keys, uint32_t n, uint32_t maxDepth, const rdx_shading_buffers& scene,
+                       Buffer radiance, Buffer hits = nullptr, size_t raysOffset = 0, size_t keysOffset = 0, size_t radianceOffset = 0,
+                       size_t hitsOffset = 0)
+{
+    if (rdx_trace_paths(accelStruct, rays, raysOffset, keys, keysOffset, n, maxDepth, &scene, radiance, radianceOffset, hits, hitsOffset))
+        detail::fatal("TracePaths");
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

@@ -429,6 +429,50 @@ int         rdx_accumulate(rdx_buffer colors, size_t colors_offset,   /* float4 
                            uint32_t flags,                            /* bit 0: RTProp.debug (skip ACES and gamma) */
                            uint32_t* invalid_out);                    /* optional */
 
+/* Radiance along the caller's own rays, on the device: the whole raygen loop between rdx_generate_rays and rdx_accumulate in one
+ * call, on the frame path's own stages -- the fused shadow + extend launch, the per-bounce ray sort, ballot compaction -- for
+ * rays of any origin: another camera model, light probes, lightmap texels, irradiance caches.  Path i starts with ray i and key i
+ * (frameID and pixel; `depth` and `_0` are ignored): radiance[i].rgb is the value of `color` at the end of the reference's raygen
+ * `while` loop (samples/shader.cl:231-260) entered with payload.nextRayOrigin / nextRayDirection = ray i, sceneData.frameID =
+ * keys[i].frameID, get_global_id(0) = keys[i].pixel, depth 0 and RTProp.depth = max_depth; radiance[i].w is 0.  The rows of the
+ * library's shader binding table are dispatched as the frame path dispatches them, colour and contribution are folded operation
+ * for operation as the frame path's shade and shadow stages fold them (color += contribution * payload.color, contribution *=
+ * payload.nextFactor; a primary miss shows the miss colour, a later miss ends the path), so for the rays and keys of
+ * rdx_generate_rays the result is the sample rdx_accumulate expects -- generate -> trace_paths -> accumulate writes the frame
+ * rdx_trace_rays writes -- and it has the bits of the loop over rdx_query_rays / rdx_shade_hits shown in the README.  (One
+ * difference from that loop, in scenes with instance SBT offsets only: a shadow ray that meets an instance dispatches row
+ * instanceSBTOffset + 2 here as in the frame path and the reference, and a row without a hit shader does not occlude; the loop's
+ * RDX_QUERY_ANY reports `hit` alone.)  The first traceRay uses
+ * ray i's OWN interval under the rule of rdx_query_rays (a NaN bound accepts nothing); every later segment and every shadow query
+ * the reference's 0.001 / 1000.  Directions need not be unit length.  max_depth == 0 gives zeros.  `hits` (optional) receives the
+ * first segment's records: exactly what rdx_query_rays(tlas, rays, ..., RDX_QUERY_CLOSEST, hits, ...) writes.  User stage
+ * programs do not run here (as for rdx_shade_hits); only lights[0] is sampled, as by the stock shader.
+ * TRUST: `scene` (descriptor slots 4, 5, 7, 8, 9, 10, 11, 12 as for rdx_shade_hits, textures by the same rule: option "textures" 1
+ * and a textureArray, uv required then) must describe the scene of `tlas`.  Every hit comes from the library's own traversal of
+ * `tlas`, so the shade stage gathers UNCHECKED, exactly as in rdx_trace_rays -- unlike rdx_shade_hits, which shades records of
+ * any origin and fences every gather.  The one record format the caller can reach, the first segment's in `hits`, is still
+ * mapped to a miss when its instanceIndex is not below the TLAS's instance count or no instance carries it.
+ * Options "kernel", "cull", "quad", "sort", "fuse", "group_instances", "group_entry_items", "unified_tree", "top_flat" and
+ * "inline_leaf_roots" apply as in rdx_trace_rays (the first segment: as in rdx_query_rays); no result depends on them.
+ * "pipeline", "groups", "overlap" and "count_visits" do not apply: one group of paths, staged.  More than "chunk_paths" paths are
+ * traced in chunks of that many.  Nothing is staged through the host; the path streams (and, without `hits`, one chunk of
+ * records) grow on first use as rdx_trace_rays' do and are reused.  The call blocks, derives the traversal layout if none exists
+ * yet, sees the transforms of the last rdx_tlas_update, and runs on logical device 0 in multi-device mode.  rdx_get_trace_stats
+ * (pixels = n, ray counts, launches, ms_total; with rdx_set_profiling the ms_* of the stages: ms_extend includes the first
+ * segment, ms_generate is the kernel that turns rays into paths) and rdx_get_bounce_counts are filled as by rdx_trace_rays.
+ * Refused, before anything is launched: an uninitialised library; a NULL or unknown handle among tlas / rays / keys / radiance /
+ * scene / scene->scene, meshInfo, index, normal, material, an unknown one among the optional ones; a scene buffer smaller than a
+ * SceneProperties; max_depth > 62; an offset that is not a multiple of 16; a range that does not hold n records (32 n for rays /
+ * hits, 16 n for keys / radiance); an output range (radiance, hits) that overlaps an input range or the other output range;
+ * wrapped memory that is misaligned.  n == 0 succeeds and touches nothing; records from n on are never written. */
+int         rdx_trace_paths(rdx_buffer tlas,
+                            rdx_buffer rays, size_t rays_offset,          /* rdx_ray per path: the first segment, with ITS tmin / tmax */
+                            rdx_buffer keys, size_t keys_offset,          /* rdx_shade_key per path: frameID, pixel (depth, _0 ignored) */
+                            uint32_t n, uint32_t max_depth,               /* RTProp.depth; 0 .. 62 */
+                            const rdx_shading_buffers* scene,             /* slots 4, 5, 7, 8, 9, 10, 11, 12 as for rdx_shade_hits */
+                            rdx_buffer radiance, size_t radiance_offset,  /* out: float4 per path: rgb, w = 0 */
+                            rdx_buffer hits, size_t hits_offset);         /* optional out: rdx_ray_hit of the first segment */
+
 /* Test seams: run single stages on caller-supplied batches (device or host pointers are NOT
  * accepted -- plain host arrays in, host arrays out; the library stages them through HBM). */
 typedef struct rdx_hit {

@@ -37,6 +37,7 @@
 #include "bvh_build.h"
 #include "device_math.h"
 #include "kernels.h"
+#include "paths.h"
 #include "raygen.h"
 #include "rdx_types.h"
 #include "shade.h"
@@ -154,6 +155,8 @@ struct Context {
     uint32_t* dShadeCounts = nullptr;       // rdx_shade_hits: [0] = surviving rays (the compaction cursor), [1] = records that failed the bounds rule
     CameraArgs* dRaygenArgs = nullptr;      // rdx_generate_rays: the camera's per-call constants, written by its first kernel
     uint32_t* dAccumInvalid = nullptr;      // rdx_accumulate: samples whose pixel number is outside the frame, one word
+    float4* pathHits = nullptr;             // rdx_trace_paths without `hits`: the first segment's records of one chunk (2 float4 per path)
+    size_t pathHitsCap = 0;
     unsigned long long* hVisit = nullptr;   // pinned
     // everything rdx_set_option / rdx_set_profiling write, except the builder's knobs below: handed to the other devices'
     // contexts as a whole (rdx_trace_rays)
@@ -625,6 +628,8 @@ static void release_device_state()
     g.dRaygenArgs = nullptr;
     if (g.dAccumInvalid) HIP_IGN(hipFree(g.dAccumInvalid));
     g.dAccumInvalid = nullptr;
+    if (g.pathHits) HIP_IGN(hipFree(g.pathHits));
+    g.pathHits = nullptr; g.pathHitsCap = 0;
     HIP_IGN(hipEventDestroy(g.evA)); HIP_IGN(hipEventDestroy(g.evB)); HIP_IGN(hipEventDestroy(g.evChunk));
     HIP_IGN(hipStreamDestroy(g.stream));
 }
@@ -1646,6 +1651,117 @@ extern "C" int rdx_get_visit_profile(uint64_t* out, uint32_t max_bounces)
 
 extern "C" int rdx_get_trace_stats(rdx_trace_stats* out) { if (!out) return fail("null"); *out = g.stats; return 0; }
 
+// ---- the bounces of a chunk: what rdx_trace_rays and rdx_trace_paths share ----------------------------------------------------
+// The engine's view, the scene and the switches of one chunk.  nPixels / sampleBase place a finished path's colour in
+// PathStreams::sampleColor (kernels.hip store_sample: [(frameID - sampleBase) * nPixels + slot]); with 0 / 0 it is record `slot`.
+struct BounceArgs {
+    rdx_buffer_s* tlas; AccelView av; SceneArgs sc;
+    uint32_t maxDepth, nPixels, sampleBase;
+    bool fuse, overlap, sortOn; SortBox sortBox;
+    unsigned long long* visit;
+    float tmin, tmax;
+};
+
+// fuse / overlap / sortOn / sortBox of a chunk of `chunkPaths` paths from the options, B.av, B.visit and the scene of B.tlas
+static void bounce_switches(uint64_t chunkPaths, BounceArgs& B)
+{
+    const auto& S = acc(B.tlas)->s;
+    // Small chunks (multi-GPU shards, low resolutions): a traversal launch costs ~0.2 ms of ramp + tail
+    // whatever its size (tools/trav_scale.py), so shadow(d) and extend(d+1) -- same ray count, disjoint
+    // streams -- go into ONE cooperative launch: 9 traversal launches per depth-8 frame instead of 16.
+    B.fuse = g.opt.fuse != 0 && !B.visit && B.av.kernel >= 2;
+    B.overlap = g.opt.overlap == 1 && !B.fuse && !B.visit;
+    // per-bounce ray sort (north star; kernels.h): only the cooperative engines hand rays out by index
+    B.sortOn = !B.visit && B.av.kernel >= 2 &&
+               (g.opt.sortRays > 0 || (g.opt.sortRays < 0 && (S.nWide >= RDX_SORT_AUTO_MIN_WIDE ||
+                                                              (S.nWide >= RDX_SORT_AUTO_MIN_WIDE_FULL && chunkPaths > (uint64_t)g.opt.sortMinPaths))));
+    for (int k = 0; k < 3; ++k) {
+        const float lo = S.sceneLo[k], ext = S.sceneHi[k] - lo;
+        B.sortBox.lo[k] = lo; B.sortBox.inv[k] = ext > 0.0f ? 16.0f / ext : 0.0f;
+    }
+}
+
+// gps[k]: the streams of group k, its gPaths[k] paths generated and their first hits found (G.dCounts[0] = gPaths[k], device side).
+// Nothing is synchronised; on return gps[k] holds the streams as the last bounce left them.
+static int trace_bounces(const BounceArgs& B, PathStreams* gps, const uint32_t* gPaths, int nGroups)
+{
+    // Per bounce and group:  shade(d) -> { shadow(d), extend(d+1) } -> shade(d+1) ...
+    // shadow(d) only fills nCol (or the final sample colour) and reads streams nobody writes meanwhile;
+    // extend(d+1) reads the next-bounce rays shade(d) wrote.  The two are traced by one fused launch,
+    // by two launches back to back, or (overlap) on two streams.
+    for (uint32_t d = 0; d < B.maxDepth; ++d) {
+        for (int k = 0; k < nGroups; ++k) {
+            Context::Group& G = g.groups[k];
+            PathStreams& ps = gps[k];
+            const uint32_t n0 = gPaths[k];
+            const bool last = d + 1 == B.maxDepth;
+            if (B.overlap && d > 0) HIP_OK(hipStreamWaitEvent(G.s0, G.evShadow[d - 1], 0));   // shade(d) reads col written by shadow(d-1)
+            g_timer.begin(&g.stats.ms_shade, G.s0);
+            if (B.sortOn && G.permCap < n0) {
+                if (G.permE) HIP_IGN(hipFree(G.permE));
+                if (G.sortKey) HIP_IGN(hipFree(G.sortKey));
+                G.permE = nullptr; G.sortKey = nullptr; G.permCap = 0;
+                HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.permE), (size_t)n0 * 4));
+                HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.sortKey), (size_t)n0 * 2));
+                G.permCap = n0;
+            }
+            ps.sortKey = B.sortOn ? G.sortKey : nullptr;        // (the shade stage writes the survivors' sort keys)
+            launch_shade(G.s0, B.av, B.sc, ps, G.dCounts + d, G.dCounts + d + 1, n0, d, B.maxDepth, B.nPixels, B.sampleBase, B.sortOn ? &B.sortBox : nullptr);
+            g_timer.end(G.s0);
+            ps.permS = nullptr; ps.permE = nullptr;
+            if (B.sortOn) {
+                // per-bounce ray sort: the traversal launch below hands its rays out in (octant, Morton cell) order
+                if (!G.sortBins) HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.sortBins), (size_t)ray_sort_tiles_words() * 4));
+                g_timer.begin(&g.stats.ms_sort, G.s0);
+                launch_ray_sort_tiles(G.s0, ps, G.dCounts + d + 1, n0, B.sortBox, G.sortBins, G.permE, acc(B.tlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE);
+                g_timer.end(G.s0);
+                ps.permS = G.permE; ps.permE = G.permE;
+            }
+            const PathStreams psShadow = ps;
+            // the compacted survivors become the live paths of the next bounce
+            std::swap(ps.rayO, ps.nRayO); std::swap(ps.rayD, ps.nRayD); std::swap(ps.thr, ps.nThr); std::swap(ps.col, ps.nCol);
+            if (B.fuse && !last) {
+                g_timer.begin(&g.stats.ms_fused, G.s0);
+                launch_fused(G.s0, B.av, B.sc, psShadow, ps, G.dCounts + d + 1, n0, B.nPixels, B.sampleBase, B.tmin, B.tmax, G.dCounts + 128 + d);
+                g_timer.end(G.s0);
+                g.stats.launches_shadow++; g.stats.launches_extend++;
+                continue;
+            }
+            hipStream_t ss = G.s0;
+            if (B.overlap) {
+                HIP_OK(hipEventRecord(G.evShade[d], G.s0));
+                HIP_OK(hipStreamWaitEvent(G.s1, G.evShade[d], 0));
+                ss = G.s1;
+            }
+            g_timer.begin(&g.stats.ms_shadow, ss);
+            launch_shadow(ss, B.av, B.sc, psShadow, G.dCounts + d + 1, n0, last, B.nPixels, B.sampleBase, B.tmin, B.tmax, B.visit ? B.visit + 8 * d : nullptr,
+                          G.dCounts + 128 + d);
+            g_timer.end(ss);
+            if (B.overlap) HIP_OK(hipEventRecord(G.evShadow[d], G.s1));
+            g.stats.launches_shadow++;
+            if (!last) {
+                g_timer.begin(&g.stats.ms_extend, G.s0);
+                launch_extend(G.s0, B.av, ps, G.dCounts + d + 1, n0, B.tmin, B.tmax, B.visit ? B.visit + 8 * (d + 1) : nullptr, G.dCounts + 64 + d + 1);
+                g_timer.end(G.s0);
+                g.stats.launches_extend++;
+            }
+        }
+    }
+    return 0;
+}
+
+// the groups' live counts of a finished chunk (hCounts, read back) into the ray counts of the call
+static void add_group_counts(int nGroups, uint32_t maxDepth)
+{
+    for (int k = 0; k < nGroups; ++k) {
+        const uint32_t* hc = g.groups[k].hCounts;
+        for (uint32_t d = 0; d <= maxDepth && maxDepth; ++d) g.bounceCounts[d] += hc[d];
+        if (maxDepth) g.stats.rays_primary += hc[0];
+        for (uint32_t d = 1; d < maxDepth; ++d) g.stats.rays_bounce += hc[d];
+        for (uint32_t d = 0; d < maxDepth; ++d) { g.stats.rays_shadow += hc[d + 1]; g.stats.closest_hits += hc[d + 1]; }
+    }
+}
+
 // one frame on the calling thread's device (context `g`, logical device tl_dev): every pixel of its shard
 static int trace_rays_device(uint32_t width, uint32_t height)
 {
@@ -1743,20 +1859,8 @@ static int trace_rays_device(uint32_t width, uint32_t height)
         int nGroups = (int)std::min<uint32_t>(wantGroups, sc_n);
         set_grid_share((uint32_t)nGroups);
         g.stats.groups = (uint32_t)nGroups;
-        // Small chunks (multi-GPU shards, low resolutions): a traversal launch costs ~0.2 ms of ramp + tail
-        // whatever its size (tools/trav_scale.py), so shadow(d) and extend(d+1) -- same ray count, disjoint
-        // streams -- go into ONE cooperative launch: 9 traversal launches per depth-8 frame instead of 16.
-        const bool fuse = g.opt.fuse != 0 && !visit && av.kernel >= 2;
-        const bool overlap = g.opt.overlap == 1 && !fuse && !visit;
-        // per-bounce ray sort (north star; kernels.h): only the cooperative engines hand rays out by index
-        const bool sortOn = !visit && av.kernel >= 2 &&
-                            (g.opt.sortRays > 0 || (g.opt.sortRays < 0 && (acc(bTlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE ||
-                                                                    (acc(bTlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE_FULL && chunkPaths > (uint64_t)g.opt.sortMinPaths))));
-        SortBox sortBox;
-        for (int k = 0; k < 3; ++k) {
-            const float lo = acc(bTlas)->s.sceneLo[k], ext = acc(bTlas)->s.sceneHi[k] - lo;
-            sortBox.lo[k] = lo; sortBox.inv[k] = ext > 0.0f ? 16.0f / ext : 0.0f;
-        }
+        BounceArgs B{bTlas, av, sc, maxDepth, P, sampleBase, false, false, false, SortBox{}, visit, tmin, tmax};
+        bounce_switches(chunkPaths, B);
         HIP_OK(hipEventRecord(g.evChunk, g.stream));          // everything before this chunk (previous accumulate) is done first
 
         if (g.pipeline->program && g.pipeline->program->stages) {
@@ -1849,9 +1953,11 @@ static int trace_rays_device(uint32_t width, uint32_t height)
         uint32_t gBegin[Context::MAX_GROUPS + 1];
         for (int k = 0; k <= nGroups; ++k) gBegin[k] = (uint32_t)((uint64_t)sc_n * k / nGroups);
         PathStreams gps[Context::MAX_GROUPS];
+        uint32_t gPaths[Context::MAX_GROUPS];
         for (int k = 0; k < nGroups; ++k) {
             Context::Group& G = g.groups[k];
             const uint32_t ns = gBegin[k + 1] - gBegin[k], n0 = ns * P;
+            gPaths[k] = n0;
             if (ensure_group(G, n0)) return -1;
             G.ps.sampleColor = g.sampleColor;
             gps[k] = G.ps;
@@ -1870,71 +1976,10 @@ static int trace_rays_device(uint32_t width, uint32_t height)
                 g.stats.launches_extend++;
             }
         }
-        // Per bounce and group:  shade(d) -> { shadow(d), extend(d+1) } -> shade(d+1) ...
-        // shadow(d) only fills nCol (or the final sample colour) and reads streams nobody writes meanwhile;
-        // extend(d+1) reads the next-bounce rays shade(d) wrote.  The two are traced by one fused launch,
-        // by two launches back to back, or (overlap) on two streams.
-        for (uint32_t d = 0; d < maxDepth; ++d) {
-            for (int k = 0; k < nGroups; ++k) {
-                Context::Group& G = g.groups[k];
-                PathStreams& ps = gps[k];
-                const uint32_t n0 = (gBegin[k + 1] - gBegin[k]) * P;
-                const bool last = d + 1 == maxDepth;
-                if (overlap && d > 0) HIP_OK(hipStreamWaitEvent(G.s0, G.evShadow[d - 1], 0));   // shade(d) reads col written by shadow(d-1)
-                g_timer.begin(&g.stats.ms_shade, G.s0);
-                if (sortOn && G.permCap < n0) {
-                    if (G.permE) HIP_IGN(hipFree(G.permE));
-                    if (G.sortKey) HIP_IGN(hipFree(G.sortKey));
-                    G.permE = nullptr; G.sortKey = nullptr; G.permCap = 0;
-                    HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.permE), (size_t)n0 * 4));
-                    HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.sortKey), (size_t)n0 * 2));
-                    G.permCap = n0;
-                }
-                ps.sortKey = sortOn ? G.sortKey : nullptr;        // (the shade stage writes the survivors' sort keys)
-                launch_shade(G.s0, av, sc, ps, G.dCounts + d, G.dCounts + d + 1, n0, d, maxDepth, P, sampleBase, sortOn ? &sortBox : nullptr);
-                g_timer.end(G.s0);
-                ps.permS = nullptr; ps.permE = nullptr;
-                if (sortOn) {
-                    // per-bounce ray sort: the traversal launch below hands its rays out in (octant, Morton cell) order
-                    if (!G.sortBins) HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.sortBins), (size_t)ray_sort_tiles_words() * 4));
-                    g_timer.begin(&g.stats.ms_sort, G.s0);
-                    launch_ray_sort_tiles(G.s0, ps, G.dCounts + d + 1, n0, sortBox, G.sortBins, G.permE, acc(bTlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE);
-                    g_timer.end(G.s0);
-                    ps.permS = G.permE; ps.permE = G.permE;
-                }
-                const PathStreams psShadow = ps;
-                // the compacted survivors become the live paths of the next bounce
-                std::swap(ps.rayO, ps.nRayO); std::swap(ps.rayD, ps.nRayD); std::swap(ps.thr, ps.nThr); std::swap(ps.col, ps.nCol);
-                if (fuse && !last) {
-                    g_timer.begin(&g.stats.ms_fused, G.s0);
-                    launch_fused(G.s0, av, sc, psShadow, ps, G.dCounts + d + 1, n0, P, sampleBase, tmin, tmax, G.dCounts + 128 + d);
-                    g_timer.end(G.s0);
-                    g.stats.launches_shadow++; g.stats.launches_extend++;
-                    continue;
-                }
-                hipStream_t ss = G.s0;
-                if (overlap) {
-                    HIP_OK(hipEventRecord(G.evShade[d], G.s0));
-                    HIP_OK(hipStreamWaitEvent(G.s1, G.evShade[d], 0));
-                    ss = G.s1;
-                }
-                g_timer.begin(&g.stats.ms_shadow, ss);
-                launch_shadow(ss, av, sc, psShadow, G.dCounts + d + 1, n0, last, P, sampleBase, tmin, tmax, visit ? visit + 8 * d : nullptr,
-                              G.dCounts + 128 + d);
-                g_timer.end(ss);
-                if (overlap) HIP_OK(hipEventRecord(G.evShadow[d], G.s1));
-                g.stats.launches_shadow++;
-                if (!last) {
-                    g_timer.begin(&g.stats.ms_extend, G.s0);
-                    launch_extend(G.s0, av, ps, G.dCounts + d + 1, n0, tmin, tmax, visit ? visit + 8 * (d + 1) : nullptr, G.dCounts + 64 + d + 1);
-                    g_timer.end(G.s0);
-                    g.stats.launches_extend++;
-                }
-            }
-        }
+        if (trace_bounces(B, gps, gPaths, nGroups)) return -1;
         for (int k = 0; k < nGroups; ++k) {
             Context::Group& G = g.groups[k];
-            if (overlap && maxDepth > 0) HIP_OK(hipStreamWaitEvent(G.s0, G.evShadow[maxDepth - 1], 0));
+            if (B.overlap && maxDepth > 0) HIP_OK(hipStreamWaitEvent(G.s0, G.evShadow[maxDepth - 1], 0));
             HIP_OK(hipMemcpyAsync(G.hCounts, G.dCounts, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, G.s0));
             if (k > 0) { HIP_OK(hipEventRecord(G.evDone, G.s0)); HIP_OK(hipStreamWaitEvent(g.stream, G.evDone, 0)); }
         }
@@ -1943,13 +1988,7 @@ static int trace_rays_device(uint32_t width, uint32_t height)
                           static_cast<float*>(dp(bScratch)), static_cast<uint8_t*>(dp(bImage)));
         g_timer.end();
         HIP_OK(hipStreamSynchronize(g.stream));
-        for (int k = 0; k < nGroups; ++k) {
-            const uint32_t* hc = g.groups[k].hCounts;
-            for (uint32_t d = 0; d <= maxDepth && maxDepth; ++d) g.bounceCounts[d] += hc[d];
-            if (maxDepth) g.stats.rays_primary += hc[0];
-            for (uint32_t d = 1; d < maxDepth; ++d) g.stats.rays_bounce += hc[d];
-            for (uint32_t d = 0; d < maxDepth; ++d) { g.stats.rays_shadow += hc[d + 1]; g.stats.closest_hits += hc[d + 1]; }
-        }
+        add_group_counts(nGroups, maxDepth);
     }
     if (batch == 0 && P) {
         // no samples: only the tonemap of the existing accumulator runs (shader.cl:283-304)
@@ -2233,6 +2272,49 @@ extern "C" int rdx_debug_surface_in_bounds(const rdx_mesh_info* mi, uint32_t nin
     return surface_in_bounds(reinterpret_cast<const MeshInfo*>(mi), ninst, nmeshinfo, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv) ? 1 : 0;
 }
 
+// ---- an rdx_shading_buffers as rdx_shade_hits and rdx_trace_paths check it --------------------------------------------------
+namespace {
+// handles and the scene buffer's size; samplerBits = the sampler as TexView::flags bits (no sampler: repeat + nearest, as scene_args)
+int check_shading_handles(const char* who, const rdx_shading_buffers* scene, uint32_t& samplerBits)
+{
+    if (!scene) return fail("%s: no scene buffers", who);
+    if (!scene->scene || !known_buffer(scene->scene)) return fail("%s: invalid scene (SceneProperties) buffer handle", who);
+    if (!scene->meshInfo || !known_buffer(scene->meshInfo)) return fail("%s: invalid meshInfo buffer handle", who);
+    if (!scene->index || !known_buffer(scene->index)) return fail("%s: invalid index buffer handle", who);
+    if (!scene->normal || !known_buffer(scene->normal)) return fail("%s: invalid normal buffer handle", who);
+    if (!scene->material || !known_buffer(scene->material)) return fail("%s: invalid material buffer handle", who);
+    if (scene->uv && !known_buffer(scene->uv)) return fail("%s: invalid uv buffer handle", who);
+    if (scene->textureArray && !known_buffer(scene->textureArray)) return fail("%s: invalid textureArray handle", who);
+    samplerBits = TEX_ADDR_REPEAT << TEX_ADDR_SHIFT;
+    if (scene->sampler && !sampler_bits(scene->sampler, samplerBits)) return fail("%s: invalid sampler handle", who);
+    if (scene->scene->size < sizeof(SceneProperties))
+        return fail("%s: the scene buffer (%zu bytes) does not hold a SceneProperties (%zu bytes)", who, scene->scene->size, sizeof(SceneProperties));
+    return 0;
+}
+int check_shading_alignment(const char* who, const rdx_shading_buffers* scene)
+{
+    if ((reinterpret_cast<uintptr_t>(scene->scene->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->meshInfo->dptr) & 3u) ||
+        (reinterpret_cast<uintptr_t>(scene->index->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->normal->dptr) & 3u) ||
+        (reinterpret_cast<uintptr_t>(scene->material->dptr) & 3u) || (scene->uv && (reinterpret_cast<uintptr_t>(scene->uv->dptr) & 3u)) ||
+        (scene->textureArray && (reinterpret_cast<uintptr_t>(scene->textureArray->dptr) & 3u)))
+        return fail("%s: wrapped scene streams must be 4-byte aligned", who);
+    return 0;
+}
+// the stock shader's rule (scene_args): texels are read only when option "textures" is 1 and an image array is given; the uv
+// buffer is required then
+int shading_textures(const char* who, const rdx_shading_buffers* scene, uint32_t samplerBits, TexView& tex)
+{
+    tex = TexView{nullptr, 0, 0, 0, 0};
+    if (!g.opt.textures || !scene->textureArray) return 0;
+    const rdx_buffer_s* img = scene->textureArray;
+    if (!img->imgW || !img->imgH || !img->imgLayers) return fail("%s: textureArray is not an image array (rdx_image_array_create)", who);
+    if (img->size / 4 / img->imgW / img->imgH < img->imgLayers) return fail("%s: textureArray is smaller than its %u layers", who, img->imgLayers);
+    if (!scene->uv || scene->uv->size < sizeof(float)) return fail("%s: option \"textures\" is 1 and a textureArray is given, but no uv buffer", who);
+    tex = TexView{static_cast<const uint8_t*>(img->dptr), img->imgW, img->imgH, img->imgLayers, TEX_ENABLED | samplerBits};
+    return 0;
+}
+} // namespace
+
 // The stock closest-hit / miss shaders on a query's records (shade.hip): the checks and the steps around the launch are those of
 // rdx_resolve_hits
 extern "C" int rdx_shade_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, rdx_buffer keys,
@@ -2249,18 +2331,8 @@ extern "C" int rdx_shade_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offs
     if (next && !known_buffer(next)) return fail("rdx_shade_hits: invalid next-ray buffer handle");
     if (shadow && !known_buffer(shadow)) return fail("rdx_shade_hits: invalid shadow-ray buffer handle");
     if (src && !known_buffer(src)) return fail("rdx_shade_hits: invalid src buffer handle");
-    if (!scene) return fail("rdx_shade_hits: no scene buffers");
-    if (!scene->scene || !known_buffer(scene->scene)) return fail("rdx_shade_hits: invalid scene (SceneProperties) buffer handle");
-    if (!scene->meshInfo || !known_buffer(scene->meshInfo)) return fail("rdx_shade_hits: invalid meshInfo buffer handle");
-    if (!scene->index || !known_buffer(scene->index)) return fail("rdx_shade_hits: invalid index buffer handle");
-    if (!scene->normal || !known_buffer(scene->normal)) return fail("rdx_shade_hits: invalid normal buffer handle");
-    if (!scene->material || !known_buffer(scene->material)) return fail("rdx_shade_hits: invalid material buffer handle");
-    if (scene->uv && !known_buffer(scene->uv)) return fail("rdx_shade_hits: invalid uv buffer handle");
-    if (scene->textureArray && !known_buffer(scene->textureArray)) return fail("rdx_shade_hits: invalid textureArray handle");
-    uint32_t samplerBits = TEX_ADDR_REPEAT << TEX_ADDR_SHIFT;      // no sampler: repeat + nearest, as scene_args
-    if (scene->sampler && !sampler_bits(scene->sampler, samplerBits)) return fail("rdx_shade_hits: invalid sampler handle");
-    if (scene->scene->size < sizeof(SceneProperties))
-        return fail("rdx_shade_hits: the scene buffer (%zu bytes) does not hold a SceneProperties (%zu bytes)", scene->scene->size, sizeof(SceneProperties));
+    uint32_t samplerBits = 0;
+    if (check_shading_handles("rdx_shade_hits", scene, samplerBits)) return -1;
     static_assert(sizeof(rdx_shade) == 48 && sizeof(rdx_shade_key) == 16 && sizeof(rdx_shading_buffers) == 8 * sizeof(void*), "three float4 per shade record, one uint4 per key");
     // every range the kernel touches: {buffer, offset, bytes per record, name}; the first three are read, the others written
     struct Range { rdx_buffer b; size_t off, rec; const char* name; };
@@ -2277,11 +2349,7 @@ extern "C" int rdx_shade_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offs
     if (!n) return 0;
     for (const Range& r : R)
         if (r.b && (reinterpret_cast<uintptr_t>(r.b->dptr) & 15u)) return fail("rdx_shade_hits: wrapped device memory must be 16-byte aligned (%s buffer)", r.name);
-    if ((reinterpret_cast<uintptr_t>(scene->scene->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->meshInfo->dptr) & 3u) ||
-        (reinterpret_cast<uintptr_t>(scene->index->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->normal->dptr) & 3u) ||
-        (reinterpret_cast<uintptr_t>(scene->material->dptr) & 3u) || (scene->uv && (reinterpret_cast<uintptr_t>(scene->uv->dptr) & 3u)) ||
-        (scene->textureArray && (reinterpret_cast<uintptr_t>(scene->textureArray->dptr) & 3u)))
-        return fail("rdx_shade_hits: wrapped scene streams must be 4-byte aligned");
+    if (check_shading_alignment("rdx_shade_hits", scene)) return -1;
     // no output range may overlap an input range or another output range, in one buffer or in several that wrap the same memory
     for (int o = 3; o < 7; ++o)
         for (int k = 0; k < o; ++k) {
@@ -2296,16 +2364,8 @@ extern "C" int rdx_shade_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offs
     sc.s.index = static_cast<const uint32_t*>(scene->index->dptr); sc.s.nIndex = scene->index->size / sizeof(uint32_t);
     sc.s.normal = static_cast<const float*>(scene->normal->dptr); sc.s.nNormal = scene->normal->size / sizeof(float);
     sc.materials = static_cast<const Material*>(scene->material->dptr); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
-    sc.tex = TexView{nullptr, 0, 0, 0, 0};
-    // the stock shader's rule (scene_args): texels are read only when option "textures" is 1 and an image array is given
-    if (g.opt.textures && scene->textureArray) {
-        const rdx_buffer_s* img = scene->textureArray;
-        if (!img->imgW || !img->imgH || !img->imgLayers) return fail("rdx_shade_hits: textureArray is not an image array (rdx_image_array_create)");
-        if (img->size / 4 / img->imgW / img->imgH < img->imgLayers) return fail("rdx_shade_hits: textureArray is smaller than its %u layers", img->imgLayers);
-        if (!scene->uv || scene->uv->size < sizeof(float)) return fail("rdx_shade_hits: option \"textures\" is 1 and a textureArray is given, but no uv buffer");
-        sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float);
-        sc.tex = TexView{static_cast<const uint8_t*>(img->dptr), img->imgW, img->imgH, img->imgLayers, TEX_ENABLED | samplerBits};
-    }
+    if (shading_textures("rdx_shade_hits", scene, samplerBits, sc.tex)) return -1;
+    if (sc.tex.flags & TEX_ENABLED) { sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float); }
     if (derive_accel(tlas)) return -1;
     const AccelCache& ac = *acc(tlas);
     auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
@@ -2442,6 +2502,107 @@ extern "C" int rdx_accumulate(rdx_buffer colors, size_t colors_offset, uint32_t 
     if (invalid_out) *invalid_out = invalid;
     std::memset(&g.stats, 0, sizeof g.stats);
     HIP_OK(hipEventElapsedTime(&g.stats.ms_accumulate, g.evA, g.evB));      // kernel time of this call
+    return 0;
+}
+
+// Radiance along the caller's own rays (include/rdx.h): launch_query_rays for the first segment, k_paths_ingest (paths.hip) to
+// make paths of rays, records and keys, then the bounces of the frame path (trace_bounces) -- per chunk of "chunk_paths" paths, in
+// group 0's streams.  A finished path stores its colour as record `slot` of sampleColor (BounceArgs: nPixels 0, sampleBase 0),
+// which is the chunk's part of the caller's radiance range.
+extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
+                               uint32_t max_depth, const rdx_shading_buffers* scene, rdx_buffer radiance, size_t radiance_offset,
+                               rdx_buffer hits, size_t hits_offset)
+{
+    if (!g.initialized) return fail("rdx_trace_paths: rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths: invalid TLAS handle");
+    if (!rays || !known_buffer(rays)) return fail("rdx_trace_paths: invalid ray buffer handle");
+    if (!keys || !known_buffer(keys)) return fail("rdx_trace_paths: invalid key buffer handle");
+    if (!radiance || !known_buffer(radiance)) return fail("rdx_trace_paths: invalid radiance buffer handle");
+    if (hits && !known_buffer(hits)) return fail("rdx_trace_paths: invalid hit buffer handle");
+    uint32_t samplerBits = 0;
+    if (check_shading_handles("rdx_trace_paths", scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths: depth %u exceeds the supported maximum of 62", max_depth);
+    static_assert(sizeof(rdx_ray) == 32 && sizeof(rdx_ray_hit) == 32 && sizeof(rdx_shade_key) == 16, "two float4 per ray and record, one uint4 per key");
+    const FrameRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16},
+                             {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16},
+                             {hits, hits_offset, (size_t)n * sizeof(rdx_ray_hit), "hit", 16}};
+    if (check_frame_ranges("rdx_trace_paths", R, 4, 2, n)) return -1;
+    if (!n) return 0;
+    if (check_shading_alignment("rdx_trace_paths", scene)) return -1;
+    SceneArgs sc{};
+    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
+    sc.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr);
+    sc.indexData = static_cast<const uint32_t*>(scene->index->dptr);
+    sc.uvData = scene->uv ? static_cast<const float*>(scene->uv->dptr) : nullptr;
+    sc.normalData = static_cast<const float*>(scene->normal->dptr);
+    sc.materials = static_cast<const Material*>(scene->material->dptr);
+    if (shading_textures("rdx_trace_paths", scene, samplerBits, sc.tex)) return -1;
+    if (derive_accel(tlas)) return -1;
+    const AccelCache& ac = *acc(tlas);
+
+    const uint32_t chunk = (uint32_t)std::min<int64_t>(n, g.opt.chunkPaths);
+    Context::Group& G = g.groups[0];
+    if (max_depth && ensure_group(G, chunk)) return -1;
+    if (max_depth && !hits && g.pathHitsCap < chunk) {
+        if (g.pathHits) HIP_IGN(hipFree(g.pathHits));
+        g.pathHits = nullptr; g.pathHitsCap = 0;
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.pathHits), (size_t)chunk * sizeof(rdx_ray_hit)));
+        g.pathHitsCap = chunk;
+    }
+    const float4* dRays = reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset);
+    const uint4* dKeys = reinterpret_cast<const uint4*>(static_cast<const char*>(keys->dptr) + keys_offset);
+    float4* dRad = reinterpret_cast<float4*>(static_cast<char*>(radiance->dptr) + radiance_offset);
+    float4* dHits = hits ? reinterpret_cast<float4*>(static_cast<char*>(hits->dptr) + hits_offset) : nullptr;
+
+    std::memset(&g.stats, 0, sizeof g.stats);
+    std::memset(g.bounceCounts, 0, sizeof g.bounceCounts);
+    g.stats.pixels = n;
+    g.stats.groups = 1;
+    g.visitDepth = 0;
+    set_grid_share(1);
+    // the first segment: the per-ray-interval engine on the view rdx_query_rays gives it; the bounces: the frame path's view
+    const AccelView avQuery = view_of(tlas);
+    BounceArgs B{tlas, view_of(tlas, (uint64_t)chunk <= (uint64_t)g.opt.sortMinPaths), sc, max_depth, 0u, 0u, false, false, false, SortBox{}, nullptr,
+                 0.001f, 1000.0f};      // shader.cl:235-236, 500
+    bounce_switches(chunk, B);
+    B.overlap = false;
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+        const uint32_t m = std::min(chunk, n - c0);
+        float4* segHits = dHits ? dHits + 2 * (size_t)c0 : g.pathHits;
+        if (max_depth == 0) {
+            // no segment is traced: colour 0 for every path; `hits` still gets the records of the query it stands for
+            HIP_OK(hipMemsetAsync(dRad + c0, 0, (size_t)m * sizeof(float4), g.stream));
+            if (dHits) {
+                HIP_OK(hipMemsetAsync(G.dCounts + 64, 0, sizeof(uint32_t), g.stream));
+                launch_query_rays(g.stream, avQuery, dRays + 2 * (size_t)c0, m, RDX_QUERY_CLOSEST, segHits, G.dCounts + 64);
+            }
+            continue;
+        }
+        std::memset(G.hCounts, 0, 256 * sizeof(uint32_t));
+        G.hCounts[0] = m;
+        HIP_OK(hipMemcpyAsync(G.dCounts, G.hCounts, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, G.s0));
+        g_timer.begin(&g.stats.ms_extend, G.s0);
+        launch_query_rays(G.s0, avQuery, dRays + 2 * (size_t)c0, m, RDX_QUERY_CLOSEST, segHits, G.dCounts + 64);
+        g_timer.end(G.s0);
+        g.stats.launches_extend++;
+        PathStreams ps = G.ps;
+        ps.sampleColor = dRad + c0;
+        g_timer.begin(&g.stats.ms_generate, G.s0);
+        launch_paths_ingest(G.s0, ac.slotOf, ac.s.nInst, dRays + 2 * (size_t)c0, segHits, dKeys + c0, m, ps);
+        g_timer.end(G.s0);
+        if (trace_bounces(B, &ps, &m, 1)) return -1;
+        HIP_OK(hipMemcpyAsync(G.hCounts, G.dCounts, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, G.s0));
+        HIP_OK(hipStreamSynchronize(g.stream));
+        add_group_counts(1, max_depth);
+    }
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    for (rdx_buffer b : {radiance, hits}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    if (take_status()) return fail("rdx_trace_paths: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_total, g.evA, g.evB));
+    g_timer.resolve();
     return 0;
 }
 

@@ -570,15 +570,15 @@ class ShadingBuffers:
         self.scene, self.meshInfo, self.index, self.uv, self.normal, self.material = scene, meshInfo, index, uv, normal, material
         self.textureArray, self.sampler = textureArray, sampler
 
-    def _struct(self):
+    def _struct(self, who="ShadeHits"):
         for name in self._REQUIRED:
             if not isinstance(getattr(self, name), Buffer):
-                raise RadianceError("ShadeHits: scene_buffers.%s must be a Buffer" % name)
+                raise RadianceError("%s: scene_buffers.%s must be a Buffer" % (who, name))
         for name in ("uv", "textureArray"):
             if getattr(self, name) is not None and not isinstance(getattr(self, name), Buffer):
-                raise RadianceError("ShadeHits: scene_buffers.%s must be a Buffer or None" % name)
+                raise RadianceError("%s: scene_buffers.%s must be a Buffer or None" % (who, name))
         if self.sampler is not None and not isinstance(self.sampler, Sampler):
-            raise RadianceError("ShadeHits: scene_buffers.sampler must be a Sampler or None")
+            raise RadianceError("%s: scene_buffers.sampler must be a Sampler or None" % who)
         h = lambda x: x.handle if x is not None else None
         return _lib.rdx_shading_buffers(self.scene.handle, self.meshInfo.handle, self.index.handle, h(self.uv), self.normal.handle,
                                         self.material.handle, h(self.textureArray), h(self.sampler))
@@ -794,6 +794,70 @@ def AccumulateTorch(colors, frame_id, scratch, image=None, pixels=None, debug=Fa
         return n
     wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
     return Accumulate(wrap(c, 16), n, frame_id, bs, bi, 0, wrap(pixels, 4), debug)
+
+
+# ---- radiance along the caller's own rays (rdx_trace_paths) -------------------------------------------------------------
+def TracePaths(tlas, rays, keys, n, max_depth, scene_buffers, radiance=None, hits=None, rays_offset=0, keys_offset=0, radiance_offset=0,
+               hits_offset=0):
+    """Extension: the reference's raygen loop for `n` rays of the caller's own, on the frame path's stages.  Path i starts with the
+    RAY_DTYPE record i of `rays` (its own tmin / tmax for the first segment; 0.001 / 1000 after it) and the SHADE_KEY_DTYPE
+    record i of `keys` (frameID, pixel; depth and _0 are ignored) and is followed for at most `max_depth` (0 .. 62) segments;
+    one float4 (rgb, 0) per path goes to `radiance`: the bits of the loop over QueryRays / ShadeHits, the sample Accumulate
+    expects.  scene_buffers: a ShadingBuffers or a tuple of its constructor's arguments; it must describe the scene of `tlas` (the
+    shade stage gathers unchecked, as TraceRays does).  radiance: a Buffer, or None (created: radiance_offset + 16 n bytes).
+    hits: a Buffer, True (created) or None / False (not wanted): the RAY_HIT_DTYPE records of the first segment, as
+    QueryRays(..., QUERY_CLOSEST) writes them.  Device buffers in and out; nothing passes through the host.  Returns `radiance`
+    (the hit buffer is `hits` where the caller passed one; rd.TracePaths(..., hits=True) returns (radiance, hits))."""
+    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
+        raise RadianceError("TracePaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    if not isinstance(scene_buffers, ShadingBuffers):
+        try:
+            scene_buffers = ShadingBuffers(*scene_buffers)
+        except TypeError:
+            raise RadianceError("TracePaths: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
+                                "[, textureArray, sampler]) tuple")
+    sb = scene_buffers._struct("TracePaths")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
+            or max_depth < 0:
+        raise RadianceError("TracePaths: n and max_depth must be non-negative integers")
+    n = int(n)
+    if radiance is None:
+        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
+    elif not isinstance(radiance, Buffer):
+        raise RadianceError("TracePaths: radiance must be a Buffer or None")
+    made_hits = hits is True
+    if made_hits:
+        hits = CreateBuffer(None, max(int(hits_offset) + RAY_HIT_DTYPE.itemsize * n, 1))
+    elif hits is False:
+        hits = None
+    hh = _optional_buffer("TracePaths", hits, "hits")
+    _check(_lib.lib().rdx_trace_paths(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), C.byref(sb),
+                                      radiance.handle, int(radiance_offset), hh, int(hits_offset)))
+    return (radiance, hits) if made_hits else radiance
+
+
+def TracePathsTorch(tlas, rays_t, keys_t, max_depth, scene_buffers, want_hits=False):
+    """Extension: TracePaths on CUDA tensors -- rays a contiguous float32 (n, 8) tensor (origin, tmin, direction, tmax per row), keys
+    a contiguous int32 (n, 4) tensor (frameID, pixel, -, -): what GenerateRaysTorch returns, or rays of the caller's own.
+    Returns radiance float32 (n, 4): rgb, 0 -- what AccumulateTorch takes -- and, with want_hits, (radiance, hits int32 (n, 8)).
+    The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
+    import torch
+    r, k = rays_t, keys_t
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
+        raise RadianceError("TracePathsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(r.shape[0])
+    if not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
+            and k.device == r.device):
+        raise RadianceError("TracePathsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
+        raise RadianceError("TracePathsTorch: max_depth must be a non-negative integer")
+    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    hits = torch.empty((n, 8), dtype=torch.int32, device=r.device) if want_hits else None
+    torch.cuda.current_stream(r.device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+        TracePaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, scene_buffers, wrap(radiance, 16), wrap(hits, 32))
+    return (radiance, hits) if want_hits else radiance
 
 
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
