@@ -189,6 +189,28 @@ inline uint32_t ShadeHits(Platform*, TopAccelStruct accelStruct, Buffer rays, Bu
     return live;
 }
 
+// Extension (no reference counterpart; rdx_resolve_materials): the evaluated material (rdx_material_record: shading normal, albedo,
+// metallic, roughness, transmission, ior, the shadow ray's origin, material number) of the `n` records `hits` that
+// rdx_query_rays(..., RDX_QUERY_CLOSEST, ...) wrote for `rays`, device memory in and out.  `scene` as for ShadeHits.  Returns the number
+// of records the bounds rule refused (they are written as zeros).
+inline uint32_t ResolveMaterials(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer hits, uint32_t n, const rdx_shading_buffers& scene,
+                                 Buffer out, size_t raysOffset = 0, size_t hitsOffset = 0, size_t outOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_resolve_materials(accelStruct, rays, raysOffset, hits, hitsOffset, n, &scene, out, outOffset, &invalid)) detail::fatal("ResolveMaterials");
+    return invalid;
+}
+
+// Extension (no reference counterpart; rdx_light_hits): the direct term of directional light `light` (0 .. 4) of the SceneProperties
+// in `scene` (the buffer of descriptor slot 4) for the `n` material records `materials` and the directions of `rays`: one float4
+// (rgb, 0) per ray goes to `lit`, the shadow ray towards the light (rdx_ray, ready for rdx_query_rays(..., RDX_QUERY_ANY, ...)) to
+// `shadow` (may be nullptr).  The ambient term stays the caller's.
+inline void LightHits(Platform*, Buffer rays, Buffer materials, uint32_t n, Buffer scene, uint32_t light, Buffer lit, Buffer shadow = nullptr,
+                      size_t raysOffset = 0, size_t materialsOffset = 0, size_t litOffset = 0, size_t shadowOffset = 0)
+{
+    if (rdx_light_hits(rays, raysOffset, materials, materialsOffset, n, scene, light, lit, litOffset, shadow, shadowOffset)) detail::fatal("LightHits");
+}
+
 // Extension (no reference counterpart; rdx_generate_rays): `n` camera rays of the PhysicalCamera in `camera` (the contents of
 // descriptor slot 3) as rdx_ray records in `rays`, and -- `keys` may be nullptr -- their rdx_shade_key records of depth 0; device
 // memory in and out.  Ray i is pixel firstPixel + i, or pixels[i]; its random input is pcg3d(frameID, totalSamples, pixel), or

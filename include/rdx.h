@@ -381,6 +381,53 @@ int         rdx_debug_shade_in_bounds(const rdx_mesh_info* mi, uint32_t ninst, u
                                       uint64_t nuv, const rdx_material* materials, uint32_t nmaterials, int textures,
                                       uint32_t layers);
 
+/* The evaluated material of the hits of a ray query, and one directional light's direct term on it, on the device: the two halves
+ * of the stock closest-hit shader `material` (samples/shader.cl:482-541) before its next-direction sample, for a caller with a
+ * light loop, a BRDF or a denoiser of its own.
+ * rdx_resolve_materials: `tlas`, `rays`, `hits`, `scene` are exactly those of rdx_shade_hits (no keys: nothing random is drawn);
+ * one 64-byte rdx_material_record per ray goes to `out`.  Record with hit == 1: the HitData is derived as for rdx_shade_hits, and
+ * every field holds the bits `material` holds in the variable of the same meaning under the floating-point contract of DESIGN.md
+ * 2: normal = N = getMatNormal(..., faceN) (shader.cl:369-395: the face normal, or -- a material with a normal map -- the mapped
+ * normal), albedo = getAlbedo (shader.cl:432-451), metallic / roughness / transmission / ior = getMaterialProp (shader.cl:398-430)
+ * with its clamps, above = getHitPosition(hitData, faceN) (the origin of the shadow ray), materialIndex = MeshInfo.materialIndex.
+ * Textures follow the stock shader's rule as in rdx_shade_hits: texels are read, through `sampler`, only when option "textures" is
+ * 1 and `textureArray` is given -- `uv` is required then; otherwise a material with a texture index sees texel 0, the normal map
+ * included (whose texel-0 normal is NOT the face normal).  Every other record -- a miss, any other value of `hit` -- is 64 zero
+ * bytes.  No record makes the kernel read outside a buffer: the bounds rule is that of rdx_shade_hits, unchanged; a hit it calls
+ * INVALID writes the zero record and is counted in *invalid_out (optional), and the call still returns 0.  Staging, blocking,
+ * layout derivation on first use, the transforms of the last rdx_tlas_update, logical device 0 in multi-device mode and
+ * rdx_get_trace_stats().ms_shade (the kernel time of the call): as for rdx_shade_hits.  Refused, before anything is launched: what
+ * rdx_shade_hits refuses, for tlas / rays / hits / out / scene (32 n bytes for rays / hits, 64 n for out; `out` overlapping the
+ * ray range or the hit range).  n == 0 succeeds and touches nothing.
+ * rdx_light_hits: for light j = `light` of the SceneProperties in `scene` (the buffer of descriptor slot 4; read on the device by
+ * every call) and a material record with hit == 1:  L = normalize(-lights[j].direction.xyz), V = normalize(-ray.direction),
+ * lit.rgb = (0, 0, 0) + microfacetBRDF(L, V, N, albedo, metallic, roughness, transmission) * lights[j].color.rgb (pbr.cl:268-287),
+ * operation for operation the `direct` of `material` (shader.cl:503-508), which it is bit for bit for j = 0; lit.w = 0.  The
+ * shadow record (optional) is (above | 0.001, L | 1000), ready for rdx_query_rays(..., RDX_QUERY_ANY, ...): the light reaches the
+ * hit iff that query reports no hit.  Any other value of `hit` gives 16 / 32 zero bytes (tmax 0 accepts nothing).  The ambient
+ * term stays the caller's (the stock shader's: albedo * 0.1f, once per hit), and lightCount is not consulted, as the stock shader
+ * does not consult it.  Only the direction of a ray is read.  The kernel gathers nothing but the one light, so no record can make
+ * it read outside a buffer; material records the caller filled in itself are equally allowed.  It takes no TLAS; it blocks, and
+ * rdx_get_trace_stats().ms_shade is the kernel time of the call.  Refused, before anything is launched: an uninitialised library;
+ * a NULL or unknown handle among rays / materials / scene / lit, an unknown `shadow`; light > 4; a scene buffer smaller than a
+ * SceneProperties; an offset that is not a multiple of 16; a range that does not hold n records (32 n for rays / shadow, 64 n for
+ * materials, 16 n for lit); an output range that overlaps an input range, the SceneProperties or the other output range; wrapped
+ * memory that is misaligned.  n == 0 succeeds and touches nothing. */
+typedef struct rdx_material_record {            /* 64 B, four float4 */
+    float normal[3];  uint32_t hit;             /* N = getMatNormal(..., faceN) (shader.cl:369-395); hit: 1 / 0 */
+    float albedo[3];  uint32_t materialIndex;   /* getAlbedo (shader.cl:432-451); MeshInfo.materialIndex */
+    float metallic, roughness, transmission, ior;   /* getMaterialProp (shader.cl:398-430), clamps included */
+    float above[3];   uint32_t _0;              /* getHitPosition(hitData, faceN): the shadow ray's origin; _0 = 0 */
+} rdx_material_record;
+int         rdx_resolve_materials(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset,
+                                  uint32_t n, const rdx_shading_buffers* scene, rdx_buffer out, size_t out_offset,
+                                  uint32_t* invalid_out /* optional */);
+int         rdx_light_hits(rdx_buffer rays, size_t rays_offset,            /* rdx_ray per record: only the direction is read */
+                           rdx_buffer materials, size_t materials_offset,  /* rdx_material_record per ray */
+                           uint32_t n, rdx_buffer scene /* slot 4: SceneProperties */, uint32_t light /* 0 .. 4 */,
+                           rdx_buffer lit, size_t lit_offset,              /* out float4 per ray: rgb, w = 0 */
+                           rdx_buffer shadow, size_t shadow_offset);       /* optional out: rdx_ray per ray */
+
 /* The two ends of a frame, on the device: the camera rays a loop over rdx_query_rays / rdx_shade_hits starts from, and the step
  * that folds its finished samples into the frame rdx_trace_rays would have written.
  * rdx_generate_rays: ray i is generateRay (samples/shader.cl:111-173) for pixel_i = pixels ? pixels[i] : first_pixel + i, with

@@ -88,6 +88,12 @@ class rdx_shade(C.Structure):
                 ("nextFactor", C.c_float * 3), ("slot", C.c_uint32)]
 
 
+class rdx_material_record(C.Structure):
+    _fields_ = [("normal", C.c_float * 3), ("hit", C.c_uint32), ("albedo", C.c_float * 3), ("materialIndex", C.c_uint32),
+                ("metallic", C.c_float), ("roughness", C.c_float), ("transmission", C.c_float), ("ior", C.c_float),
+                ("above", C.c_float * 3), ("_0", C.c_uint32)]
+
+
 class rdx_shading_buffers(C.Structure):
     _fields_ = [("scene", C.c_void_p), ("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p),
                 ("material", C.c_void_p), ("textureArray", C.c_void_p), ("sampler", C.c_void_p)]
@@ -158,6 +164,10 @@ SIGNATURES = {
     "rdx_shade_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
                                  C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                  C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rdx_resolve_materials": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(rdx_shading_buffers),
+                                        C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rdx_light_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                 C.c_void_p, C.c_size_t]),
     "rdx_generate_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                     C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "rdx_accumulate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,

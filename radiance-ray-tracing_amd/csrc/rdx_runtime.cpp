@@ -37,6 +37,7 @@
 #include "bvh_build.h"
 #include "device_math.h"
 #include "kernels.h"
+#include "material_eval.h"
 #include "paths.h"
 #include "raygen.h"
 #include "rdx_types.h"
@@ -152,7 +153,7 @@ struct Context {
     uint32_t* dStatus = nullptr;            // its device address
     unsigned long long* dVisit = nullptr;   // 8 words
     uint32_t* dSurfaceInvalid = nullptr;    // rdx_resolve_hits: records that failed the bounds rule, one word
-    uint32_t* dShadeCounts = nullptr;       // rdx_shade_hits: [0] = surviving rays (the compaction cursor), [1] = records that failed the bounds rule
+    uint32_t* dShadeCounts = nullptr;       // rdx_shade_hits: [0] = surviving rays (the compaction cursor), [1] = records that failed the bounds rule (also rdx_resolve_materials')
     CameraArgs* dRaygenArgs = nullptr;      // rdx_generate_rays: the camera's per-call constants, written by its first kernel
     uint32_t* dAccumInvalid = nullptr;      // rdx_accumulate: samples whose pixel number is outside the frame, one word
     float4* pathHits = nullptr;             // rdx_trace_paths without `hits`: the first segment's records of one chunk (2 float4 per path)
@@ -2398,6 +2399,118 @@ extern "C" int rdx_debug_shade_in_bounds(const rdx_mesh_info* mi, uint32_t ninst
     static_assert(sizeof(Material) == sizeof(rdx_material), "Material layout");
     return shade_in_bounds(reinterpret_cast<const MeshInfo*>(mi), ninst, nmeshinfo, instanceIndex, primitiveIndex, idx3, nindex, nnormal,
                            textures ? nuv : 0u, reinterpret_cast<const Material*>(materials), nmaterials, textures != 0, layers) ? 1 : 0;
+}
+
+// The evaluated material of a query's hits (material.hip): the inputs, the checks and the steps around the launch are those of
+// rdx_shade_hits without the keys
+extern "C" int rdx_resolve_materials(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, uint32_t n,
+                                     const rdx_shading_buffers* scene, rdx_buffer out, size_t out_offset, uint32_t* invalid_out)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_resolve_materials: invalid TLAS handle");
+    if (!rays || !known_buffer(rays)) return fail("rdx_resolve_materials: invalid ray buffer handle");
+    if (!hits || !known_buffer(hits)) return fail("rdx_resolve_materials: invalid hit buffer handle");
+    if (!out || !known_buffer(out)) return fail("rdx_resolve_materials: invalid output buffer handle");
+    uint32_t samplerBits = 0;
+    if (check_shading_handles("rdx_resolve_materials", scene, samplerBits)) return -1;
+    static_assert(sizeof(rdx_material_record) == 64, "four float4 per material record");
+    struct Range { rdx_buffer b; size_t off, rec; const char* name; };
+    const Range R[3] = {{rays, rays_offset, sizeof(rdx_ray), "ray"}, {hits, hits_offset, sizeof(rdx_ray_hit), "hit"},
+                        {out, out_offset, sizeof(rdx_material_record), "output"}};
+    for (const Range& r : R)
+        if (r.off & 15u) return fail("rdx_resolve_materials: offsets must be multiples of 16 bytes (%s offset %zu)", r.name, r.off);
+    for (const Range& r : R)
+        if (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off)
+            return fail("rdx_resolve_materials: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
+    if (invalid_out) *invalid_out = 0;
+    if (!n) return 0;
+    for (const Range& r : R)
+        if (reinterpret_cast<uintptr_t>(r.b->dptr) & 15u) return fail("rdx_resolve_materials: wrapped device memory must be 16-byte aligned (%s buffer)", r.name);
+    if (check_shading_alignment("rdx_resolve_materials", scene)) return -1;
+    for (int k = 0; k < 2; ++k) {       // the output must not overlap what the kernel reads of the rays and of the records
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[2].b->dptr) + R[2].off, a1 = a0 + (size_t)n * R[2].rec,
+                        b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
+        if (a0 < b1 && b0 < a1) return fail("rdx_resolve_materials: the %s range and the %s range overlap", R[2].name, R[k].name);
+    }
+    ShadeScene sc{};
+    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
+    sc.s.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.s.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
+    sc.s.index = static_cast<const uint32_t*>(scene->index->dptr); sc.s.nIndex = scene->index->size / sizeof(uint32_t);
+    sc.s.normal = static_cast<const float*>(scene->normal->dptr); sc.s.nNormal = scene->normal->size / sizeof(float);
+    sc.materials = static_cast<const Material*>(scene->material->dptr); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
+    if (shading_textures("rdx_resolve_materials", scene, samplerBits, sc.tex)) return -1;
+    if (sc.tex.flags & TEX_ENABLED) { sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float); }
+    if (derive_accel(tlas)) return -1;
+    const AccelCache& ac = *acc(tlas);
+    HIP_OK(hipMemsetAsync(g.dShadeCounts, 0, 2 * sizeof(uint32_t), g.stream));
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_resolve_materials(g.stream, ac.insts, ac.slotOf, ac.s.nInst, reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset),
+                             reinterpret_cast<const float4*>(static_cast<const char*>(hits->dptr) + hits_offset), n, sc,
+                             reinterpret_cast<float4*>(static_cast<char*>(out->dptr) + out_offset), g.dShadeCounts + 1);
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    ++out->version; out->mirrorValid = false;      // device code wrote it
+    uint32_t invalid = 0;
+    HIP_OK(hipMemcpy(&invalid, g.dShadeCounts + 1, sizeof invalid, hipMemcpyDeviceToHost));
+    if (invalid_out) *invalid_out = invalid;
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
+    return 0;
+}
+
+// One directional light's direct term on material records (material.hip).  No TLAS and no scene streams: the kernel reads the
+// rays' directions, the records and the one DirLight, so the checks are those of the ranges alone
+extern "C" int rdx_light_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer materials, size_t materials_offset, uint32_t n, rdx_buffer scene,
+                              uint32_t light, rdx_buffer lit, size_t lit_offset, rdx_buffer shadow, size_t shadow_offset)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!rays || !known_buffer(rays)) return fail("rdx_light_hits: invalid ray buffer handle");
+    if (!materials || !known_buffer(materials)) return fail("rdx_light_hits: invalid material-record buffer handle");
+    if (!scene || !known_buffer(scene)) return fail("rdx_light_hits: invalid scene (SceneProperties) buffer handle");
+    if (!lit || !known_buffer(lit)) return fail("rdx_light_hits: invalid lit buffer handle");
+    if (shadow && !known_buffer(shadow)) return fail("rdx_light_hits: invalid shadow-ray buffer handle");
+    constexpr uint32_t nLights = sizeof(SceneProperties::lights) / sizeof(DirLight);
+    if (light >= nLights) return fail("rdx_light_hits: light %u is not one of the %u lights of a SceneProperties (0 .. %u)", light, nLights, nLights - 1u);
+    if (scene->size < sizeof(SceneProperties))
+        return fail("rdx_light_hits: the scene buffer (%zu bytes) does not hold a SceneProperties (%zu bytes)", scene->size, sizeof(SceneProperties));
+    // every range the kernel touches: {buffer, offset, bytes per record, name}; the first two are read, the others written
+    struct Range { rdx_buffer b; size_t off, rec; const char* name; };
+    const Range R[4] = {{rays, rays_offset, sizeof(rdx_ray), "ray"}, {materials, materials_offset, sizeof(rdx_material_record), "material-record"},
+                        {lit, lit_offset, 4 * sizeof(float), "lit"}, {shadow, shadow_offset, sizeof(rdx_ray), "shadow-ray"}};
+    for (const Range& r : R)
+        if (r.b && (r.off & 15u)) return fail("rdx_light_hits: offsets must be multiples of 16 bytes (%s offset %zu)", r.name, r.off);
+    for (const Range& r : R)
+        if (r.b && (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off))
+            return fail("rdx_light_hits: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
+    if (!n) return 0;
+    for (const Range& r : R)
+        if (r.b && (reinterpret_cast<uintptr_t>(r.b->dptr) & 15u)) return fail("rdx_light_hits: wrapped device memory must be 16-byte aligned (%s buffer)", r.name);
+    if (reinterpret_cast<uintptr_t>(scene->dptr) & 3u) return fail("rdx_light_hits: a wrapped scene buffer must be 4-byte aligned");
+    // no output range may overlap an input range, the SceneProperties or the other output range, in one buffer or in several
+    // that wrap the same memory
+    for (int o = 2; o < 4; ++o) {
+        if (!R[o].b) continue;
+        const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[o].b->dptr) + R[o].off, a1 = a0 + (size_t)n * R[o].rec;
+        for (int k = 0; k < o; ++k) {
+            const uintptr_t b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
+            if (a0 < b1 && b0 < a1) return fail("rdx_light_hits: the %s range and the %s range overlap", R[o].name, R[k].name);
+        }
+        const uintptr_t s0 = reinterpret_cast<uintptr_t>(scene->dptr), s1 = s0 + sizeof(SceneProperties);
+        if (a0 < s1 && s0 < a1) return fail("rdx_light_hits: the %s range and the SceneProperties overlap", R[o].name);
+    }
+    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_light_hits(g.stream, reinterpret_cast<const float4*>(at(rays, rays_offset)), reinterpret_cast<const float4*>(at(materials, materials_offset)), n,
+                      reinterpret_cast<const DirLight*>(static_cast<const char*>(scene->dptr) + offsetof(SceneProperties, lights)) + light, reinterpret_cast<float4*>(at(lit, lit_offset)),
+                      reinterpret_cast<float4*>(at(shadow, shadow_offset)));
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    for (rdx_buffer b : {lit, shadow}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
+    return 0;
 }
 
 // ---- the two ends of a frame on device memory (raygen.hip) ---------------------------------------------------------------------

@@ -679,6 +679,123 @@ def DebugShadeInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nin
     return rc == 1
 
 
+# ---- the evaluated material of a query's hits, and one light's direct term (rdx_resolve_materials, rdx_light_hits) --------
+MATERIAL_RECORD_DTYPE = np.dtype([("normal", "<f4", 3), ("hit", "<u4"), ("albedo", "<f4", 3), ("materialIndex", "<u4"), ("metallic", "<f4"),
+                                  ("roughness", "<f4"), ("transmission", "<f4"), ("ior", "<f4"), ("above", "<f4", 3), ("_0", "<u4")])
+assert MATERIAL_RECORD_DTYPE.itemsize == C.sizeof(_lib.rdx_material_record) == 64
+MAX_LIGHTS = 5          # the DirLights of a SceneProperties
+
+
+def ResolveMaterials(tlas, rays, hits, n, scene_buffers, out=None, rays_offset=0, hits_offset=0, out_offset=0):
+    """Extension: one MATERIAL_RECORD_DTYPE record per ray -- the shading normal (normal map applied), the sampled albedo, metallic,
+    roughness, transmission, ior, the shadow ray's origin `above` and the material number, as the stock closest-hit shader holds
+    them -- for the `n` RAY_HIT_DTYPE records QueryRays(..., QUERY_CLOSEST) wrote to `hits` for `rays`; device buffers in, device
+    buffer out (created when None: out_offset + 64 n bytes).  scene_buffers: a ShadingBuffers or a tuple of its constructor's
+    arguments, textures by ShadeHits' rule.  Misses are 64 zero bytes; so are hits that would read outside a scene buffer, which
+    are counted.  Returns (out, invalid)."""
+    if not (isinstance(tlas, Buffer) and isinstance(rays, Buffer) and isinstance(hits, Buffer)):
+        raise RadianceError("ResolveMaterials: tlas, rays and hits must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    if not isinstance(scene_buffers, ShadingBuffers):
+        try:
+            scene_buffers = ShadingBuffers(*scene_buffers)
+        except TypeError:
+            raise RadianceError("ResolveMaterials: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
+                                "[, textureArray, sampler]) tuple")
+    sb = scene_buffers._struct("ResolveMaterials")
+    if out is None:
+        out = CreateBuffer(None, max(int(out_offset) + MATERIAL_RECORD_DTYPE.itemsize * int(n), 1))
+    elif not isinstance(out, Buffer):
+        raise RadianceError("ResolveMaterials: out must be a Buffer or None")
+    invalid = C.c_uint32(0)
+    _check(_lib.lib().rdx_resolve_materials(tlas.handle, rays.handle, int(rays_offset), hits.handle, int(hits_offset), int(n), C.byref(sb),
+                                            out.handle, int(out_offset), C.byref(invalid)))
+    return out, int(invalid.value)
+
+
+def LightHits(rays, materials, n, scene, light, lit=None, shadow=True, rays_offset=0, materials_offset=0, lit_offset=0, shadow_offset=0):
+    """Extension: the direct term of directional light `light` (0 .. 4) of the SceneProperties in the device buffer `scene`
+    (descriptor slot 4) for the `n` MATERIAL_RECORD_DTYPE records of `materials` (ResolveMaterials', or the caller's own) and the
+    directions of `rays`: one float4 (rgb, 0) per ray goes to `lit` (a Buffer, or None: created), and the shadow ray towards the
+    light, a RAY_DTYPE record ready for QueryRays(..., QUERY_ANY), to `shadow` (a Buffer, True: created, None / False: not wanted).
+    Records whose `hit` is not 1 give zeros.  The ambient term (albedo * 0.1 in the stock shader) stays the caller's.  Returns
+    (lit, shadow)."""
+    if not all(isinstance(b, Buffer) for b in (rays, materials, scene)):
+        raise RadianceError("LightHits: rays, materials and scene must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    n, light = int(n), int(light)
+    if not 0 <= light < MAX_LIGHTS:
+        raise RadianceError("LightHits: light %d is not one of the %d lights of a SceneProperties (0 .. %d)" % (light, MAX_LIGHTS, MAX_LIGHTS - 1))
+    if lit is None:
+        lit = CreateBuffer(None, max(int(lit_offset) + 16 * n, 1))
+    elif not isinstance(lit, Buffer):
+        raise RadianceError("LightHits: lit must be a Buffer or None")
+    if shadow is True:
+        shadow = CreateBuffer(None, max(int(shadow_offset) + RAY_DTYPE.itemsize * n, 1))
+    elif shadow is None or shadow is False:
+        shadow = None
+    elif not isinstance(shadow, Buffer):
+        raise RadianceError("LightHits: shadow must be a Buffer, True or None")
+    _check(_lib.lib().rdx_light_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), n, scene.handle, light, lit.handle,
+                                     int(lit_offset), shadow.handle if shadow is not None else None, int(shadow_offset)))
+    return lit, shadow
+
+
+def ResolveMaterialsTorch(tlas, rays_tensor, hits_tensor, scene_buffers, out=None):
+    """Extension: ResolveMaterials on CUDA tensors -- rays a contiguous float32 (n, 8) tensor, hits the contiguous int32 / float32
+    (n, 8) tensor QueryRaysTorch returned for them; the records land in `out`, a contiguous float32 CUDA tensor of shape (n, 16)
+    (created when None): columns 0-2 the normal, 4-6 the albedo, 8-11 metallic, roughness, transmission, ior, 12-14 `above`;
+    `.view(torch.int32)` shows hit and materialIndex in columns 3 and 7.  The library cannot see torch's stream, so the current
+    stream is synchronised first; the call blocks.  Returns (out, invalid)."""
+    import torch
+    r, h = rays_tensor, hits_tensor
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
+        raise RadianceError("ResolveMaterialsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(r.shape[0])
+    if not (isinstance(h, torch.Tensor) and h.is_cuda and h.dtype in (torch.int32, torch.float32) and tuple(h.shape) == (n, 8)
+            and h.is_contiguous() and h.device == r.device):
+        raise RadianceError("ResolveMaterialsTorch: hits must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
+    if out is None:
+        out = torch.empty((n, 16), dtype=torch.float32, device=r.device)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 16)
+              and out.is_contiguous() and out.device == r.device):
+        raise RadianceError("ResolveMaterialsTorch: out must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device")
+    torch.cuda.current_stream(r.device).synchronize()
+    invalid = 0
+    if n:
+        rays = WrapDeviceMemory(None, r.data_ptr(), n * 32, keepalive=r)
+        hits = WrapDeviceMemory(None, h.data_ptr(), n * 32, keepalive=h)
+        dst = WrapDeviceMemory(None, out.data_ptr(), n * 64, keepalive=out)
+        _, invalid = ResolveMaterials(tlas, rays, hits, n, scene_buffers, dst)
+    return out, invalid
+
+
+def LightHitsTorch(rays_t, materials_t, scene_buffer, light, want_shadow=True):
+    """Extension: LightHits on CUDA tensors -- rays a contiguous float32 (n, 8) tensor, materials the contiguous float32 (n, 16)
+    tensor ResolveMaterialsTorch returned for them (or the caller's own records), scene_buffer the Buffer of descriptor slot 4.
+    Returns (lit, shadow): lit float32 (n, 4) (rgb, 0), shadow float32 (n, 8) -- the rays QueryRaysTorch(..., QUERY_ANY) takes --
+    or None without want_shadow.  The library cannot see torch's stream, so the current stream is synchronised first; the call
+    blocks."""
+    import torch
+    r, m = rays_t, materials_t
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
+        raise RadianceError("LightHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(r.shape[0])
+    if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float32 and tuple(m.shape) == (n, 16) and m.is_contiguous()
+            and m.device == r.device):
+        raise RadianceError("LightHitsTorch: materials must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device")
+    if not isinstance(scene_buffer, Buffer):
+        raise RadianceError("LightHitsTorch: scene_buffer must be a Buffer (the SceneProperties of descriptor slot 4)")
+    light = int(light)
+    if not 0 <= light < MAX_LIGHTS:
+        raise RadianceError("LightHitsTorch: light %d is not one of the %d lights of a SceneProperties (0 .. %d)" % (light, MAX_LIGHTS, MAX_LIGHTS - 1))
+    lit = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device) if want_shadow else None
+    torch.cuda.current_stream(r.device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+        LightHits(wrap(r, 32), wrap(m, 64), n, scene_buffer, light, wrap(lit, 16), wrap(shadow, 32))
+    return lit, shadow
+
+
 # ---- the two ends of a frame on device memory (rdx_generate_rays, rdx_accumulate) ---------------------------------------
 RAYGEN_SEED_DTYPE = np.dtype([("in", "<u4", 3), ("_0", "<u4")])
 assert RAYGEN_SEED_DTYPE.itemsize == C.sizeof(_lib.rdx_raygen_seed) == 16
