@@ -25,6 +25,13 @@ Second entry point (leaves the files above alone):
     python tests/golden/make_golden_gpu.py rayedges [DIR]     # on the MI355X; writes DIR/refgpu_rayedges.npz
     cp DIR/refgpu_rayedges.npz tests/golden/                   # (DIR defaults to the folder the files above are written to, OUT)
 
+Third entry point:
+
+    python tests/golden/make_golden_gpu.py shadeedges [DIR]   # on the MI355X; writes DIR/refgpu_shade_edges.npz
+
+refgpu_shade_edges.npz  the reference's `material`, microfacetBRDF, raygen (frames, the tone map alone at batchSize 0, the running
+                      mean alone at depth 0) and generateRay on the edge inputs of tests/shade_edge_cases.py (layout: there).
+
 refgpu_rayedges.npz   the reference's intersectTop beyond the stock ray interval and unit directions: every cell of
                       tests/ray_edge_cases.py (scene x family x interval), closest hit (sbt 1: full HitData) and any hit
                       (sbt 2: flags), plus the inputs that depend on the reference's own answers.  Layout: ray_edge_cases.py
@@ -141,8 +148,19 @@ def rayedges(out_dir=OUT):
     print("refgpu_rayedges.npz: %d bytes" % os.path.getsize(path), flush=True)
 
 
+def shadeedges(out_dir=OUT):
+    import shade_edge_cases as se
+    os.makedirs(out_dir, exist_ok=True)
+    out = se.reference_recordings(rg.RefGpu("p"), rg, rd, scenes)
+    path = os.path.join(out_dir, "refgpu_shade_edges.npz")
+    save_npz_reproducibly(path, out)
+    print("refgpu_shade_edges.npz: %d arrays, %d bytes" % (len(out), os.path.getsize(path)), flush=True)
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["rayedges"]:
         rayedges(*[os.path.abspath(a) for a in sys.argv[2:3]])
+    elif sys.argv[1:2] == ["shadeedges"]:
+        shadeedges(*[os.path.abspath(a) for a in sys.argv[2:3]])
     else:
         main()

@@ -215,12 +215,31 @@ class RefScene:
     def frame(self, local=64):
         """one host frame like sample1.cpp:447-498: raygen over all pixels, then totalSamples += batchSize.
         The reference launches with local_work_size 1 (radiance.cpp:250-259); results do not depend on it."""
-        n = self.width * self.height
-        ms = self.ref.launch("k_ref_raygen", [self.rtprop, self.scratch, self.image, self.cam, self.props, self.meshInfo,
-                                              self.vertex, self.index, self.uv, self.normal, self.material, self.tlas,
-                                              np.uint32(n)], n, local)
+        ms = self.raygen(local)
         self.set_rtprop(totalSamples=int(self.rtprop_host[0]["totalSamples"]) + int(self.rtprop_host[0]["batchSize"]))
         return ms
+
+    def raygen(self, local=64):
+        """the raygen kernel over all pixels with RTProp as it stands (no host bookkeeping after it)"""
+        n = self.width * self.height
+        return self.ref.launch("k_ref_raygen", [self.rtprop, self.scratch, self.image, self.cam, self.props, self.meshInfo,
+                                                self.vertex, self.index, self.uv, self.normal, self.material, self.tlas,
+                                                np.uint32(n)], n, local)
+
+    def write_scratch(self, values):
+        """prefill imageScratch (width * height float4): with batchSize 0 a frame is the tone map alone, with depth 0 and
+        batchSize 1 the running mean of colour (0, 0, 0) alone (samples/shader.cl:197-304)"""
+        a = np.ascontiguousarray(values, np.float32).reshape(-1)
+        assert a.shape[0] == self.width * self.height * 4
+        _ck(hip().hipMemcpy(self.scratch.ptr, a.ctypes.data, a.nbytes, 1), "hipMemcpy H2D")
+
+    def set_props(self, scene_props):
+        """another SceneProperties record (the lights)"""
+        self.props = DevBuf.of(np.array(scene_props).reshape(1).view(np.uint8))
+
+    def set_camera(self, camera):
+        """another PhysicalCamera record"""
+        self.cam = DevBuf.of(np.array(camera).reshape(1).view(np.uint8))
 
     def read_scratch(self):
         return self.scratch.read(np.float32, self.width * self.height * 4)
