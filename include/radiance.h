@@ -211,6 +211,23 @@ inline void LightHits(Platform*, Buffer rays, Buffer materials, uint32_t n, Buff
     if (rdx_light_hits(rays, raysOffset, materials, materialsOffset, n, scene, light, lit, litOffset, shadow, shadowOffset)) detail::fatal("LightHits");
 }
 
+// Extension (no reference counterpart; rdx_scatter_hits): the next ray of the `n` material records `materials` (rdx_resolve_materials')
+// and surface records `surfaces` (rdx_resolve_hits') and the directions of `rays` -- the stock shader's next-direction sample, with
+// pcg3d of the rdx_shade_key records `keys` as the random numbers, or with the float4 records `randoms` (exactly one of the two is
+// nullptr).  One rdx_scatter (nextFactor, slot) per ray goes to `scatter`, the next ray of every survivor (rdx_ray, ready for
+// rdx_query_rays) to `next`; with `src` (may be nullptr) the survivors are packed and src[k] is the ray's number.  Returns the
+// number of survivors.
+inline uint32_t ScatterHits(Platform*, Buffer rays, Buffer materials, Buffer surfaces, Buffer keys, Buffer randoms, uint32_t n, Buffer scatter,
+                            Buffer next, Buffer src = nullptr, size_t raysOffset = 0, size_t materialsOffset = 0, size_t surfacesOffset = 0,
+                            size_t keysOffset = 0, size_t randomsOffset = 0, size_t scatterOffset = 0, size_t nextOffset = 0, size_t srcOffset = 0)
+{
+    uint32_t live = 0;
+    if (rdx_scatter_hits(rays, raysOffset, materials, materialsOffset, surfaces, surfacesOffset, keys, keysOffset, randoms, randomsOffset, n,
+                         scatter, scatterOffset, next, nextOffset, src, srcOffset, &live))
+        detail::fatal("ScatterHits");
+    return live;
+}
+
 // Extension (no reference counterpart; rdx_generate_rays): `n` camera rays of the PhysicalCamera in `camera` (the contents of
 // descriptor slot 3) as rdx_ray records in `rays`, and -- `keys` may be nullptr -- their rdx_shade_key records of depth 0; device
 // memory in and out.  Ray i is pixel firstPixel + i, or pixels[i]; its random input is pcg3d(frameID, totalSamples, pixel), or

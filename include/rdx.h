@@ -428,6 +428,44 @@ int         rdx_light_hits(rdx_buffer rays, size_t rays_offset,            /* rd
                            rdx_buffer lit, size_t lit_offset,              /* out float4 per ray: rgb, w = 0 */
                            rdx_buffer shadow, size_t shadow_offset);       /* optional out: rdx_ray per ray */
 
+/* The next ray of the hits of a ray query, on the device: the second half of the stock closest-hit shader `material`
+ * (samples/shader.cl:482-541) -- the next-direction sample sampleMicrofacetBRDF_transm (pbr.cl:289-385), nextFactor and the choice
+ * between the two offset origins -- on the records of rdx_resolve_materials and rdx_resolve_hits.  With rdx_light_hits it closes
+ * the set: a path tracer over any number of lights runs on rdx_query_rays, rdx_resolve_hits, rdx_resolve_materials, rdx_light_hits
+ * and this call alone, on the device throughout.
+ * A material record with hit == 1:  V = normalize(-ray.direction), N = record.normal, rnd = pcg3d(frameID, pixel, depth) of the key
+ * (math.cl:10-23) -- or randoms[i].xyz as they are, for a caller with a sampler of its own; nf = (0, 0, 0); nd =
+ * sampleMicrofacetBRDF_transm(V, N, albedo, metallic, roughness, transmission, ior, rnd, &nf); origin = surfaces[i].below if
+ * dot(nd, N) < 0, else materials[i].above -- operation for operation what `material` does after its light term (shader.cl:518-540),
+ * so on the records of a hit whose SBT row is `material` (instanceSBTOffset 0) nextFactor and the next ray carry the bits of
+ * rdx_shade_hits and of the frame path.  The ray SURVIVES and gets a record number k: next[k] = (origin | 0.001, nd | 1000), ready
+ * for rdx_query_rays with the reference's interval, scatter[i] = (nf, k), src[k] = i.  Any other value of `hit`: scatter[i] =
+ * (0, 0, 0, 0xffffffff), and the ray does not survive.
+ * Compaction is that of rdx_shade_hits: without `src`, k = i and record i of a ray that does not survive is 32 zero bytes in `next`
+ * (tmax = 0: such a ray accepts nothing).  With `src`, the survivors are packed into records 0 .. live - 1: the survivors among
+ * input rays 64 j .. 64 j + 63 occupy consecutive records in input order; the order of these groups among each other is
+ * unspecified and may differ from call to call; records from `live` on are left untouched.  *live_out (optional) receives the
+ * survivor count either way.
+ * Of a ray only the direction is read, of a surface record only `below`.  The kernel gathers nothing, so no record can make it read
+ * outside a buffer; records the caller filled in itself are equally allowed.  It takes no TLAS and no scene buffers.  Nothing is
+ * staged and nothing is allocated per call; the call blocks, and runs on logical device 0 in multi-device mode.
+ * rdx_get_trace_stats().ms_shade is the kernel time of the call.  Refused, before anything is launched: an uninitialised library;
+ * a NULL or unknown handle among rays / materials / surfaces / scatter / next, an unknown one among keys / randoms / src; keys and
+ * randoms both NULL or both given; an offset that is not a multiple of 16 (4 for src); a range that does not hold n records (32 n
+ * for rays / next, 64 n for materials / surfaces, 16 n for keys / randoms / scatter, 4 n for src: the worst case); an output range
+ * that overlaps an input range or another output range; wrapped memory that is misaligned.  n == 0 succeeds and touches nothing. */
+typedef struct rdx_scatter { float nextFactor[3]; uint32_t slot; } rdx_scatter;   /* 16 B: payload.nextFactor | record number of the next ray in `next`, 0xffffffff = none */
+int         rdx_scatter_hits(rdx_buffer rays, size_t rays_offset,            /* rdx_ray per record: only the direction is read */
+                             rdx_buffer materials, size_t materials_offset,  /* rdx_material_record per ray */
+                             rdx_buffer surfaces, size_t surfaces_offset,    /* rdx_surface per ray: only `below` is read */
+                             rdx_buffer keys, size_t keys_offset,            /* rdx_shade_key per ray, or NULL when `randoms` is given */
+                             rdx_buffer randoms, size_t randoms_offset,      /* optional float4 per ray: xyz take the place of pcg3d(key), w ignored */
+                             uint32_t n,
+                             rdx_buffer scatter, size_t scatter_offset,      /* out: rdx_scatter per ray */
+                             rdx_buffer next, size_t next_offset,            /* out: rdx_ray per surviving ray */
+                             rdx_buffer src, size_t src_offset,              /* optional uint32 per survivor: switches compaction on */
+                             uint32_t* live_out);                            /* optional */
+
 /* The two ends of a frame, on the device: the camera rays a loop over rdx_query_rays / rdx_shade_hits starts from, and the step
  * that folds its finished samples into the frame rdx_trace_rays would have written.
  * rdx_generate_rays: ray i is generateRay (samples/shader.cl:111-173) for pixel_i = pixels ? pixels[i] : first_pixel + i, with

@@ -94,6 +94,10 @@ class rdx_material_record(C.Structure):
                 ("above", C.c_float * 3), ("_0", C.c_uint32)]
 
 
+class rdx_scatter(C.Structure):
+    _fields_ = [("nextFactor", C.c_float * 3), ("slot", C.c_uint32)]
+
+
 class rdx_shading_buffers(C.Structure):
     _fields_ = [("scene", C.c_void_p), ("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p),
                 ("material", C.c_void_p), ("textureArray", C.c_void_p), ("sampler", C.c_void_p)]
@@ -168,6 +172,9 @@ SIGNATURES = {
                                         C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "rdx_light_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
                                  C.c_void_p, C.c_size_t]),
+    "rdx_scatter_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                   C.POINTER(C.c_uint32)]),
     "rdx_generate_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                     C.c_float, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "rdx_accumulate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p,

@@ -38,6 +38,7 @@
 #include "device_math.h"
 #include "kernels.h"
 #include "material_eval.h"
+#include "scatter.h"
 #include "paths.h"
 #include "raygen.h"
 #include "rdx_types.h"
@@ -2508,6 +2509,70 @@ extern "C" int rdx_light_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer ma
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(g.stream));
     for (rdx_buffer b : {lit, shadow}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
+    return 0;
+}
+
+// The next-direction sample of `material` on material and surface records (scatter.hip).  No TLAS and no scene buffers: the kernel
+// reads the rays' directions, the records and one key or one float4 of randoms per ray, so the checks are those of the ranges
+// alone.  *live is the counter word of rdx_shade_hits
+extern "C" int rdx_scatter_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer materials, size_t materials_offset, rdx_buffer surfaces,
+                                size_t surfaces_offset, rdx_buffer keys, size_t keys_offset, rdx_buffer randoms, size_t randoms_offset, uint32_t n,
+                                rdx_buffer scatter, size_t scatter_offset, rdx_buffer next, size_t next_offset, rdx_buffer src, size_t src_offset,
+                                uint32_t* live_out)
+{
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!rays || !known_buffer(rays)) return fail("rdx_scatter_hits: invalid ray buffer handle");
+    if (!materials || !known_buffer(materials)) return fail("rdx_scatter_hits: invalid material-record buffer handle");
+    if (!surfaces || !known_buffer(surfaces)) return fail("rdx_scatter_hits: invalid surface-record buffer handle");
+    if (!scatter || !known_buffer(scatter)) return fail("rdx_scatter_hits: invalid scatter buffer handle");
+    if (!next || !known_buffer(next)) return fail("rdx_scatter_hits: invalid next-ray buffer handle");
+    if (keys && !known_buffer(keys)) return fail("rdx_scatter_hits: invalid key buffer handle");
+    if (randoms && !known_buffer(randoms)) return fail("rdx_scatter_hits: invalid randoms buffer handle");
+    if (src && !known_buffer(src)) return fail("rdx_scatter_hits: invalid src buffer handle");
+    if (!keys && !randoms) return fail("rdx_scatter_hits: neither keys nor randoms given: one of the two is required");
+    if (keys && randoms) return fail("rdx_scatter_hits: both keys and randoms given: only one of the two is allowed");
+    static_assert(sizeof(rdx_scatter) == 16 && sizeof(rdx_material_record) == 64 && sizeof(rdx_surface) == 64, "one float4 per scatter record");
+    // every range the kernel touches: {buffer, offset, bytes per record, name, alignment}; the first five are read, the others written
+    struct Range { rdx_buffer b; size_t off, rec; const char* name; uint32_t align; };
+    const Range R[8] = {{rays, rays_offset, sizeof(rdx_ray), "ray", 16u}, {materials, materials_offset, sizeof(rdx_material_record), "material-record", 16u},
+                        {surfaces, surfaces_offset, sizeof(rdx_surface), "surface-record", 16u}, {keys, keys_offset, sizeof(rdx_shade_key), "key", 16u},
+                        {randoms, randoms_offset, 4 * sizeof(float), "randoms", 16u}, {scatter, scatter_offset, sizeof(rdx_scatter), "scatter", 16u},
+                        {next, next_offset, sizeof(rdx_ray), "next-ray", 16u}, {src, src_offset, sizeof(uint32_t), "src", 4u}};
+    for (const Range& r : R)
+        if (r.b && (r.off & (r.align - 1u)))
+            return fail("rdx_scatter_hits: offsets must be multiples of 16 bytes, 4 for src (%s offset %zu)", r.name, r.off);
+    for (const Range& r : R)
+        if (r.b && (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off))
+            return fail("rdx_scatter_hits: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
+    if (live_out) *live_out = 0;
+    if (!n) return 0;
+    for (const Range& r : R)
+        if (r.b && (reinterpret_cast<uintptr_t>(r.b->dptr) & (r.align - 1u)))
+            return fail("rdx_scatter_hits: wrapped device memory must be %u-byte aligned (%s buffer)", r.align, r.name);
+    // no output range may overlap an input range or another output range, in one buffer or in several that wrap the same memory
+    for (int o = 5; o < 8; ++o)
+        for (int k = 0; k < o; ++k) {
+            if (!R[o].b || !R[k].b) continue;
+            const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[o].b->dptr) + R[o].off, a1 = a0 + (size_t)n * R[o].rec,
+                            b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
+            if (a0 < b1 && b0 < a1) return fail("rdx_scatter_hits: the %s range and the %s range overlap", R[o].name, R[k].name);
+        }
+    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
+    HIP_OK(hipMemsetAsync(g.dShadeCounts, 0, sizeof(uint32_t), g.stream));
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    launch_scatter_hits(g.stream, reinterpret_cast<const float4*>(at(rays, rays_offset)), reinterpret_cast<const float4*>(at(materials, materials_offset)),
+                        reinterpret_cast<const float4*>(at(surfaces, surfaces_offset)), reinterpret_cast<const uint4*>(at(keys, keys_offset)),
+                        reinterpret_cast<const float4*>(at(randoms, randoms_offset)), n, reinterpret_cast<float4*>(at(scatter, scatter_offset)),
+                        reinterpret_cast<float4*>(at(next, next_offset)), reinterpret_cast<uint32_t*>(at(src, src_offset)), g.dShadeCounts);
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    for (rdx_buffer b : {scatter, next, src}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    uint32_t live = 0;
+    HIP_OK(hipMemcpy(&live, g.dShadeCounts, sizeof live, hipMemcpyDeviceToHost));
+    if (live_out) *live_out = live;
     std::memset(&g.stats, 0, sizeof g.stats);
     HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
     return 0;

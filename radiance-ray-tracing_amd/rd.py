@@ -796,6 +796,90 @@ def LightHitsTorch(rays_t, materials_t, scene_buffer, light, want_shadow=True):
     return lit, shadow
 
 
+# ---- the next ray of a query's hits from material and surface records (rdx_scatter_hits) --------------------------------
+SCATTER_DTYPE = np.dtype([("nextFactor", "<f4", 3), ("slot", "<u4")])
+assert SCATTER_DTYPE.itemsize == C.sizeof(_lib.rdx_scatter) == 16
+
+
+def ScatterHits(rays, materials, surfaces, keys, n, randoms=None, scatter=None, next=None, src=None, compact=False, rays_offset=0,
+                materials_offset=0, surfaces_offset=0, keys_offset=0, randoms_offset=0, scatter_offset=0, next_offset=0, src_offset=0):
+    """Extension: the next ray of the `n` MATERIAL_RECORD_DTYPE records of `materials` (ResolveMaterials', or the caller's own), the
+    SURFACE_DTYPE records of `surfaces` (ResolveHits': only `below` is read) and the directions of `rays` -- the stock closest-hit
+    shader's next-direction sample, nextFactor and choice of the offset origin.  The random numbers are pcg3d of the
+    SHADE_KEY_DTYPE records of `keys` (frameID, pixel, depth), or -- keys None -- the float4 records of `randoms` (xyz as they
+    are, w ignored): exactly one of the two is given.  One SCATTER_DTYPE record per ray goes to `scatter`: `nextFactor`, and
+    `slot` = the record number k of the ray's next ray in `next` (RAY_DTYPE records, ready for QueryRays), NO_SLOT for a record
+    whose `hit` is not 1.  scatter / next: a Buffer, or None (created).  src: a Buffer, or None -- then compact=True creates it.
+    With `src`, the survivors are packed into records 0 .. live - 1 (those of 64 consecutive input rays contiguous and in input
+    order, the groups in no fixed order), src[k] = the ray's number, and records from `live` on are untouched; without, k = i
+    and the record of a ray that does not survive is zeros.  Returns (scatter, next, src, live)."""
+    if not all(isinstance(b, Buffer) for b in (rays, materials, surfaces)):
+        raise RadianceError("ScatterHits: rays, materials and surfaces must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    for what, b in (("keys", keys), ("randoms", randoms)):
+        if b is not None and not isinstance(b, Buffer):
+            raise RadianceError("ScatterHits: %s must be a Buffer or None" % what)
+    if keys is None and randoms is None:
+        raise RadianceError("ScatterHits: neither keys nor randoms given: one of the two is required")
+    if keys is not None and randoms is not None:
+        raise RadianceError("ScatterHits: both keys and randoms given: only one of the two is allowed")
+    n = int(n)
+
+    def out(buf, offset, rec, what, optional):
+        if buf is True or (buf is None and not optional):
+            return CreateBuffer(None, max(int(offset) + rec * n, 1))
+        if buf is None or buf is False:
+            return None
+        if not isinstance(buf, Buffer):
+            raise RadianceError("ScatterHits: %s must be a Buffer or None" % what)
+        return buf
+    scatter = out(scatter, scatter_offset, SCATTER_DTYPE.itemsize, "scatter", False)
+    next = out(next, next_offset, RAY_DTYPE.itemsize, "next", False)
+    src = out(True if (src is None and compact) else src, src_offset, 4, "src", True)
+    live = C.c_uint32(0)
+    h = lambda b: b.handle if b is not None else None
+    _check(_lib.lib().rdx_scatter_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), surfaces.handle, int(surfaces_offset),
+                                       h(keys), int(keys_offset), h(randoms), int(randoms_offset), n, scatter.handle, int(scatter_offset),
+                                       next.handle, int(next_offset), h(src), int(src_offset), C.byref(live)))
+    return scatter, next, src, int(live.value)
+
+
+def ScatterHitsTorch(rays_t, materials_t, surfaces_t, keys_t=None, randoms_t=None, compact=True):
+    """Extension: ScatterHits on CUDA tensors -- rays a contiguous float32 (n, 8) tensor, materials / surfaces the contiguous float32
+    (n, 16) tensors ResolveMaterialsTorch / ResolveHitsTorch returned for them (or the caller's own records), and exactly one of
+    keys, a contiguous int32 (n, 4) tensor (frameID, pixel, depth, 0), and randoms, a contiguous float32 (n, 4) tensor (xyz used).
+    Returns (scatter, next, src, live): scatter float32 (n, 4) (nextFactor; `.view(torch.int32)` shows slot in column 3), next
+    float32 (live, 8) when compacting -- already sliced to the survivors -- else (n, 8), src int32 (live,) or None.  The library
+    cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
+    import torch
+    r, m, s, k, u = rays_t, materials_t, surfaces_t, keys_t, randoms_t
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
+        raise RadianceError("ScatterHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(r.shape[0])
+    for what, t in (("materials", m), ("surfaces", s)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (n, 16) and t.is_contiguous()
+                and t.device == r.device):
+            raise RadianceError("ScatterHitsTorch: %s must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device" % what)
+    if (k is None) == (u is None):
+        raise RadianceError("ScatterHitsTorch: exactly one of keys and randoms must be given")
+    if k is not None and not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
+                              and k.device == r.device):
+        raise RadianceError("ScatterHitsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
+    if u is not None and not (isinstance(u, torch.Tensor) and u.is_cuda and u.dtype == torch.float32 and tuple(u.shape) == (n, 4) and u.is_contiguous()
+                              and u.device == r.device):
+        raise RadianceError("ScatterHitsTorch: randoms must be a contiguous float32 CUDA tensor of shape (n, 4) on the rays' device")
+    scatter = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    nxt = torch.empty((n, 8), dtype=torch.float32, device=r.device)
+    src = torch.empty((n,), dtype=torch.int32, device=r.device) if compact else None
+    torch.cuda.current_stream(r.device).synchronize()
+    live = 0
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+        _, _, _, live = ScatterHits(wrap(r, 32), wrap(m, 64), wrap(s, 64), wrap(k, 16), n, wrap(u, 16), wrap(scatter, 16), wrap(nxt, 32), wrap(src, 4))
+    if compact:
+        nxt, src = nxt[:live], src[:live]
+    return scatter, nxt, src, live
+
+
 # ---- the two ends of a frame on device memory (rdx_generate_rays, rdx_accumulate) ---------------------------------------
 RAYGEN_SEED_DTYPE = np.dtype([("in", "<u4", 3), ("_0", "<u4")])
 assert RAYGEN_SEED_DTYPE.itemsize == C.sizeof(_lib.rdx_raygen_seed) == 16
