@@ -267,6 +267,20 @@ inline void TracePaths(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffe
         detail::fatal("TracePaths");
 }
 
+// Extension (no reference counterpart; rdx_trace_paths_lights): TracePaths with every one of the first `lightCount` (0 .. 5)
+// directional lights of the scene's SceneProperties sampled at every hit -- the path tracer over ResolveHits / ResolveMaterials /
+// LightHits / ScatterHits in one call, device memory in and out.  Gathers checked: returns the number of hits that `scene` does not
+// describe (they count as misses).  With lightCount 1 the result has the bits of TracePaths (rdx.h).
+inline uint32_t TraceLightPaths(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer keys, uint32_t n, uint32_t maxDepth, uint32_t lightCount,
+                                const rdx_shading_buffers& scene, Buffer radiance, size_t raysOffset = 0, size_t keysOffset = 0,
+                                size_t radianceOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_trace_paths_lights(accelStruct, rays, raysOffset, keys, keysOffset, n, maxDepth, lightCount, &scene, radiance, radianceOffset, &invalid))
+        detail::fatal("TraceLightPaths");
+    return invalid;
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

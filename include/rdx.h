@@ -558,6 +558,54 @@ int         rdx_trace_paths(rdx_buffer tlas,
                             rdx_buffer radiance, size_t radiance_offset,  /* out: float4 per path: rgb, w = 0 */
                             rdx_buffer hits, size_t hits_offset);         /* optional out: rdx_ray_hit of the first segment */
 
+/* Radiance along `n` rays of the caller's own with EVERY directional light of the scene sampled at every hit -- the reference's
+ * closest-hit shader ends its light term with "TODO: support multiple lights" (samples/shader.cl:504) and reads lights[0] only, as
+ * do rdx_trace_rays, rdx_shade_hits and rdx_trace_paths.  Rays and keys as for rdx_trace_paths; light_count (0 .. 5) lights,
+ * lights[0 .. light_count - 1] of the SceneProperties in scene->scene, are read ON THE DEVICE by every call (SceneProperties.
+ * lightCount is not consulted, as no other call consults it).  radiance[i].rgb is `color` of the path tracer over the public calls
+ * shown in the README (its second loop), bit for bit, run on ray i, key i, max_depth and light_count; radiance[i].w is 0.  Each
+ * float32 operation is rounded on its own.  Per live ray at depth d:
+ *   query   a closest-hit query under the ray's own interval (the rule of rdx_query_rays): the first segment carries the caller's
+ *           tmin / tmax, every later one the 0.001 / 1000 of rdx_scatter_hits;
+ *   miss    a record whose `hit` is not 1, or a hit the bounds rule rejects (below): at depth 0 the colour becomes the stock miss
+ *           colour (0.2, 0.2, 0.5); at a later depth the path ends with the colour it has;
+ *   hit     the material record is that of rdx_resolve_materials, `below` that of rdx_resolve_hits; direct = (0, 0, 0); for j = 0 ..
+ *           light_count - 1 in this order: lit_j and its shadow ray are those of rdx_light_hits for light j, the shadow ray is
+ *           answered by an RDX_QUERY_ANY query, direct = direct + (occluded ? 0 : lit_j); radiance = direct + albedo * 0.1f;
+ *           color = color + weight * radiance; weight = weight * nextFactor, with nextFactor and the next ray those of
+ *           rdx_scatter_hits under the key (frameID, pixel, d).
+ * max_depth == 0 gives zeros; at the last depth no next ray is sampled or traced (no result depends on it).  light_count == 0 is
+ * valid and leaves the ambient term.  Two consequences:
+ *   - for light_count == 1 the result has the bits of rdx_trace_paths, and of the frames rdx_trace_rays writes (generate ->
+ *     trace_paths_lights(1) -> accumulate), in scenes without instance SBT offsets;
+ *   - with instance SBT offsets the call follows the README's loop: RDX_QUERY_ANY reports `hit` alone, so a shadow ray that meets
+ *     an instance whose row instanceSBTOffset + 2 has no hit shader still occludes.  That is the difference rdx_trace_paths
+ *     documents, from the other side.
+ * FENCED: unlike rdx_trace_paths this call gathers checked.  Every hit passes the bounds rule of rdx_shade_hits / rdx_resolve_
+ * materials (csrc/shade.h shade_in_bounds, asked before and after the index gather) and must name an instance the TLAS carries, so
+ * `scene` buffers that do not describe the scene of `tlas` cannot make a kernel read outside a buffer: such a hit is a miss and is
+ * counted in *invalid_out (optional).  Textures follow the rule of rdx_shade_hits (option "textures" 1 and a textureArray; uv
+ * required then).  User closest-hit programs do not run here; point and area lights do not exist; one device.
+ * Nothing is staged through the host: the library reads back ONE 32-bit word per bounce, the survivors' count that sizes the next
+ * launches.  Internal streams of 192 + 80 light_count bytes per path of a chunk grow on first use and are reused.  More than
+ * "chunk_paths" paths are traced in chunks of that many.  The call blocks, derives the traversal layout if none exists yet, sees
+ * the transforms of the last rdx_tlas_update, and runs on logical device 0 in multi-device mode.  The engine options ("kernel",
+ * "cull", "quad", "group_instances", "group_entry_items", "unified_tree", "top_flat", "inline_leaf_roots") apply as in
+ * rdx_query_rays; no result depends on them.  rdx_get_trace_stats: pixels = n, rays_primary = n, rays_bounce = the live rays of the
+ * depths >= 1, closest_hits = the valid hits, rays_shadow = light_count x closest_hits, launches_extend / launches_shadow = the
+ * closest-hit / any-hit launches, ms_total; with rdx_set_profiling ms_extend / ms_shadow = those launches and ms_shade = the two
+ * kernels of this call.  rdx_get_bounce_counts: out[0] = n, out[d + 1] = the survivors of depth d.
+ * Refused, before anything is launched: everything rdx_trace_paths refuses (`hits` aside); light_count > 5; max_depth > 62; a
+ * radiance range that overlaps the SceneProperties.  n == 0 succeeds and touches nothing; records from n on are never written. */
+int         rdx_trace_paths_lights(rdx_buffer tlas,
+                                   rdx_buffer rays, size_t rays_offset,          /* rdx_ray per path: the first segment, with ITS tmin / tmax */
+                                   rdx_buffer keys, size_t keys_offset,          /* rdx_shade_key per path: frameID, pixel (depth, _0 ignored) */
+                                   uint32_t n, uint32_t max_depth,               /* 0 .. 62 */
+                                   uint32_t light_count,                         /* 0 .. 5: lights[0 .. light_count - 1] of the SceneProperties */
+                                   const rdx_shading_buffers* scene,             /* slots 4, 5, 7, 8, 9, 10, 11, 12 as for rdx_shade_hits */
+                                   rdx_buffer radiance, size_t radiance_offset,  /* out: float4 per path: rgb, w = 0 */
+                                   uint32_t* invalid_out);                       /* optional */
+
 /* Test seams: run single stages on caller-supplied batches (device or host pointers are NOT
  * accepted -- plain host arrays in, host arrays out; the library stages them through HBM). */
 typedef struct rdx_hit {

@@ -181,6 +181,8 @@ SIGNATURES = {
                                  C.c_uint32, C.POINTER(C.c_uint32)]),
     "rdx_trace_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(rdx_shading_buffers),
                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rdx_trace_paths_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),
     "rdx_trace_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int,

@@ -37,6 +37,7 @@
 #include "bvh_build.h"
 #include "device_math.h"
 #include "kernels.h"
+#include "light_paths.h"
 #include "material_eval.h"
 #include "scatter.h"
 #include "paths.h"
@@ -159,6 +160,8 @@ struct Context {
     uint32_t* dAccumInvalid = nullptr;      // rdx_accumulate: samples whose pixel number is outside the frame, one word
     float4* pathHits = nullptr;             // rdx_trace_paths without `hits`: the first segment's records of one chunk (2 float4 per path)
     size_t pathHitsCap = 0;
+    char* lightScratch = nullptr;           // rdx_trace_paths_lights: the streams of one chunk (light_paths.h LightPathStreams), one allocation
+    size_t lightScratchCap = 0;             // ... its size in bytes
     unsigned long long* hVisit = nullptr;   // pinned
     // everything rdx_set_option / rdx_set_profiling write, except the builder's knobs below: handed to the other devices'
     // contexts as a whole (rdx_trace_rays)
@@ -632,6 +635,8 @@ static void release_device_state()
     g.dAccumInvalid = nullptr;
     if (g.pathHits) HIP_IGN(hipFree(g.pathHits));
     g.pathHits = nullptr; g.pathHitsCap = 0;
+    if (g.lightScratch) HIP_IGN(hipFree(g.lightScratch));
+    g.lightScratch = nullptr; g.lightScratchCap = 0;
     HIP_IGN(hipEventDestroy(g.evA)); HIP_IGN(hipEventDestroy(g.evB)); HIP_IGN(hipEventDestroy(g.evChunk));
     HIP_IGN(hipStreamDestroy(g.stream));
 }
@@ -2779,6 +2784,151 @@ extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_off
     HIP_OK(hipStreamSynchronize(g.stream));
     for (rdx_buffer b : {radiance, hits}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
     if (take_status()) return fail("rdx_trace_paths: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
+    HIP_OK(hipEventElapsedTime(&g.stats.ms_total, g.evA, g.evB));
+    g_timer.resolve();
+    return 0;
+}
+
+// Radiance along the caller's own rays with every light of the scene sampled at every hit (include/rdx.h; light_paths.hip).  Per
+// chunk of "chunk_paths" paths and per depth: launch_query_rays (closest) -> k_lights_shade -> launch_query_rays (any) on the live x L
+// shadow rays, one contiguous range -> k_lights_fold.  launch_query_rays sizes its grid on the host, so ONE word -- the survivors
+// of the depth -- is read back per bounce; nothing else passes through the host.  The chunk's streams are one allocation that
+// grows on first use and is reused: 192 + 80 L bytes per path.
+extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
+                                      uint32_t max_depth, uint32_t light_count, const rdx_shading_buffers* scene, rdx_buffer radiance,
+                                      size_t radiance_offset, uint32_t* invalid_out)
+{
+    const char* who = "rdx_trace_paths_lights";
+    if (!g.initialized) return fail("rdx_trace_paths_lights: rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_lights: invalid TLAS handle");
+    if (!rays || !known_buffer(rays)) return fail("rdx_trace_paths_lights: invalid ray buffer handle");
+    if (!keys || !known_buffer(keys)) return fail("rdx_trace_paths_lights: invalid key buffer handle");
+    if (!radiance || !known_buffer(radiance)) return fail("rdx_trace_paths_lights: invalid radiance buffer handle");
+    uint32_t samplerBits = 0;
+    if (check_shading_handles(who, scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths_lights: depth %u exceeds the supported maximum of 62", max_depth);
+    if (light_count > 5) return fail("rdx_trace_paths_lights: light_count %u exceeds the 5 lights of a SceneProperties", light_count);
+    static_assert(sizeof(((SceneProperties*)nullptr)->lights) == 5 * sizeof(DirLight), "five DirLights");
+    const FrameRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16},
+                             {scene->scene, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4},
+                             {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16}};
+    if (check_frame_ranges(who, R, 4, 3, n)) return -1;
+    if (invalid_out) *invalid_out = 0;
+    if (!n) return 0;
+    if (check_shading_alignment(who, scene)) return -1;
+    ShadeScene sc{};
+    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
+    sc.s.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.s.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
+    sc.s.index = static_cast<const uint32_t*>(scene->index->dptr); sc.s.nIndex = scene->index->size / sizeof(uint32_t);
+    sc.s.normal = static_cast<const float*>(scene->normal->dptr); sc.s.nNormal = scene->normal->size / sizeof(float);
+    sc.materials = static_cast<const Material*>(scene->material->dptr); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
+    if (shading_textures(who, scene, samplerBits, sc.tex)) return -1;
+    if (sc.tex.flags & TEX_ENABLED) { sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float); }
+    if (derive_accel(tlas)) return -1;
+    const AccelCache& ac = *acc(tlas);
+    const DirLight* lights = sc.scene->lights;       // a device address: read by the kernels of every call
+
+    const uint32_t L = light_count;
+    // a chunk's shadow rays are one launch_query_rays range, whose count is 32 bits
+    const uint32_t chunk = (uint32_t)std::min<int64_t>(std::min<int64_t>(n, g.opt.chunkPaths), 0xffffffffll / std::max<uint32_t>(L, 1u));
+    Context::Group& G = g.groups[0];
+    // the chunk's streams, each a multiple of 256 bytes: hits 32 | rays x 2 64 | ids x 2 32 | weight x 2 32 | foldF 16 | foldA 16 |
+    // lit 16 L | shadow 32 L | any 32 L
+    const size_t c256 = ((size_t)chunk + 15) & ~(size_t)15;
+    if (max_depth) {
+        const size_t need = c256 * (192 + 80 * (size_t)L);
+        if (g.lightScratchCap < need) {
+            if (g.lightScratch) HIP_IGN(hipFree(g.lightScratch));
+            g.lightScratch = nullptr; g.lightScratchCap = 0;
+            HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.lightScratch), need));
+            g.lightScratchCap = need;
+        }
+    }
+    char* at = g.lightScratch;
+    auto take = [&](size_t bytesPerPath) { char* p = at; at += c256 * bytesPerPath; return p; };
+    float4* sHits = reinterpret_cast<float4*>(take(32));
+    float4* sRays[2] = {reinterpret_cast<float4*>(take(32)), reinterpret_cast<float4*>(take(32))};
+    uint4* sIds[2] = {reinterpret_cast<uint4*>(take(16)), reinterpret_cast<uint4*>(take(16))};
+    float4* sWeight[2] = {reinterpret_cast<float4*>(take(16)), reinterpret_cast<float4*>(take(16))};
+    float4* sFoldF = reinterpret_cast<float4*>(take(16));
+    float4* sFoldA = reinterpret_cast<float4*>(take(16));
+    float4* sLit = reinterpret_cast<float4*>(take(16 * (size_t)L));
+    float4* sShadow = reinterpret_cast<float4*>(take(32 * (size_t)L));
+    float4* sAny = reinterpret_cast<float4*>(take(32 * (size_t)L));
+
+    const float4* dRays = reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset);
+    const uint4* dKeys = reinterpret_cast<const uint4*>(static_cast<const char*>(keys->dptr) + keys_offset);
+    float4* dRad = reinterpret_cast<float4*>(static_cast<char*>(radiance->dptr) + radiance_offset);
+
+    std::memset(&g.stats, 0, sizeof g.stats);
+    std::memset(g.bounceCounts, 0, sizeof g.bounceCounts);
+    g.stats.pixels = n;
+    g.stats.groups = 1;
+    g.visitDepth = 0;
+    set_grid_share(1);
+    const AccelView av = view_of(tlas);      // the per-ray-interval engine on the view rdx_query_rays gives it
+    HIP_OK(hipMemsetAsync(g.dShadeCounts, 0, 2 * sizeof(uint32_t), g.stream));
+    HIP_OK(hipEventRecord(g.evA, g.stream));
+    for (uint32_t c0 = 0; c0 < n; c0 += chunk) {
+        const uint32_t m = std::min(chunk, n - c0);
+        if (max_depth == 0) {       // no segment is traced: colour 0 for every path
+            HIP_OK(hipMemsetAsync(dRad + c0, 0, (size_t)m * sizeof(float4), g.stream));
+            continue;
+        }
+        // G.dCounts: [d + 1] = survivors of depth d (the compaction cursor), [64 + d] / [128 + d] = the work counters of the depth's
+        // closest-hit / any-hit launch, all zero before the first launch
+        std::memset(G.hCounts, 0, 256 * sizeof(uint32_t));
+        G.hCounts[0] = m;
+        HIP_OK(hipMemcpyAsync(G.dCounts, G.hCounts, 256 * sizeof(uint32_t), hipMemcpyHostToDevice, G.s0));
+        uint32_t liveRays = m;
+        g.bounceCounts[0] += m;
+        for (uint32_t d = 0; d < max_depth && liveRays; ++d) {
+            const bool last = d + 1 == max_depth;
+            LightPathStreams io{};
+            io.rays = d == 0 ? dRays + 2 * (size_t)c0 : sRays[(d - 1) & 1u];
+            io.hits = sHits;
+            io.keys = d == 0 ? dKeys + c0 : nullptr;
+            io.ids = d == 0 ? nullptr : sIds[(d - 1) & 1u];
+            io.weight = d == 0 ? nullptr : sWeight[(d - 1) & 1u];
+            io.nIds = sIds[d & 1u]; io.nWeight = sWeight[d & 1u]; io.nRays = sRays[d & 1u];
+            io.foldF = sFoldF; io.foldA = sFoldA; io.lit = sLit; io.shadow = sShadow;
+            io.radiance = dRad + c0;
+            g_timer.begin(&g.stats.ms_extend, G.s0);
+            launch_query_rays(G.s0, av, io.rays, liveRays, RDX_QUERY_CLOSEST, sHits, G.dCounts + 64 + d);
+            g_timer.end(G.s0);
+            g.stats.launches_extend++;
+            g_timer.begin(&g.stats.ms_shade, G.s0);
+            launch_lights_shade(G.s0, ac.insts, ac.slotOf, ac.s.nInst, sc, lights, L, io, liveRays, d, !last, G.dCounts + d + 1, g.dShadeCounts + 1);
+            g_timer.end(G.s0);
+            // the one word per bounce: launch_query_rays and the fold are sized on the host
+            HIP_OK(hipMemcpyAsync(G.hCounts + d + 1, G.dCounts + d + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, G.s0));
+            HIP_OK(hipStreamSynchronize(G.s0));
+            const uint32_t survivors = G.hCounts[d + 1];
+            if (survivors > liveRays) return fail("rdx_trace_paths_lights: internal error: %u survivors of %u live rays", survivors, liveRays);
+            if (survivors && L) {
+                g_timer.begin(&g.stats.ms_shadow, G.s0);
+                launch_query_rays(G.s0, av, sShadow, survivors * L, RDX_QUERY_ANY, sAny, G.dCounts + 128 + d);
+                g_timer.end(G.s0);
+                g.stats.launches_shadow++;
+            }
+            g_timer.begin(&g.stats.ms_shade, G.s0);
+            launch_lights_fold(G.s0, sAny, L, io, survivors);
+            g_timer.end(G.s0);
+            g.bounceCounts[d + 1] += survivors;
+            if (d == 0) g.stats.rays_primary += liveRays; else g.stats.rays_bounce += liveRays;
+            g.stats.closest_hits += survivors;
+            g.stats.rays_shadow += (uint64_t)L * survivors;
+            liveRays = survivors;
+        }
+    }
+    HIP_OK(hipEventRecord(g.evB, g.stream));
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(g.stream));
+    ++radiance->version; radiance->mirrorValid = false;      // device code wrote it
+    if (take_status()) return fail("rdx_trace_paths_lights: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
+    uint32_t invalid = 0;
+    HIP_OK(hipMemcpy(&invalid, g.dShadeCounts + 1, sizeof invalid, hipMemcpyDeviceToHost));
+    if (invalid_out) *invalid_out = invalid;
     HIP_OK(hipEventElapsedTime(&g.stats.ms_total, g.evA, g.evB));
     g_timer.resolve();
     return 0;

@@ -1061,6 +1061,66 @@ def TracePathsTorch(tlas, rays_t, keys_t, max_depth, scene_buffers, want_hits=Fa
     return (radiance, hits) if want_hits else radiance
 
 
+# ---- radiance along the caller's own rays, every light of the scene sampled (rdx_trace_paths_lights) ---------------------
+def _light_count(who, light_count):
+    if isinstance(light_count, bool) or not isinstance(light_count, (int, np.integer)) or not 0 <= light_count <= 5:
+        raise RadianceError("%s: light_count must be an integer from 0 to 5 (the lights of a SceneProperties)" % who)
+    return int(light_count)
+
+
+def TraceLightPaths(tlas, rays, keys, n, max_depth, light_count, scene_buffers, radiance=None, rays_offset=0, keys_offset=0, radiance_offset=0):
+    """Extension: TracePaths with the first `light_count` (0 .. 5) directional lights of scene_buffers.scene sampled at every hit --
+    the path tracer over QueryRays / ResolveHits / ResolveMaterials / LightHits / ScatterHits (the README's second loop) in one
+    call, with its bits.  Rays and keys as for TracePaths.  The lights are read on the device by every call.  The call gathers
+    checked: a hit that scene_buffers does not describe is a miss and is counted.  radiance: a Buffer, or None (created:
+    radiance_offset + 16 n bytes).  Device buffers in and out.  Returns (radiance, invalid)."""
+    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
+        raise RadianceError("TraceLightPaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    if not isinstance(scene_buffers, ShadingBuffers):
+        try:
+            scene_buffers = ShadingBuffers(*scene_buffers)
+        except TypeError:
+            raise RadianceError("TraceLightPaths: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
+                                "[, textureArray, sampler]) tuple")
+    sb = scene_buffers._struct("TraceLightPaths")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
+            or max_depth < 0:
+        raise RadianceError("TraceLightPaths: n and max_depth must be non-negative integers")
+    light_count = _light_count("TraceLightPaths", light_count)
+    n = int(n)
+    if radiance is None:
+        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
+    elif not isinstance(radiance, Buffer):
+        raise RadianceError("TraceLightPaths: radiance must be a Buffer or None")
+    invalid = C.c_uint32(0)
+    _check(_lib.lib().rdx_trace_paths_lights(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), light_count,
+                                             C.byref(sb), radiance.handle, int(radiance_offset), C.byref(invalid)))
+    return radiance, int(invalid.value)
+
+
+def TraceLightPathsTorch(tlas, rays_t, keys_t, max_depth, light_count, scene_buffers):
+    """Extension: TraceLightPaths on CUDA tensors -- rays a contiguous float32 (n, 8) tensor, keys a contiguous int32 (n, 4) tensor, as
+    for TracePathsTorch.  Returns radiance float32 (n, 4): rgb, 0 -- what AccumulateTorch takes.  The library cannot see torch's
+    stream, so the current stream is synchronised first; the call blocks."""
+    import torch
+    r, k = rays_t, keys_t
+    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
+        raise RadianceError("TraceLightPathsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
+    n = int(r.shape[0])
+    if not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
+            and k.device == r.device):
+        raise RadianceError("TraceLightPathsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
+        raise RadianceError("TraceLightPathsTorch: max_depth must be a non-negative integer")
+    light_count = _light_count("TraceLightPathsTorch", light_count)
+    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    torch.cuda.current_stream(r.device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t)
+        TraceLightPaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, light_count, scene_buffers, wrap(radiance, 16))
+    return radiance
+
+
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
 _DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
 _DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),
