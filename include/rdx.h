@@ -606,6 +606,17 @@ int         rdx_trace_paths_lights(rdx_buffer tlas,
                                    rdx_buffer radiance, size_t radiance_offset,  /* out: float4 per path: rgb, w = 0 */
                                    uint32_t* invalid_out);                       /* optional */
 
+/* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_lights applies to the byte ranges it is given, on plain
+ * numbers (needs no device and no initialised library; no address is dereferenced) -> 0, or -1 with the refusal in
+ * rdx_last_error().  A row is one range: `bytes` at `offset` of a buffer of `size` bytes at `address`; `align` (a power of two)
+ * is the multiple required of the offset and of the address; present == 0: an optional buffer that was not given, the row is
+ * skipped.  Rows from first_out on are written: none may overlap a row before it; rows before first_out may overlap each other.
+ * Refused, in this order: an offset that is no multiple of its row's align (every row, before any size); offset > size or
+ * bytes > size - offset; then, only if n != 0: an address that is no multiple of its row's align; an overlap. */
+typedef struct rdx_debug_range { uint64_t address, size, offset, bytes; uint32_t align, present; } rdx_debug_range;
+int         rdx_debug_check_ranges(const rdx_debug_range* rows, const char* const* names, uint32_t count, uint32_t first_out,
+                                   uint32_t n);
+
 /* Test seams: run single stages on caller-supplied batches (device or host pointers are NOT
  * accepted -- plain host arrays in, host arrays out; the library stages them through HBM). */
 typedef struct rdx_hit {

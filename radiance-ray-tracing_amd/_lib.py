@@ -70,6 +70,11 @@ class rdx_surface_buffers(C.Structure):
     _fields_ = [("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class rdx_debug_range(C.Structure):
+    _fields_ = [("address", C.c_uint64), ("size", C.c_uint64), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("align", C.c_uint32),
+                ("present", C.c_uint32)]
+
+
 class rdx_surface(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("hit", C.c_uint32), ("normal", C.c_float * 3), ("materialIndex", C.c_uint32),
                 ("above", C.c_float * 3), ("u", C.c_float), ("below", C.c_float * 3), ("v", C.c_float)]
@@ -183,6 +188,7 @@ SIGNATURES = {
                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "rdx_trace_paths_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rdx_debug_check_ranges": (C.c_int, [C.POINTER(rdx_debug_range), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),
     "rdx_trace_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_int, C.c_int,

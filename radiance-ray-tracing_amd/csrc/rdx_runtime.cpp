@@ -2173,102 +2173,164 @@ extern "C" int rdx_trace_batch(rdx_buffer tlas, const float* o, const float* d, 
     return 0;
 }
 
-// Device-resident ray queries: nothing is staged through the host and nothing is allocated; the steps around the launch are those
-// of rdx_trace_batch above, in the same order
-extern "C" int rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, uint32_t n, int kind, rdx_buffer hits, size_t hits_offset)
+// ---- what every device-resident call below shares -------------------------------------------------------------------
+namespace {
+// a byte range a kernel touches, as plain numbers: {address of the buffer, its size, offset, bytes, required multiple of offset and
+// address, name, given at all}.  Nothing in the rule dereferences an address
+struct RangeRow { uintptr_t addr; size_t size, off, bytes; uint32_t align; const char* name; bool present; };
+bool ranges_overlap(const RangeRow& a, const RangeRow& b)
 {
-    if (!g.initialized) return fail("rdx_init has not been called");
-    if (!tlas || !known_buffer(tlas)) return fail("rdx_query_rays: invalid TLAS handle");
-    if (!rays || !known_buffer(rays)) return fail("rdx_query_rays: invalid ray buffer handle");
-    if (!hits || !known_buffer(hits)) return fail("rdx_query_rays: invalid hit buffer handle");
-    if (kind != RDX_QUERY_CLOSEST && kind != RDX_QUERY_ANY) return fail("rdx_query_rays: kind must be RDX_QUERY_CLOSEST (1) or RDX_QUERY_ANY (2), not %d", kind);
-    if ((rays_offset & 15u) || (hits_offset & 15u)) return fail("rdx_query_rays: offsets must be multiples of 16 bytes (rays_offset %zu, hits_offset %zu)", rays_offset, hits_offset);
-    const size_t bytes = (size_t)n * sizeof(rdx_ray);
-    static_assert(sizeof(rdx_ray) == 32 && sizeof(rdx_ray_hit) == 32, "two float4 per ray, two per record");
-    if (rays_offset > rays->size || bytes > rays->size - rays_offset)
-        return fail("rdx_query_rays: %u rays at offset %zu run past the ray buffer (%zu bytes)", n, rays_offset, rays->size);
-    if (hits_offset > hits->size || bytes > hits->size - hits_offset)
-        return fail("rdx_query_rays: %u records at offset %zu run past the hit buffer (%zu bytes)", n, hits_offset, hits->size);
+    if (!a.present || !b.present || !a.bytes || !b.bytes) return false;
+    const uintptr_t a0 = a.addr + a.off, a1 = a0 + a.bytes, b0 = b.addr + b.off, b1 = b0 + b.bytes;
+    return a0 < b1 && b0 < a1;
+}
+// The rule, in the order of its refusals: the offset of every present row, then every size (no sum that could wrap), then the
+// caller's *_out words are zeroed and n == 0 is done; then the addresses (wrapped memory), the scene streams' (streamsAligned: the
+// caller's finding), and the overlaps: outputs are R[firstOut ..], none may overlap a row before it, inputs may overlap each other
+int check_ranges(const char* who, const RangeRow* R, int count, int firstOut, uint32_t n, std::initializer_list<uint32_t*> outWords = {},
+                 bool streamsAligned = true)
+{
+    for (int k = 0; k < count; ++k)
+        if (R[k].present && (R[k].off & (R[k].align - 1u)))
+            return fail("%s: an offset must be a multiple of its range's alignment, %u for %s (offset %zu)", who, R[k].align, R[k].name, R[k].off);
+    for (int k = 0; k < count; ++k)
+        if (R[k].present && (R[k].off > R[k].size || R[k].bytes > R[k].size - R[k].off))
+            return fail("%s: %u records at offset %zu run past the %s buffer (%zu bytes)", who, n, R[k].off, R[k].name, R[k].size);
+    for (uint32_t* w : outWords) if (w) *w = 0;
     if (!n) return 0;
-    if ((reinterpret_cast<uintptr_t>(rays->dptr) & 15u) || (reinterpret_cast<uintptr_t>(hits->dptr) & 15u))
-        return fail("rdx_query_rays: wrapped device memory must be 16-byte aligned");
-    {   // the two ranges must not overlap, in one buffer or in two that wrap the same memory
-        const uintptr_t r0 = reinterpret_cast<uintptr_t>(rays->dptr) + rays_offset, h0 = reinterpret_cast<uintptr_t>(hits->dptr) + hits_offset;
-        if (r0 < h0 + bytes && h0 < r0 + bytes) return fail("rdx_query_rays: the ray range and the hit range overlap");
-    }
-    if (derive_accel(tlas)) return -1;
-    HIP_OK(hipMemsetAsync(g.dCounts + 64, 0, sizeof(uint32_t), g.stream));
-    HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_query_rays(g.stream, view_of(tlas), reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset), n, kind,
-                      reinterpret_cast<float4*>(static_cast<char*>(hits->dptr) + hits_offset), g.dCounts + 64);
-    HIP_OK(hipEventRecord(g.evB, g.stream));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(g.stream));
-    ++hits->version; hits->mirrorValid = false;      // device code wrote it
-    if (take_status()) return fail("rdx_query_rays: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_extend, g.evA, g.evB));      // kernel time of this call
+    for (int k = 0; k < count; ++k)
+        if (R[k].present && (R[k].addr & (R[k].align - 1u)))
+            return fail("%s: wrapped device memory must be %u-byte aligned (%s buffer)", who, R[k].align, R[k].name);
+    if (!streamsAligned) return fail("%s: wrapped scene streams must be 4-byte aligned", who);
+    for (int o = firstOut; o < count; ++o)
+        for (int k = 0; k < o; ++k)
+            if (ranges_overlap(R[o], R[k])) return fail("%s: the %s range and the %s range overlap", who, R[o].name, R[k].name);
     return 0;
 }
 
-// Surface records of a query's hits (surface.hip): the checks and the steps around the launch are those of rdx_query_rays
-extern "C" int rdx_resolve_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, uint32_t n,
-                                const rdx_surface_buffers* scene, rdx_buffer out, size_t out_offset, uint32_t* invalid_out)
+// a call's table: one row per range, inputs first.  required: a NULL handle is refused, else it is an absent row
+struct CallRange { rdx_buffer b; size_t off, bytes; const char* name; uint32_t align; bool required; };
+constexpr size_t WHOLE_BUFFER = ~(size_t)0;     // as `bytes`: the row spans its buffer, whatever n is
+template <int N> int check_call_handles(const char* who, const CallRange (&R)[N])
 {
-    if (!g.initialized) return fail("rdx_init has not been called");
-    if (!tlas || !known_buffer(tlas)) return fail("rdx_resolve_hits: invalid TLAS handle");
-    if (!rays || !known_buffer(rays)) return fail("rdx_resolve_hits: invalid ray buffer handle");
-    if (!hits || !known_buffer(hits)) return fail("rdx_resolve_hits: invalid hit buffer handle");
-    if (!out || !known_buffer(out)) return fail("rdx_resolve_hits: invalid output buffer handle");
-    if (!scene) return fail("rdx_resolve_hits: no scene buffers");
-    if (!scene->meshInfo || !known_buffer(scene->meshInfo)) return fail("rdx_resolve_hits: invalid meshInfo buffer handle");
-    if (!scene->index || !known_buffer(scene->index)) return fail("rdx_resolve_hits: invalid index buffer handle");
-    if (!scene->normal || !known_buffer(scene->normal)) return fail("rdx_resolve_hits: invalid normal buffer handle");
-    if (scene->uv && !known_buffer(scene->uv)) return fail("rdx_resolve_hits: invalid uv buffer handle");
-    if ((rays_offset & 15u) || (hits_offset & 15u) || (out_offset & 15u))
-        return fail("rdx_resolve_hits: offsets must be multiples of 16 bytes (rays_offset %zu, hits_offset %zu, out_offset %zu)", rays_offset, hits_offset, out_offset);
-    static_assert(sizeof(rdx_surface) == 64 && sizeof(MeshInfo) == sizeof(rdx_mesh_info), "four float4 per surface record");
-    const size_t bytes = (size_t)n * sizeof(rdx_ray), outBytes = (size_t)n * sizeof(rdx_surface);
-    if (rays_offset > rays->size || bytes > rays->size - rays_offset)
-        return fail("rdx_resolve_hits: %u rays at offset %zu run past the ray buffer (%zu bytes)", n, rays_offset, rays->size);
-    if (hits_offset > hits->size || bytes > hits->size - hits_offset)
-        return fail("rdx_resolve_hits: %u records at offset %zu run past the hit buffer (%zu bytes)", n, hits_offset, hits->size);
-    if (out_offset > out->size || outBytes > out->size - out_offset)
-        return fail("rdx_resolve_hits: %u surface records at offset %zu run past the output buffer (%zu bytes)", n, out_offset, out->size);
-    if (invalid_out) *invalid_out = 0;
-    if (!n) return 0;
-    if ((reinterpret_cast<uintptr_t>(rays->dptr) & 15u) || (reinterpret_cast<uintptr_t>(hits->dptr) & 15u) || (reinterpret_cast<uintptr_t>(out->dptr) & 15u))
-        return fail("rdx_resolve_hits: wrapped device memory must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(scene->meshInfo->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->index->dptr) & 3u) ||
-        (reinterpret_cast<uintptr_t>(scene->normal->dptr) & 3u) || (scene->uv && (reinterpret_cast<uintptr_t>(scene->uv->dptr) & 3u)))
-        return fail("rdx_resolve_hits: wrapped scene streams must be 4-byte aligned");
-    {   // the output must not overlap what the kernel reads of the rays and of the records, in one buffer or in several that wrap the same memory
-        const uintptr_t r0 = reinterpret_cast<uintptr_t>(rays->dptr) + rays_offset, h0 = reinterpret_cast<uintptr_t>(hits->dptr) + hits_offset,
-                        o0 = reinterpret_cast<uintptr_t>(out->dptr) + out_offset;
-        if (o0 < r0 + bytes && r0 < o0 + outBytes) return fail("rdx_resolve_hits: the output range and the ray range overlap");
-        if (o0 < h0 + bytes && h0 < o0 + outBytes) return fail("rdx_resolve_hits: the output range and the hit range overlap");
+    for (int optional = 0; optional < 2; ++optional)       // the required rows first
+        for (const CallRange& r : R)
+            if (r.required != (optional != 0) && (r.b ? !known_buffer(r.b) : r.required)) return fail("%s: invalid %s buffer handle", who, r.name);
+    return 0;
+}
+template <int N> int check_call_ranges(const char* who, const CallRange (&R)[N], int firstOut, uint32_t n,
+                                       std::initializer_list<uint32_t*> outWords = {}, bool streamsAligned = true)
+{
+    RangeRow rows[N];
+    for (int k = 0; k < N; ++k) {
+        const rdx_buffer b = R[k].b;
+        rows[k] = RangeRow{b ? reinterpret_cast<uintptr_t>(b->dptr) : 0, b ? b->size : 0, R[k].off, b && R[k].bytes == WHOLE_BUFFER ? b->size : R[k].bytes,
+                           R[k].align, R[k].name, b != nullptr};
     }
-    if (derive_accel(tlas)) return -1;
-    const AccelCache& ac = *acc(tlas);
-    SurfaceScene sc{};
-    sc.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
-    sc.index = static_cast<const uint32_t*>(scene->index->dptr); sc.nIndex = scene->index->size / sizeof(uint32_t);
-    sc.normal = static_cast<const float*>(scene->normal->dptr); sc.nNormal = scene->normal->size / sizeof(float);
-    if (scene->uv && scene->uv->size >= sizeof(float)) { sc.uv = static_cast<const float*>(scene->uv->dptr); sc.nUv = scene->uv->size / sizeof(float); }
-    HIP_OK(hipMemsetAsync(g.dSurfaceInvalid, 0, sizeof(uint32_t), g.stream));
+    return check_ranges(who, rows, N, firstOut, n, outWords, streamsAligned);
+}
+
+template <class T> T* at(rdx_buffer b, size_t off = 0) { return b ? reinterpret_cast<T*>(static_cast<char*>(b->dptr) + off) : nullptr; }
+bool aligned4(rdx_buffer b) { return !b || !(reinterpret_cast<uintptr_t>(b->dptr) & 3u); }
+void mark_written(std::initializer_list<rdx_buffer> outs)      // device code wrote them
+{
+    for (rdx_buffer b : outs) if (b) { ++b->version; b->mirrorValid = false; }
+}
+// one launch on g.stream between the two events, waited for; its kernel time is the one figure of g.stats.  Counters are cleared
+// before it and read back after it by the caller
+template <class Launch> int timed_launch(float rdx_trace_stats::* ms, std::initializer_list<rdx_buffer> outs, Launch&& launch)
+{
     HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_resolve_hits(g.stream, ac.insts, ac.slotOf, ac.s.nInst, reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset),
-                        reinterpret_cast<const float4*>(static_cast<const char*>(hits->dptr) + hits_offset), n, sc,
-                        reinterpret_cast<float4*>(static_cast<char*>(out->dptr) + out_offset), g.dSurfaceInvalid);
+    launch();
     HIP_OK(hipEventRecord(g.evB, g.stream));
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(g.stream));
-    ++out->version; out->mirrorValid = false;      // device code wrote it
+    mark_written(outs);
+    std::memset(&g.stats, 0, sizeof g.stats);
+    HIP_OK(hipEventElapsedTime(&(g.stats.*ms), g.evA, g.evB));
+    return 0;
+}
+
+// descriptor slots 5, 7, 8, 9 with their element counts; uv may be null
+SurfaceScene surface_scene(rdx_buffer meshInfo, rdx_buffer index, rdx_buffer normal, rdx_buffer uv)
+{
+    SurfaceScene s{};
+    s.meshInfo = at<const MeshInfo>(meshInfo); s.nMeshInfo = (uint32_t)std::min<size_t>(meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
+    s.index = at<const uint32_t>(index); s.nIndex = index->size / sizeof(uint32_t);
+    s.normal = at<const float>(normal); s.nNormal = normal->size / sizeof(float);
+    if (uv) { s.uv = at<const float>(uv); s.nUv = uv->size / sizeof(float); }
+    return s;
+}
+int check_surface_handles(const char* who, const rdx_surface_buffers* scene)
+{
+    if (!scene) return fail("%s: no scene buffers", who);
+    if (!scene->meshInfo || !known_buffer(scene->meshInfo)) return fail("%s: invalid meshInfo buffer handle", who);
+    if (!scene->index || !known_buffer(scene->index)) return fail("%s: invalid index buffer handle", who);
+    if (!scene->normal || !known_buffer(scene->normal)) return fail("%s: invalid normal buffer handle", who);
+    if (scene->uv && !known_buffer(scene->uv)) return fail("%s: invalid uv buffer handle", who);
+    return 0;
+}
+bool surface_aligned(const rdx_surface_buffers* s) { return aligned4(s->meshInfo) && aligned4(s->index) && aligned4(s->normal) && aligned4(s->uv); }
+} // namespace
+
+extern "C" int rdx_debug_check_ranges(const rdx_debug_range* rows, const char* const* names, uint32_t count, uint32_t first_out, uint32_t n)
+{
+    if (count && (!rows || !names)) return fail("rdx_debug_check_ranges: no rows");
+    std::vector<RangeRow> R(count);
+    for (uint32_t k = 0; k < count; ++k) {
+        if (!rows[k].align || (rows[k].align & (rows[k].align - 1u))) return fail("rdx_debug_check_ranges: row %u: align %u is not a power of two", k, rows[k].align);
+        R[k] = RangeRow{(uintptr_t)rows[k].address, (size_t)rows[k].size, (size_t)rows[k].offset, (size_t)rows[k].bytes, rows[k].align,
+                        names[k] ? names[k] : "?", rows[k].present != 0};
+    }
+    return check_ranges("rdx_debug_check_ranges", R.data(), (int)count, (int)std::min<uint32_t>(first_out, count), n);
+}
+
+// Device-resident ray queries: nothing is staged through the host and nothing is allocated
+extern "C" int rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, uint32_t n, int kind, rdx_buffer hits, size_t hits_offset)
+{
+    const char* who = "rdx_query_rays";
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_query_rays: invalid TLAS handle");
+    static_assert(sizeof(rdx_ray) == 32 && sizeof(rdx_ray_hit) == 32, "two float4 per ray, two per record");
+    const CallRange R[2] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {hits, hits_offset, (size_t)n * sizeof(rdx_ray_hit), "hit", 16, true}};
+    if (check_call_handles(who, R)) return -1;
+    if (kind != RDX_QUERY_CLOSEST && kind != RDX_QUERY_ANY) return fail("rdx_query_rays: kind must be RDX_QUERY_CLOSEST (1) or RDX_QUERY_ANY (2), not %d", kind);
+    if (check_call_ranges(who, R, 1, n)) return -1;
+    if (!n) return 0;
+    if (derive_accel(tlas)) return -1;
+    HIP_OK(hipMemsetAsync(g.dCounts + 64, 0, sizeof(uint32_t), g.stream));
+    if (timed_launch(&rdx_trace_stats::ms_extend, {hits}, [&] {
+            launch_query_rays(g.stream, view_of(tlas), at<const float4>(rays, rays_offset), n, kind, at<float4>(hits, hits_offset), g.dCounts + 64); }))
+        return -1;
+    if (take_status()) return fail("rdx_query_rays: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
+    return 0;
+}
+
+// Surface records of a query's hits (surface.hip)
+extern "C" int rdx_resolve_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, uint32_t n,
+                                const rdx_surface_buffers* scene, rdx_buffer out, size_t out_offset, uint32_t* invalid_out)
+{
+    const char* who = "rdx_resolve_hits";
+    if (!g.initialized) return fail("rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_resolve_hits: invalid TLAS handle");
+    static_assert(sizeof(rdx_surface) == 64 && sizeof(MeshInfo) == sizeof(rdx_mesh_info), "four float4 per surface record");
+    const CallRange R[3] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {hits, hits_offset, (size_t)n * sizeof(rdx_ray_hit), "hit", 16, true},
+                            {out, out_offset, (size_t)n * sizeof(rdx_surface), "output", 16, true}};
+    if (check_call_handles(who, R) || check_surface_handles(who, scene)) return -1;
+    if (check_call_ranges(who, R, 2, n, {invalid_out}, surface_aligned(scene))) return -1;
+    if (!n) return 0;
+    if (derive_accel(tlas)) return -1;
+    const AccelCache& ac = *acc(tlas);
+    // (ShadeScene passes the uv stream only with textures on; here it is passed whenever it is given)
+    const SurfaceScene sc = surface_scene(scene->meshInfo, scene->index, scene->normal, scene->uv && scene->uv->size >= sizeof(float) ? scene->uv : nullptr);
+    HIP_OK(hipMemsetAsync(g.dSurfaceInvalid, 0, sizeof(uint32_t), g.stream));
+    if (timed_launch(&rdx_trace_stats::ms_shade, {out}, [&] {
+            launch_resolve_hits(g.stream, ac.insts, ac.slotOf, ac.s.nInst, at<const float4>(rays, rays_offset), at<const float4>(hits, hits_offset), n, sc,
+                                at<float4>(out, out_offset), g.dSurfaceInvalid); }))
+        return -1;
     uint32_t invalid = 0;
     HIP_OK(hipMemcpy(&invalid, g.dSurfaceInvalid, sizeof invalid, hipMemcpyDeviceToHost));
     if (invalid_out) *invalid_out = invalid;
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
     return 0;
 }
 
@@ -2298,14 +2360,10 @@ int check_shading_handles(const char* who, const rdx_shading_buffers* scene, uin
         return fail("%s: the scene buffer (%zu bytes) does not hold a SceneProperties (%zu bytes)", who, scene->scene->size, sizeof(SceneProperties));
     return 0;
 }
-int check_shading_alignment(const char* who, const rdx_shading_buffers* scene)
+bool shading_aligned(const rdx_shading_buffers* s)
 {
-    if ((reinterpret_cast<uintptr_t>(scene->scene->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->meshInfo->dptr) & 3u) ||
-        (reinterpret_cast<uintptr_t>(scene->index->dptr) & 3u) || (reinterpret_cast<uintptr_t>(scene->normal->dptr) & 3u) ||
-        (reinterpret_cast<uintptr_t>(scene->material->dptr) & 3u) || (scene->uv && (reinterpret_cast<uintptr_t>(scene->uv->dptr) & 3u)) ||
-        (scene->textureArray && (reinterpret_cast<uintptr_t>(scene->textureArray->dptr) & 3u)))
-        return fail("%s: wrapped scene streams must be 4-byte aligned", who);
-    return 0;
+    return aligned4(s->scene) && aligned4(s->meshInfo) && aligned4(s->index) && aligned4(s->normal) && aligned4(s->material) && aligned4(s->uv) &&
+           aligned4(s->textureArray);
 }
 // the stock shader's rule (scene_args): texels are read only when option "textures" is 1 and an image array is given; the uv
 // buffer is required then
@@ -2320,79 +2378,51 @@ int shading_textures(const char* who, const rdx_shading_buffers* scene, uint32_t
     tex = TexView{static_cast<const uint8_t*>(img->dptr), img->imgW, img->imgH, img->imgLayers, TEX_ENABLED | samplerBits};
     return 0;
 }
+// the scene as shade.hip, material.hip and light_paths.hip read it: the pointers, the element counts, the texture view, and the uv
+// stream only with textures on
+int shade_scene(const char* who, const rdx_shading_buffers* scene, uint32_t samplerBits, ShadeScene& sc)
+{
+    sc = ShadeScene{};
+    sc.scene = at<const SceneProperties>(scene->scene);
+    sc.materials = at<const Material>(scene->material); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
+    if (shading_textures(who, scene, samplerBits, sc.tex)) return -1;
+    sc.s = surface_scene(scene->meshInfo, scene->index, scene->normal, (sc.tex.flags & TEX_ENABLED) ? scene->uv : nullptr);
+    return 0;
+}
 } // namespace
 
-// The stock closest-hit / miss shaders on a query's records (shade.hip): the checks and the steps around the launch are those of
-// rdx_resolve_hits
+// The stock closest-hit / miss shaders on a query's records (shade.hip)
 extern "C" int rdx_shade_hits(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, rdx_buffer keys,
                               size_t keys_offset, uint32_t n, const rdx_shading_buffers* scene, rdx_buffer shade, size_t shade_offset,
                               rdx_buffer next, size_t next_offset, rdx_buffer shadow, size_t shadow_offset, rdx_buffer src, size_t src_offset,
                               uint32_t* live_out, uint32_t* invalid_out)
 {
+    const char* who = "rdx_shade_hits";
     if (!g.initialized) return fail("rdx_init has not been called");
     if (!tlas || !known_buffer(tlas)) return fail("rdx_shade_hits: invalid TLAS handle");
-    if (!rays || !known_buffer(rays)) return fail("rdx_shade_hits: invalid ray buffer handle");
-    if (!hits || !known_buffer(hits)) return fail("rdx_shade_hits: invalid hit buffer handle");
-    if (!keys || !known_buffer(keys)) return fail("rdx_shade_hits: invalid key buffer handle");
-    if (!shade || !known_buffer(shade)) return fail("rdx_shade_hits: invalid shade buffer handle");
-    if (next && !known_buffer(next)) return fail("rdx_shade_hits: invalid next-ray buffer handle");
-    if (shadow && !known_buffer(shadow)) return fail("rdx_shade_hits: invalid shadow-ray buffer handle");
-    if (src && !known_buffer(src)) return fail("rdx_shade_hits: invalid src buffer handle");
-    uint32_t samplerBits = 0;
-    if (check_shading_handles("rdx_shade_hits", scene, samplerBits)) return -1;
     static_assert(sizeof(rdx_shade) == 48 && sizeof(rdx_shade_key) == 16 && sizeof(rdx_shading_buffers) == 8 * sizeof(void*), "three float4 per shade record, one uint4 per key");
-    // every range the kernel touches: {buffer, offset, bytes per record, name}; the first three are read, the others written
-    struct Range { rdx_buffer b; size_t off, rec; const char* name; };
-    const Range R[7] = {{rays, rays_offset, sizeof(rdx_ray), "ray"}, {hits, hits_offset, sizeof(rdx_ray_hit), "hit"}, {keys, keys_offset, sizeof(rdx_shade_key), "key"},
-                        {shade, shade_offset, sizeof(rdx_shade), "shade"}, {next, next_offset, sizeof(rdx_ray), "next-ray"},
-                        {shadow, shadow_offset, sizeof(rdx_ray), "shadow-ray"}, {src, src_offset, sizeof(uint32_t), "src"}};
-    for (const Range& r : R)
-        if (r.b && (r.off & 15u)) return fail("rdx_shade_hits: offsets must be multiples of 16 bytes (%s offset %zu)", r.name, r.off);
-    for (const Range& r : R)
-        if (r.b && (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off))
-            return fail("rdx_shade_hits: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
-    if (live_out) *live_out = 0;
-    if (invalid_out) *invalid_out = 0;
+    // the first three are read, the others written; src is held to 16 bytes here (4 in rdx_scatter_hits)
+    const CallRange R[7] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {hits, hits_offset, (size_t)n * sizeof(rdx_ray_hit), "hit", 16, true},
+                            {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true}, {shade, shade_offset, (size_t)n * sizeof(rdx_shade), "shade", 16, true},
+                            {next, next_offset, (size_t)n * sizeof(rdx_ray), "next-ray", 16, false}, {shadow, shadow_offset, (size_t)n * sizeof(rdx_ray), "shadow-ray", 16, false},
+                            {src, src_offset, (size_t)n * sizeof(uint32_t), "src", 16, false}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (check_call_ranges(who, R, 3, n, {live_out, invalid_out}, shading_aligned(scene))) return -1;
     if (!n) return 0;
-    for (const Range& r : R)
-        if (r.b && (reinterpret_cast<uintptr_t>(r.b->dptr) & 15u)) return fail("rdx_shade_hits: wrapped device memory must be 16-byte aligned (%s buffer)", r.name);
-    if (check_shading_alignment("rdx_shade_hits", scene)) return -1;
-    // no output range may overlap an input range or another output range, in one buffer or in several that wrap the same memory
-    for (int o = 3; o < 7; ++o)
-        for (int k = 0; k < o; ++k) {
-            if (!R[o].b || !R[k].b) continue;
-            const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[o].b->dptr) + R[o].off, a1 = a0 + (size_t)n * R[o].rec,
-                            b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
-            if (a0 < b1 && b0 < a1) return fail("rdx_shade_hits: the %s range and the %s range overlap", R[o].name, R[k].name);
-        }
-    ShadeScene sc{};
-    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
-    sc.s.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.s.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
-    sc.s.index = static_cast<const uint32_t*>(scene->index->dptr); sc.s.nIndex = scene->index->size / sizeof(uint32_t);
-    sc.s.normal = static_cast<const float*>(scene->normal->dptr); sc.s.nNormal = scene->normal->size / sizeof(float);
-    sc.materials = static_cast<const Material*>(scene->material->dptr); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
-    if (shading_textures("rdx_shade_hits", scene, samplerBits, sc.tex)) return -1;
-    if (sc.tex.flags & TEX_ENABLED) { sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float); }
-    if (derive_accel(tlas)) return -1;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
     const AccelCache& ac = *acc(tlas);
-    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
     HIP_OK(hipMemsetAsync(g.dShadeCounts, 0, 2 * sizeof(uint32_t), g.stream));
-    HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_shade_hits(g.stream, ac.insts, ac.slotOf, ac.s.nInst, reinterpret_cast<const float4*>(at(rays, rays_offset)),
-                      reinterpret_cast<const float4*>(at(hits, hits_offset)), reinterpret_cast<const uint4*>(at(keys, keys_offset)), n, sc,
-                      reinterpret_cast<float4*>(at(shade, shade_offset)), reinterpret_cast<float4*>(at(next, next_offset)),
-                      reinterpret_cast<float4*>(at(shadow, shadow_offset)), reinterpret_cast<uint32_t*>(at(src, src_offset)), g.dShadeCounts,
-                      g.dShadeCounts + 1);
-    HIP_OK(hipEventRecord(g.evB, g.stream));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(g.stream));
-    for (rdx_buffer b : {shade, next, shadow, src}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    if (timed_launch(&rdx_trace_stats::ms_shade, {shade, next, shadow, src}, [&] {
+            launch_shade_hits(g.stream, ac.insts, ac.slotOf, ac.s.nInst, at<const float4>(rays, rays_offset), at<const float4>(hits, hits_offset),
+                              at<const uint4>(keys, keys_offset), n, sc, at<float4>(shade, shade_offset), at<float4>(next, next_offset),
+                              at<float4>(shadow, shadow_offset), at<uint32_t>(src, src_offset), g.dShadeCounts, g.dShadeCounts + 1); }))
+        return -1;
     uint32_t counts[2] = {0, 0};
     HIP_OK(hipMemcpy(counts, g.dShadeCounts, sizeof counts, hipMemcpyDeviceToHost));
     if (live_out) *live_out = counts[0];
     if (invalid_out) *invalid_out = counts[1];
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
     return 0;
 }
 
@@ -2407,61 +2437,31 @@ extern "C" int rdx_debug_shade_in_bounds(const rdx_mesh_info* mi, uint32_t ninst
                            textures ? nuv : 0u, reinterpret_cast<const Material*>(materials), nmaterials, textures != 0, layers) ? 1 : 0;
 }
 
-// The evaluated material of a query's hits (material.hip): the inputs, the checks and the steps around the launch are those of
-// rdx_shade_hits without the keys
+// The evaluated material of a query's hits (material.hip): the inputs are those of rdx_shade_hits without the keys
 extern "C" int rdx_resolve_materials(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer hits, size_t hits_offset, uint32_t n,
                                      const rdx_shading_buffers* scene, rdx_buffer out, size_t out_offset, uint32_t* invalid_out)
 {
+    const char* who = "rdx_resolve_materials";
     if (!g.initialized) return fail("rdx_init has not been called");
     if (!tlas || !known_buffer(tlas)) return fail("rdx_resolve_materials: invalid TLAS handle");
-    if (!rays || !known_buffer(rays)) return fail("rdx_resolve_materials: invalid ray buffer handle");
-    if (!hits || !known_buffer(hits)) return fail("rdx_resolve_materials: invalid hit buffer handle");
-    if (!out || !known_buffer(out)) return fail("rdx_resolve_materials: invalid output buffer handle");
-    uint32_t samplerBits = 0;
-    if (check_shading_handles("rdx_resolve_materials", scene, samplerBits)) return -1;
     static_assert(sizeof(rdx_material_record) == 64, "four float4 per material record");
-    struct Range { rdx_buffer b; size_t off, rec; const char* name; };
-    const Range R[3] = {{rays, rays_offset, sizeof(rdx_ray), "ray"}, {hits, hits_offset, sizeof(rdx_ray_hit), "hit"},
-                        {out, out_offset, sizeof(rdx_material_record), "output"}};
-    for (const Range& r : R)
-        if (r.off & 15u) return fail("rdx_resolve_materials: offsets must be multiples of 16 bytes (%s offset %zu)", r.name, r.off);
-    for (const Range& r : R)
-        if (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off)
-            return fail("rdx_resolve_materials: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
-    if (invalid_out) *invalid_out = 0;
+    const CallRange R[3] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {hits, hits_offset, (size_t)n * sizeof(rdx_ray_hit), "hit", 16, true},
+                            {out, out_offset, (size_t)n * sizeof(rdx_material_record), "output", 16, true}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (check_call_ranges(who, R, 2, n, {invalid_out}, shading_aligned(scene))) return -1;
     if (!n) return 0;
-    for (const Range& r : R)
-        if (reinterpret_cast<uintptr_t>(r.b->dptr) & 15u) return fail("rdx_resolve_materials: wrapped device memory must be 16-byte aligned (%s buffer)", r.name);
-    if (check_shading_alignment("rdx_resolve_materials", scene)) return -1;
-    for (int k = 0; k < 2; ++k) {       // the output must not overlap what the kernel reads of the rays and of the records
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[2].b->dptr) + R[2].off, a1 = a0 + (size_t)n * R[2].rec,
-                        b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
-        if (a0 < b1 && b0 < a1) return fail("rdx_resolve_materials: the %s range and the %s range overlap", R[2].name, R[k].name);
-    }
-    ShadeScene sc{};
-    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
-    sc.s.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.s.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
-    sc.s.index = static_cast<const uint32_t*>(scene->index->dptr); sc.s.nIndex = scene->index->size / sizeof(uint32_t);
-    sc.s.normal = static_cast<const float*>(scene->normal->dptr); sc.s.nNormal = scene->normal->size / sizeof(float);
-    sc.materials = static_cast<const Material*>(scene->material->dptr); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
-    if (shading_textures("rdx_resolve_materials", scene, samplerBits, sc.tex)) return -1;
-    if (sc.tex.flags & TEX_ENABLED) { sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float); }
-    if (derive_accel(tlas)) return -1;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
     const AccelCache& ac = *acc(tlas);
     HIP_OK(hipMemsetAsync(g.dShadeCounts, 0, 2 * sizeof(uint32_t), g.stream));
-    HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_resolve_materials(g.stream, ac.insts, ac.slotOf, ac.s.nInst, reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset),
-                             reinterpret_cast<const float4*>(static_cast<const char*>(hits->dptr) + hits_offset), n, sc,
-                             reinterpret_cast<float4*>(static_cast<char*>(out->dptr) + out_offset), g.dShadeCounts + 1);
-    HIP_OK(hipEventRecord(g.evB, g.stream));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(g.stream));
-    ++out->version; out->mirrorValid = false;      // device code wrote it
+    if (timed_launch(&rdx_trace_stats::ms_shade, {out}, [&] {
+            launch_resolve_materials(g.stream, ac.insts, ac.slotOf, ac.s.nInst, at<const float4>(rays, rays_offset), at<const float4>(hits, hits_offset), n, sc,
+                                     at<float4>(out, out_offset), g.dShadeCounts + 1); }))
+        return -1;
     uint32_t invalid = 0;
     HIP_OK(hipMemcpy(&invalid, g.dShadeCounts + 1, sizeof invalid, hipMemcpyDeviceToHost));
     if (invalid_out) *invalid_out = invalid;
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
     return 0;
 }
 
@@ -2470,53 +2470,23 @@ extern "C" int rdx_resolve_materials(rdx_buffer tlas, rdx_buffer rays, size_t ra
 extern "C" int rdx_light_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer materials, size_t materials_offset, uint32_t n, rdx_buffer scene,
                               uint32_t light, rdx_buffer lit, size_t lit_offset, rdx_buffer shadow, size_t shadow_offset)
 {
+    const char* who = "rdx_light_hits";
     if (!g.initialized) return fail("rdx_init has not been called");
-    if (!rays || !known_buffer(rays)) return fail("rdx_light_hits: invalid ray buffer handle");
-    if (!materials || !known_buffer(materials)) return fail("rdx_light_hits: invalid material-record buffer handle");
-    if (!scene || !known_buffer(scene)) return fail("rdx_light_hits: invalid scene (SceneProperties) buffer handle");
-    if (!lit || !known_buffer(lit)) return fail("rdx_light_hits: invalid lit buffer handle");
-    if (shadow && !known_buffer(shadow)) return fail("rdx_light_hits: invalid shadow-ray buffer handle");
+    // the first three are read (the whole SceneProperties stands for its one light), the others written
+    const CallRange R[5] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true},
+                            {materials, materials_offset, (size_t)n * sizeof(rdx_material_record), "material-record", 16, true},
+                            {scene, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, true},
+                            {lit, lit_offset, (size_t)n * 4 * sizeof(float), "lit", 16, true}, {shadow, shadow_offset, (size_t)n * sizeof(rdx_ray), "shadow-ray", 16, false}};
+    if (check_call_handles(who, R)) return -1;
     constexpr uint32_t nLights = sizeof(SceneProperties::lights) / sizeof(DirLight);
     if (light >= nLights) return fail("rdx_light_hits: light %u is not one of the %u lights of a SceneProperties (0 .. %u)", light, nLights, nLights - 1u);
     if (scene->size < sizeof(SceneProperties))
         return fail("rdx_light_hits: the scene buffer (%zu bytes) does not hold a SceneProperties (%zu bytes)", scene->size, sizeof(SceneProperties));
-    // every range the kernel touches: {buffer, offset, bytes per record, name}; the first two are read, the others written
-    struct Range { rdx_buffer b; size_t off, rec; const char* name; };
-    const Range R[4] = {{rays, rays_offset, sizeof(rdx_ray), "ray"}, {materials, materials_offset, sizeof(rdx_material_record), "material-record"},
-                        {lit, lit_offset, 4 * sizeof(float), "lit"}, {shadow, shadow_offset, sizeof(rdx_ray), "shadow-ray"}};
-    for (const Range& r : R)
-        if (r.b && (r.off & 15u)) return fail("rdx_light_hits: offsets must be multiples of 16 bytes (%s offset %zu)", r.name, r.off);
-    for (const Range& r : R)
-        if (r.b && (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off))
-            return fail("rdx_light_hits: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
+    if (check_call_ranges(who, R, 3, n)) return -1;
     if (!n) return 0;
-    for (const Range& r : R)
-        if (r.b && (reinterpret_cast<uintptr_t>(r.b->dptr) & 15u)) return fail("rdx_light_hits: wrapped device memory must be 16-byte aligned (%s buffer)", r.name);
-    if (reinterpret_cast<uintptr_t>(scene->dptr) & 3u) return fail("rdx_light_hits: a wrapped scene buffer must be 4-byte aligned");
-    // no output range may overlap an input range, the SceneProperties or the other output range, in one buffer or in several
-    // that wrap the same memory
-    for (int o = 2; o < 4; ++o) {
-        if (!R[o].b) continue;
-        const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[o].b->dptr) + R[o].off, a1 = a0 + (size_t)n * R[o].rec;
-        for (int k = 0; k < o; ++k) {
-            const uintptr_t b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
-            if (a0 < b1 && b0 < a1) return fail("rdx_light_hits: the %s range and the %s range overlap", R[o].name, R[k].name);
-        }
-        const uintptr_t s0 = reinterpret_cast<uintptr_t>(scene->dptr), s1 = s0 + sizeof(SceneProperties);
-        if (a0 < s1 && s0 < a1) return fail("rdx_light_hits: the %s range and the SceneProperties overlap", R[o].name);
-    }
-    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
-    HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_light_hits(g.stream, reinterpret_cast<const float4*>(at(rays, rays_offset)), reinterpret_cast<const float4*>(at(materials, materials_offset)), n,
-                      reinterpret_cast<const DirLight*>(static_cast<const char*>(scene->dptr) + offsetof(SceneProperties, lights)) + light, reinterpret_cast<float4*>(at(lit, lit_offset)),
-                      reinterpret_cast<float4*>(at(shadow, shadow_offset)));
-    HIP_OK(hipEventRecord(g.evB, g.stream));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(g.stream));
-    for (rdx_buffer b : {lit, shadow}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
-    return 0;
+    return timed_launch(&rdx_trace_stats::ms_shade, {lit, shadow}, [&] {
+        launch_light_hits(g.stream, at<const float4>(rays, rays_offset), at<const float4>(materials, materials_offset), n,
+                          at<const DirLight>(scene, offsetof(SceneProperties, lights)) + light, at<float4>(lit, lit_offset), at<float4>(shadow, shadow_offset)); });
 }
 
 // The next-direction sample of `material` on material and surface records (scatter.hip).  No TLAS and no scene buffers: the kernel
@@ -2527,164 +2497,84 @@ extern "C" int rdx_scatter_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer 
                                 rdx_buffer scatter, size_t scatter_offset, rdx_buffer next, size_t next_offset, rdx_buffer src, size_t src_offset,
                                 uint32_t* live_out)
 {
+    const char* who = "rdx_scatter_hits";
     if (!g.initialized) return fail("rdx_init has not been called");
-    if (!rays || !known_buffer(rays)) return fail("rdx_scatter_hits: invalid ray buffer handle");
-    if (!materials || !known_buffer(materials)) return fail("rdx_scatter_hits: invalid material-record buffer handle");
-    if (!surfaces || !known_buffer(surfaces)) return fail("rdx_scatter_hits: invalid surface-record buffer handle");
-    if (!scatter || !known_buffer(scatter)) return fail("rdx_scatter_hits: invalid scatter buffer handle");
-    if (!next || !known_buffer(next)) return fail("rdx_scatter_hits: invalid next-ray buffer handle");
-    if (keys && !known_buffer(keys)) return fail("rdx_scatter_hits: invalid key buffer handle");
-    if (randoms && !known_buffer(randoms)) return fail("rdx_scatter_hits: invalid randoms buffer handle");
-    if (src && !known_buffer(src)) return fail("rdx_scatter_hits: invalid src buffer handle");
+    static_assert(sizeof(rdx_scatter) == 16 && sizeof(rdx_material_record) == 64 && sizeof(rdx_surface) == 64, "one float4 per scatter record");
+    // the first five are read, the others written
+    const CallRange R[8] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true},
+                            {materials, materials_offset, (size_t)n * sizeof(rdx_material_record), "material-record", 16, true},
+                            {surfaces, surfaces_offset, (size_t)n * sizeof(rdx_surface), "surface-record", 16, true},
+                            {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, false}, {randoms, randoms_offset, (size_t)n * 4 * sizeof(float), "randoms", 16, false},
+                            {scatter, scatter_offset, (size_t)n * sizeof(rdx_scatter), "scatter", 16, true}, {next, next_offset, (size_t)n * sizeof(rdx_ray), "next-ray", 16, true},
+                            {src, src_offset, (size_t)n * sizeof(uint32_t), "src", 4, false}};
+    if (check_call_handles(who, R)) return -1;
     if (!keys && !randoms) return fail("rdx_scatter_hits: neither keys nor randoms given: one of the two is required");
     if (keys && randoms) return fail("rdx_scatter_hits: both keys and randoms given: only one of the two is allowed");
-    static_assert(sizeof(rdx_scatter) == 16 && sizeof(rdx_material_record) == 64 && sizeof(rdx_surface) == 64, "one float4 per scatter record");
-    // every range the kernel touches: {buffer, offset, bytes per record, name, alignment}; the first five are read, the others written
-    struct Range { rdx_buffer b; size_t off, rec; const char* name; uint32_t align; };
-    const Range R[8] = {{rays, rays_offset, sizeof(rdx_ray), "ray", 16u}, {materials, materials_offset, sizeof(rdx_material_record), "material-record", 16u},
-                        {surfaces, surfaces_offset, sizeof(rdx_surface), "surface-record", 16u}, {keys, keys_offset, sizeof(rdx_shade_key), "key", 16u},
-                        {randoms, randoms_offset, 4 * sizeof(float), "randoms", 16u}, {scatter, scatter_offset, sizeof(rdx_scatter), "scatter", 16u},
-                        {next, next_offset, sizeof(rdx_ray), "next-ray", 16u}, {src, src_offset, sizeof(uint32_t), "src", 4u}};
-    for (const Range& r : R)
-        if (r.b && (r.off & (r.align - 1u)))
-            return fail("rdx_scatter_hits: offsets must be multiples of 16 bytes, 4 for src (%s offset %zu)", r.name, r.off);
-    for (const Range& r : R)
-        if (r.b && (r.off > r.b->size || (size_t)n * r.rec > r.b->size - r.off))
-            return fail("rdx_scatter_hits: %u records at offset %zu run past the %s buffer (%zu bytes)", n, r.off, r.name, r.b->size);
-    if (live_out) *live_out = 0;
+    if (check_call_ranges(who, R, 5, n, {live_out})) return -1;
     if (!n) return 0;
-    for (const Range& r : R)
-        if (r.b && (reinterpret_cast<uintptr_t>(r.b->dptr) & (r.align - 1u)))
-            return fail("rdx_scatter_hits: wrapped device memory must be %u-byte aligned (%s buffer)", r.align, r.name);
-    // no output range may overlap an input range or another output range, in one buffer or in several that wrap the same memory
-    for (int o = 5; o < 8; ++o)
-        for (int k = 0; k < o; ++k) {
-            if (!R[o].b || !R[k].b) continue;
-            const uintptr_t a0 = reinterpret_cast<uintptr_t>(R[o].b->dptr) + R[o].off, a1 = a0 + (size_t)n * R[o].rec,
-                            b0 = reinterpret_cast<uintptr_t>(R[k].b->dptr) + R[k].off, b1 = b0 + (size_t)n * R[k].rec;
-            if (a0 < b1 && b0 < a1) return fail("rdx_scatter_hits: the %s range and the %s range overlap", R[o].name, R[k].name);
-        }
-    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
     HIP_OK(hipMemsetAsync(g.dShadeCounts, 0, sizeof(uint32_t), g.stream));
-    HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_scatter_hits(g.stream, reinterpret_cast<const float4*>(at(rays, rays_offset)), reinterpret_cast<const float4*>(at(materials, materials_offset)),
-                        reinterpret_cast<const float4*>(at(surfaces, surfaces_offset)), reinterpret_cast<const uint4*>(at(keys, keys_offset)),
-                        reinterpret_cast<const float4*>(at(randoms, randoms_offset)), n, reinterpret_cast<float4*>(at(scatter, scatter_offset)),
-                        reinterpret_cast<float4*>(at(next, next_offset)), reinterpret_cast<uint32_t*>(at(src, src_offset)), g.dShadeCounts);
-    HIP_OK(hipEventRecord(g.evB, g.stream));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(g.stream));
-    for (rdx_buffer b : {scatter, next, src}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    if (timed_launch(&rdx_trace_stats::ms_shade, {scatter, next, src}, [&] {
+            launch_scatter_hits(g.stream, at<const float4>(rays, rays_offset), at<const float4>(materials, materials_offset), at<const float4>(surfaces, surfaces_offset),
+                                at<const uint4>(keys, keys_offset), at<const float4>(randoms, randoms_offset), n, at<float4>(scatter, scatter_offset),
+                                at<float4>(next, next_offset), at<uint32_t>(src, src_offset), g.dShadeCounts); }))
+        return -1;
     uint32_t live = 0;
     HIP_OK(hipMemcpy(&live, g.dShadeCounts, sizeof live, hipMemcpyDeviceToHost));
     if (live_out) *live_out = live;
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_shade, g.evA, g.evB));      // kernel time of this call
     return 0;
 }
 
 // ---- the two ends of a frame on device memory (raygen.hip) ---------------------------------------------------------------------
-namespace {
-// a byte range a kernel touches: {buffer, offset, bytes, name, required alignment of offset and address}
-struct FrameRange { rdx_buffer b; size_t off, bytes; const char* name; uint32_t align; };
-bool ranges_overlap(const FrameRange& a, const FrameRange& b)
-{
-    if (!a.b || !b.b || !a.bytes || !b.bytes) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.b->dptr) + a.off, a1 = a0 + a.bytes,
-                    b0 = reinterpret_cast<uintptr_t>(b.b->dptr) + b.off, b1 = b0 + b.bytes;
-    return a0 < b1 && b0 < a1;
-}
-// offsets, sizes and -- n != 0 -- addresses of R[0 .. count); outputs are R[firstOut ..]: none may overlap a range before it
-int check_frame_ranges(const char* who, const FrameRange* R, int count, int firstOut, uint32_t n)
-{
-    for (int k = 0; k < count; ++k)
-        if (R[k].b && (R[k].off & (R[k].align - 1u))) return fail("%s: the %s offset must be a multiple of %u bytes (offset %zu)", who, R[k].name, R[k].align, R[k].off);
-    for (int k = 0; k < count; ++k)
-        if (R[k].b && (R[k].off > R[k].b->size || R[k].bytes > R[k].b->size - R[k].off))
-            return fail("%s: %u records at offset %zu run past the %s buffer (%zu bytes)", who, n, R[k].off, R[k].name, R[k].b->size);
-    if (!n) return 0;
-    for (int k = 0; k < count; ++k)
-        if (R[k].b && (reinterpret_cast<uintptr_t>(R[k].b->dptr) & (R[k].align - 1u)))
-            return fail("%s: wrapped device memory must be %u-byte aligned (%s buffer)", who, R[k].align, R[k].name);
-    for (int o = firstOut; o < count; ++o)
-        for (int k = 0; k < o; ++k)
-            if (ranges_overlap(R[o], R[k])) return fail("%s: the %s range and the %s range overlap", who, R[o].name, R[k].name);
-    return 0;
-}
-} // namespace
-
 // Primary rays of the camera in `camera`, as rdx_ray / rdx_shade_key records on the device (include/rdx.h)
 extern "C" int rdx_generate_rays(rdx_buffer camera, uint32_t n, uint32_t first_pixel, rdx_buffer pixels, size_t pixels_offset, uint32_t frameID,
                                  uint32_t totalSamples, rdx_buffer seeds, size_t seeds_offset, float tmin, float tmax, rdx_buffer rays,
                                  size_t rays_offset, rdx_buffer keys, size_t keys_offset)
 {
+    const char* who = "rdx_generate_rays";
     if (!g.initialized) return fail("rdx_init has not been called");
-    if (!camera || !known_buffer(camera)) return fail("rdx_generate_rays: invalid camera buffer handle");
-    if (!rays || !known_buffer(rays)) return fail("rdx_generate_rays: invalid ray buffer handle");
-    if (pixels && !known_buffer(pixels)) return fail("rdx_generate_rays: invalid pixel buffer handle");
-    if (seeds && !known_buffer(seeds)) return fail("rdx_generate_rays: invalid seed buffer handle");
-    if (keys && !known_buffer(keys)) return fail("rdx_generate_rays: invalid key buffer handle");
+    static_assert(sizeof(rdx_raygen_seed) == 16 && sizeof(rdx_shade_key) == 16 && sizeof(rdx_ray) == 32, "one uint4 per seed and key, two float4 per ray");
+    const CallRange R[5] = {{camera, 0, sizeof(PhysicalCamera), "camera", 4, true}, {pixels, pixels_offset, (size_t)n * sizeof(uint32_t), "pixel", 4, false},
+                            {seeds, seeds_offset, (size_t)n * sizeof(rdx_raygen_seed), "seed", 16, false},
+                            {rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, false}};
+    if (check_call_handles(who, R)) return -1;
     if (camera->size < sizeof(PhysicalCamera))
         return fail("rdx_generate_rays: the camera buffer (%zu bytes) does not hold a PhysicalCamera (%zu bytes)", camera->size, sizeof(PhysicalCamera));
-    static_assert(sizeof(rdx_raygen_seed) == 16 && sizeof(rdx_shade_key) == 16 && sizeof(rdx_ray) == 32, "one uint4 per seed and key, two float4 per ray");
     if (!pixels && (uint64_t)first_pixel + n > 0x100000000ull)
         return fail("rdx_generate_rays: first_pixel + n (%u + %u) does not fit 32 bits", first_pixel, n);
-    const FrameRange R[5] = {{camera, 0, sizeof(PhysicalCamera), "camera", 4}, {pixels, pixels_offset, (size_t)n * sizeof(uint32_t), "pixel", 4},
-                             {seeds, seeds_offset, (size_t)n * sizeof(rdx_raygen_seed), "seed", 16},
-                             {rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16}};
-    if (check_frame_ranges("rdx_generate_rays", R, 5, 3, n)) return -1;
+    if (check_call_ranges(who, R, 3, n)) return -1;
     if (!n) return 0;
-    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
-    HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_generate_rays(g.stream, static_cast<const PhysicalCamera*>(camera->dptr), g.dRaygenArgs, n, first_pixel,
-                         reinterpret_cast<const uint32_t*>(at(pixels, pixels_offset)), frameID, totalSamples,
-                         reinterpret_cast<const uint4*>(at(seeds, seeds_offset)), tmin, tmax, reinterpret_cast<float4*>(at(rays, rays_offset)),
-                         reinterpret_cast<uint4*>(at(keys, keys_offset)));
-    HIP_OK(hipEventRecord(g.evB, g.stream));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(g.stream));
-    for (rdx_buffer b : {rays, keys}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_generate, g.evA, g.evB));      // kernel time of this call (the camera's one-thread kernel included)
-    return 0;
+    // (the time includes the camera's one-thread kernel)
+    return timed_launch(&rdx_trace_stats::ms_generate, {rays, keys}, [&] {
+        launch_generate_rays(g.stream, at<const PhysicalCamera>(camera), g.dRaygenArgs, n, first_pixel, at<const uint32_t>(pixels, pixels_offset), frameID,
+                             totalSamples, at<const uint4>(seeds, seeds_offset), tmin, tmax, at<float4>(rays, rays_offset), at<uint4>(keys, keys_offset)); });
 }
 
 // One sample per pixel folded into imageScratch, and the RGBA8 image of the new mean (include/rdx.h)
 extern "C" int rdx_accumulate(rdx_buffer colors, size_t colors_offset, uint32_t n, uint32_t first_pixel, rdx_buffer pixels, size_t pixels_offset,
                               uint32_t frameID, rdx_buffer scratch, rdx_buffer image, uint32_t flags, uint32_t* invalid_out)
 {
+    const char* who = "rdx_accumulate";
     if (!g.initialized) return fail("rdx_init has not been called");
-    if (!colors || !known_buffer(colors)) return fail("rdx_accumulate: invalid colour buffer handle");
-    if (!scratch || !known_buffer(scratch)) return fail("rdx_accumulate: invalid scratch (imageScratch) buffer handle");
-    if (pixels && !known_buffer(pixels)) return fail("rdx_accumulate: invalid pixel buffer handle");
-    if (image && !known_buffer(image)) return fail("rdx_accumulate: invalid image buffer handle");
+    const CallRange R[4] = {{colors, colors_offset, (size_t)n * sizeof(float4), "colour", 16, true}, {pixels, pixels_offset, (size_t)n * sizeof(uint32_t), "pixel", 4, false},
+                            {scratch, 0, WHOLE_BUFFER, "scratch", 16, true}, {image, 0, WHOLE_BUFFER, "image", 4, false}};
+    if (check_call_handles(who, R)) return -1;
     if (flags & ~1u) return fail("rdx_accumulate: unknown flags 0x%x (bit 0 = debug)", flags);
     if (!pixels && (uint64_t)first_pixel + n > 0x100000000ull)
         return fail("rdx_accumulate: first_pixel + n (%u + %u) does not fit 32 bits", first_pixel, n);
+    if (check_call_ranges(who, R, 2, n, {invalid_out})) return -1;
+    if (!n) return 0;
     // the frame: whole pixels both buffers hold
     size_t npix = scratch->size / sizeof(float4);
     if (image) npix = std::min(npix, image->size / 4);
     npix = std::min<size_t>(npix, 0xffffffffu);
-    const FrameRange R[4] = {{colors, colors_offset, (size_t)n * sizeof(float4), "colour", 16}, {pixels, pixels_offset, (size_t)n * sizeof(uint32_t), "pixel", 4},
-                             {scratch, 0, scratch->size, "scratch", 16}, {image, 0, image ? image->size : 0, "image", 4}};
-    if (check_frame_ranges("rdx_accumulate", R, 4, 2, n)) return -1;
-    if (invalid_out) *invalid_out = 0;
-    if (!n) return 0;
-    auto at = [](rdx_buffer b, size_t off) { return b ? static_cast<char*>(b->dptr) + off : nullptr; };
     HIP_OK(hipMemsetAsync(g.dAccumInvalid, 0, sizeof(uint32_t), g.stream));
-    HIP_OK(hipEventRecord(g.evA, g.stream));
-    launch_accumulate_samples(g.stream, reinterpret_cast<const float4*>(at(colors, colors_offset)), n, first_pixel,
-                              reinterpret_cast<const uint32_t*>(at(pixels, pixels_offset)), frameID, static_cast<float4*>(scratch->dptr),
-                              image ? static_cast<uchar4*>(image->dptr) : nullptr, (uint32_t)npix, flags & 1u, g.dAccumInvalid);
-    HIP_OK(hipEventRecord(g.evB, g.stream));
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipStreamSynchronize(g.stream));
-    for (rdx_buffer b : {scratch, image}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    if (timed_launch(&rdx_trace_stats::ms_accumulate, {scratch, image}, [&] {
+            launch_accumulate_samples(g.stream, at<const float4>(colors, colors_offset), n, first_pixel, at<const uint32_t>(pixels, pixels_offset), frameID,
+                                      at<float4>(scratch), at<uchar4>(image), (uint32_t)npix, flags & 1u, g.dAccumInvalid); }))
+        return -1;
     uint32_t invalid = 0;
     HIP_OK(hipMemcpy(&invalid, g.dAccumInvalid, sizeof invalid, hipMemcpyDeviceToHost));
     if (invalid_out) *invalid_out = invalid;
-    std::memset(&g.stats, 0, sizeof g.stats);
-    HIP_OK(hipEventElapsedTime(&g.stats.ms_accumulate, g.evA, g.evB));      // kernel time of this call
     return 0;
 }
 
@@ -2696,30 +2586,26 @@ extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_off
                                uint32_t max_depth, const rdx_shading_buffers* scene, rdx_buffer radiance, size_t radiance_offset,
                                rdx_buffer hits, size_t hits_offset)
 {
+    const char* who = "rdx_trace_paths";
     if (!g.initialized) return fail("rdx_trace_paths: rdx_init has not been called");
     if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths: invalid TLAS handle");
-    if (!rays || !known_buffer(rays)) return fail("rdx_trace_paths: invalid ray buffer handle");
-    if (!keys || !known_buffer(keys)) return fail("rdx_trace_paths: invalid key buffer handle");
-    if (!radiance || !known_buffer(radiance)) return fail("rdx_trace_paths: invalid radiance buffer handle");
-    if (hits && !known_buffer(hits)) return fail("rdx_trace_paths: invalid hit buffer handle");
-    uint32_t samplerBits = 0;
-    if (check_shading_handles("rdx_trace_paths", scene, samplerBits)) return -1;
-    if (max_depth > 62) return fail("rdx_trace_paths: depth %u exceeds the supported maximum of 62", max_depth);
     static_assert(sizeof(rdx_ray) == 32 && sizeof(rdx_ray_hit) == 32 && sizeof(rdx_shade_key) == 16, "two float4 per ray and record, one uint4 per key");
-    const FrameRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16},
-                             {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16},
-                             {hits, hits_offset, (size_t)n * sizeof(rdx_ray_hit), "hit", 16}};
-    if (check_frame_ranges("rdx_trace_paths", R, 4, 2, n)) return -1;
+    const CallRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true},
+                            {hits, hits_offset, (size_t)n * sizeof(rdx_ray_hit), "hit", 16, false}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths: depth %u exceeds the supported maximum of 62", max_depth);
+    if (check_call_ranges(who, R, 2, n, {}, shading_aligned(scene))) return -1;
     if (!n) return 0;
-    if (check_shading_alignment("rdx_trace_paths", scene)) return -1;
     SceneArgs sc{};
-    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
-    sc.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr);
-    sc.indexData = static_cast<const uint32_t*>(scene->index->dptr);
-    sc.uvData = scene->uv ? static_cast<const float*>(scene->uv->dptr) : nullptr;
-    sc.normalData = static_cast<const float*>(scene->normal->dptr);
-    sc.materials = static_cast<const Material*>(scene->material->dptr);
-    if (shading_textures("rdx_trace_paths", scene, samplerBits, sc.tex)) return -1;
+    sc.scene = at<const SceneProperties>(scene->scene);
+    sc.meshInfo = at<const MeshInfo>(scene->meshInfo);
+    sc.indexData = at<const uint32_t>(scene->index);
+    sc.uvData = at<const float>(scene->uv);
+    sc.normalData = at<const float>(scene->normal);
+    sc.materials = at<const Material>(scene->material);
+    if (shading_textures(who, scene, samplerBits, sc.tex)) return -1;
     if (derive_accel(tlas)) return -1;
     const AccelCache& ac = *acc(tlas);
 
@@ -2732,10 +2618,10 @@ extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_off
         HIP_OK(hipMalloc(reinterpret_cast<void**>(&g.pathHits), (size_t)chunk * sizeof(rdx_ray_hit)));
         g.pathHitsCap = chunk;
     }
-    const float4* dRays = reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset);
-    const uint4* dKeys = reinterpret_cast<const uint4*>(static_cast<const char*>(keys->dptr) + keys_offset);
-    float4* dRad = reinterpret_cast<float4*>(static_cast<char*>(radiance->dptr) + radiance_offset);
-    float4* dHits = hits ? reinterpret_cast<float4*>(static_cast<char*>(hits->dptr) + hits_offset) : nullptr;
+    const float4* dRays = at<const float4>(rays, rays_offset);
+    const uint4* dKeys = at<const uint4>(keys, keys_offset);
+    float4* dRad = at<float4>(radiance, radiance_offset);
+    float4* dHits = at<float4>(hits, hits_offset);
 
     std::memset(&g.stats, 0, sizeof g.stats);
     std::memset(g.bounceCounts, 0, sizeof g.bounceCounts);
@@ -2782,7 +2668,7 @@ extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_off
     HIP_OK(hipEventRecord(g.evB, g.stream));
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(g.stream));
-    for (rdx_buffer b : {radiance, hits}) if (b) { ++b->version; b->mirrorValid = false; }      // device code wrote them
+    mark_written({radiance, hits});
     if (take_status()) return fail("rdx_trace_paths: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
     HIP_OK(hipEventElapsedTime(&g.stats.ms_total, g.evA, g.evB));
     g_timer.resolve();
@@ -2801,30 +2687,20 @@ extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t r
     const char* who = "rdx_trace_paths_lights";
     if (!g.initialized) return fail("rdx_trace_paths_lights: rdx_init has not been called");
     if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_lights: invalid TLAS handle");
-    if (!rays || !known_buffer(rays)) return fail("rdx_trace_paths_lights: invalid ray buffer handle");
-    if (!keys || !known_buffer(keys)) return fail("rdx_trace_paths_lights: invalid key buffer handle");
-    if (!radiance || !known_buffer(radiance)) return fail("rdx_trace_paths_lights: invalid radiance buffer handle");
+    // the SceneProperties is a row because the kernels of every depth read its lights: optional here only so that a NULL `scene` or
+    // a NULL handle in it is left to check_shading_handles
+    const CallRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
+                            {scene ? scene->scene : nullptr, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, false},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
     uint32_t samplerBits = 0;
-    if (check_shading_handles(who, scene, samplerBits)) return -1;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
     if (max_depth > 62) return fail("rdx_trace_paths_lights: depth %u exceeds the supported maximum of 62", max_depth);
     if (light_count > 5) return fail("rdx_trace_paths_lights: light_count %u exceeds the 5 lights of a SceneProperties", light_count);
     static_assert(sizeof(((SceneProperties*)nullptr)->lights) == 5 * sizeof(DirLight), "five DirLights");
-    const FrameRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16},
-                             {scene->scene, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4},
-                             {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16}};
-    if (check_frame_ranges(who, R, 4, 3, n)) return -1;
-    if (invalid_out) *invalid_out = 0;
+    if (check_call_ranges(who, R, 3, n, {invalid_out}, shading_aligned(scene))) return -1;
     if (!n) return 0;
-    if (check_shading_alignment(who, scene)) return -1;
-    ShadeScene sc{};
-    sc.scene = static_cast<const SceneProperties*>(scene->scene->dptr);
-    sc.s.meshInfo = static_cast<const MeshInfo*>(scene->meshInfo->dptr); sc.s.nMeshInfo = (uint32_t)std::min<size_t>(scene->meshInfo->size / sizeof(MeshInfo), 0xffffffffu);
-    sc.s.index = static_cast<const uint32_t*>(scene->index->dptr); sc.s.nIndex = scene->index->size / sizeof(uint32_t);
-    sc.s.normal = static_cast<const float*>(scene->normal->dptr); sc.s.nNormal = scene->normal->size / sizeof(float);
-    sc.materials = static_cast<const Material*>(scene->material->dptr); sc.nMaterials = (uint32_t)std::min<size_t>(scene->material->size / sizeof(Material), 0xffffffffu);
-    if (shading_textures(who, scene, samplerBits, sc.tex)) return -1;
-    if (sc.tex.flags & TEX_ENABLED) { sc.s.uv = static_cast<const float*>(scene->uv->dptr); sc.s.nUv = scene->uv->size / sizeof(float); }
-    if (derive_accel(tlas)) return -1;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
     const AccelCache& ac = *acc(tlas);
     const DirLight* lights = sc.scene->lights;       // a device address: read by the kernels of every call
 
@@ -2844,8 +2720,8 @@ extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t r
             g.lightScratchCap = need;
         }
     }
-    char* at = g.lightScratch;
-    auto take = [&](size_t bytesPerPath) { char* p = at; at += c256 * bytesPerPath; return p; };
+    char* cursor = g.lightScratch;
+    auto take = [&](size_t bytesPerPath) { char* p = cursor; cursor += c256 * bytesPerPath; return p; };
     float4* sHits = reinterpret_cast<float4*>(take(32));
     float4* sRays[2] = {reinterpret_cast<float4*>(take(32)), reinterpret_cast<float4*>(take(32))};
     uint4* sIds[2] = {reinterpret_cast<uint4*>(take(16)), reinterpret_cast<uint4*>(take(16))};
@@ -2856,9 +2732,9 @@ extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t r
     float4* sShadow = reinterpret_cast<float4*>(take(32 * (size_t)L));
     float4* sAny = reinterpret_cast<float4*>(take(32 * (size_t)L));
 
-    const float4* dRays = reinterpret_cast<const float4*>(static_cast<const char*>(rays->dptr) + rays_offset);
-    const uint4* dKeys = reinterpret_cast<const uint4*>(static_cast<const char*>(keys->dptr) + keys_offset);
-    float4* dRad = reinterpret_cast<float4*>(static_cast<char*>(radiance->dptr) + radiance_offset);
+    const float4* dRays = at<const float4>(rays, rays_offset);
+    const uint4* dKeys = at<const uint4>(keys, keys_offset);
+    float4* dRad = at<float4>(radiance, radiance_offset);
 
     std::memset(&g.stats, 0, sizeof g.stats);
     std::memset(g.bounceCounts, 0, sizeof g.bounceCounts);
@@ -2924,7 +2800,7 @@ extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t r
     HIP_OK(hipEventRecord(g.evB, g.stream));
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(g.stream));
-    ++radiance->version; radiance->mirrorValid = false;      // device code wrote it
+    mark_written({radiance});
     if (take_status()) return fail("rdx_trace_paths_lights: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
     uint32_t invalid = 0;
     HIP_OK(hipMemcpy(&invalid, g.dShadeCounts + 1, sizeof invalid, hipMemcpyDeviceToHost));

@@ -443,20 +443,29 @@ def QueryRays(tlas, rays, n, kind=QUERY_CLOSEST, hits=None, rays_offset=0, hits_
     return hits
 
 
+def _cuda_tensor(who, t, dtypes, shape, what, device=None, owner="rays"):
+    """-> n, the rows of `t`: a contiguous CUDA tensor of one of `dtypes` and of `shape` (shape[0] None: any n), on `device` (the
+    device of the owner's tensor) if one is given; anything else is a RadianceError"""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:])
+            and shape[0] in (None, t.shape[0]) and t.is_contiguous() and (device is None or t.device == device)):
+        raise RadianceError("%s: %s must be a contiguous %s CUDA tensor of shape (n,%s)%s"
+                            % (who, what, " / ".join(str(d).replace("torch.", "") for d in dtypes), "".join(" %d" % s for s in shape[1:]),
+                               " on the %s' device" % owner if device is not None else ""))
+    return int(t.shape[0])
+
+
 def QueryRaysTorch(tlas, rays_tensor, kind=QUERY_CLOSEST, out=None):
     """Extension: rays from a contiguous float32 CUDA tensor of shape (n, 8) -- origin, tmin, direction, tmax per row; the records
     land in `out`, an int32 (or float32) CUDA tensor of shape (n, 8) (created when None: int32; `.view(torch.float32)` shows t,
     b1, b2).  The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
     import torch
     t = rays_tensor
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 8 and t.is_contiguous()):
-        raise RadianceError("QueryRaysTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(t.shape[0])
+    n = _cuda_tensor("QueryRaysTorch", t, (torch.float32,), (None, 8), "rays")
     if out is None:
         out = torch.empty((n, 8), dtype=torch.int32, device=t.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.int32, torch.float32) and tuple(out.shape) == (n, 8)
-              and out.is_contiguous() and out.device == t.device):
-        raise RadianceError("QueryRaysTorch: out must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
+    else:
+        _cuda_tensor("QueryRaysTorch", out, (torch.int32, torch.float32), (n, 8), "out", t.device)
     torch.cuda.current_stream(t.device).synchronize()
     if n:
         rays = WrapDeviceMemory(None, t.data_ptr(), n * 32, keepalive=t)
@@ -518,17 +527,12 @@ def ResolveHitsTorch(tlas, rays_tensor, hits_tensor, scene_buffers, out=None):
     stream, so the current stream is synchronised first; the call blocks.  Returns (out, invalid)."""
     import torch
     r, h = rays_tensor, hits_tensor
-    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
-        raise RadianceError("ResolveHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(r.shape[0])
-    if not (isinstance(h, torch.Tensor) and h.is_cuda and h.dtype in (torch.int32, torch.float32) and tuple(h.shape) == (n, 8)
-            and h.is_contiguous() and h.device == r.device):
-        raise RadianceError("ResolveHitsTorch: hits must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
+    n = _cuda_tensor("ResolveHitsTorch", r, (torch.float32,), (None, 8), "rays")
+    _cuda_tensor("ResolveHitsTorch", h, (torch.int32, torch.float32), (n, 8), "hits", r.device)
     if out is None:
         out = torch.empty((n, 16), dtype=torch.float32, device=r.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 16)
-              and out.is_contiguous() and out.device == r.device):
-        raise RadianceError("ResolveHitsTorch: out must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device")
+    else:
+        _cuda_tensor("ResolveHitsTorch", out, (torch.float32,), (n, 16), "out", r.device)
     torch.cuda.current_stream(r.device).synchronize()
     invalid = 0
     if n:
@@ -550,6 +554,19 @@ def DebugSurfaceInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, n
     if rc < 0:
         raise RadianceError(_lib.last_error())
     return rc == 1
+
+
+def DebugCheckRanges(rows, first_out, n):
+    """Test seam (rdx_debug_check_ranges): the range rule of every device-resident call from QueryRays to TraceLightPaths, on plain
+    numbers, on the host.  rows: (name, address, size, offset, bytes, align, present) per range, inputs first; rows from
+    `first_out` on are outputs.  Returns None if the call would be accepted, else the refusal's text."""
+    rows = list(rows)
+    R = (_lib.rdx_debug_range * max(len(rows), 1))()
+    for k, (_, address, size, offset, nbytes, align, present) in enumerate(rows):
+        R[k] = _lib.rdx_debug_range(int(address), int(size), int(offset), int(nbytes), int(align), 1 if present else 0)
+    names = (C.c_char_p * max(len(rows), 1))(*[str(r[0]).encode() for r in rows])
+    rc = _lib.lib().rdx_debug_check_ranges(R, names, len(rows), int(first_out), int(n))
+    return None if rc == 0 else _lib.last_error()
 
 
 # ---- the stock closest-hit shader on a query's hits (rdx_shade_hits) --------------------------------------------------
@@ -584,6 +601,29 @@ class ShadingBuffers:
                                         self.material.handle, h(self.textureArray), h(self.sampler))
 
 
+def _shading_struct(who, scene_buffers):
+    """the rdx_shading_buffers of a ShadingBuffers, or of a tuple of its constructor's arguments"""
+    if not isinstance(scene_buffers, ShadingBuffers):
+        try:
+            scene_buffers = ShadingBuffers(*scene_buffers)
+        except TypeError:
+            raise RadianceError("%s: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
+                                "[, textureArray, sampler]) tuple" % who)
+    return scene_buffers._struct(who)
+
+
+def _out_buffer(who, n, buf, offset, rec, what, optional, or_true=None):
+    """an output argument: a Buffer; True, or None where it is not optional: created for n records of `rec` bytes behind `offset`;
+    None / False where it is optional: not wanted.  or_true: the refusal names True as a choice (default: where optional)"""
+    if buf is True or (buf is None and not optional):
+        return CreateBuffer(None, max(int(offset) + rec * n, 1))
+    if buf is None or buf is False:
+        return None
+    if not isinstance(buf, Buffer):
+        raise RadianceError("%s: %s must be a Buffer%s" % (who, what, ", True or None" if (optional if or_true is None else or_true) else " or None"))
+    return buf
+
+
 def ShadeHits(tlas, rays, hits, keys, n, scene_buffers, shade=None, next=True, shadow=True, src=None, compact=False, rays_offset=0,
               hits_offset=0, keys_offset=0, shade_offset=0, next_offset=0, shadow_offset=0, src_offset=0):
     """Extension: the stock closest-hit / miss shaders on the `n` RAY_HIT_DTYPE records QueryRays(..., QUERY_CLOSEST) wrote to `hits`
@@ -599,27 +639,12 @@ def ShadeHits(tlas, rays, hits, keys, n, scene_buffers, shade=None, next=True, s
     survivors; `invalid` hits that would read outside a scene buffer, zeroed and counted."""
     if not all(isinstance(b, Buffer) for b in (tlas, rays, hits, keys)):
         raise RadianceError("ShadeHits: tlas, rays, hits and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    if not isinstance(scene_buffers, ShadingBuffers):
-        try:
-            scene_buffers = ShadingBuffers(*scene_buffers)
-        except TypeError:
-            raise RadianceError("ShadeHits: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
-                                "[, textureArray, sampler]) tuple")
-    sb = scene_buffers._struct()
+    sb = _shading_struct("ShadeHits", scene_buffers)
     n = int(n)
-
-    def out(buf, offset, rec, what, optional):
-        if buf is True or (buf is None and not optional):
-            return CreateBuffer(None, max(int(offset) + rec * n, 1))
-        if buf is None or buf is False:
-            return None
-        if not isinstance(buf, Buffer):
-            raise RadianceError("ShadeHits: %s must be a Buffer%s" % (what, ", True or None" if optional else " or None"))
-        return buf
-    shade = out(shade, shade_offset, SHADE_DTYPE.itemsize, "shade", False)
-    next = out(next, next_offset, RAY_DTYPE.itemsize, "next", True)
-    shadow = out(shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
-    src = out(True if (src is None and compact) else src, src_offset, 4, "src", True)
+    shade = _out_buffer("ShadeHits", n, shade, shade_offset, SHADE_DTYPE.itemsize, "shade", False)
+    next = _out_buffer("ShadeHits", n, next, next_offset, RAY_DTYPE.itemsize, "next", True)
+    shadow = _out_buffer("ShadeHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
+    src = _out_buffer("ShadeHits", n, True if (src is None and compact) else src, src_offset, 4, "src", True)
     live, invalid = C.c_uint32(0), C.c_uint32(0)
     h = lambda b: b.handle if b is not None else None
     _check(_lib.lib().rdx_shade_hits(tlas.handle, rays.handle, int(rays_offset), hits.handle, int(hits_offset), keys.handle, int(keys_offset), n,
@@ -637,15 +662,9 @@ def ShadeHitsTorch(tlas, rays_t, hits_t, keys_t, scene_buffers, compact=True, sa
     first; the call blocks."""
     import torch
     r, h, k = rays_t, hits_t, keys_t
-    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
-        raise RadianceError("ShadeHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(r.shape[0])
-    if not (isinstance(h, torch.Tensor) and h.is_cuda and h.dtype in (torch.int32, torch.float32) and tuple(h.shape) == (n, 8)
-            and h.is_contiguous() and h.device == r.device):
-        raise RadianceError("ShadeHitsTorch: hits must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
-    if not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
-            and k.device == r.device):
-        raise RadianceError("ShadeHitsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
+    n = _cuda_tensor("ShadeHitsTorch", r, (torch.float32,), (None, 8), "rays")
+    _cuda_tensor("ShadeHitsTorch", h, (torch.int32, torch.float32), (n, 8), "hits", r.device)
+    _cuda_tensor("ShadeHitsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
     shade = torch.empty((n, 12), dtype=torch.float32, device=r.device)
     nxt = torch.empty((n, 8), dtype=torch.float32, device=r.device) if sample_next else None
     shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device)
@@ -695,13 +714,7 @@ def ResolveMaterials(tlas, rays, hits, n, scene_buffers, out=None, rays_offset=0
     are counted.  Returns (out, invalid)."""
     if not (isinstance(tlas, Buffer) and isinstance(rays, Buffer) and isinstance(hits, Buffer)):
         raise RadianceError("ResolveMaterials: tlas, rays and hits must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    if not isinstance(scene_buffers, ShadingBuffers):
-        try:
-            scene_buffers = ShadingBuffers(*scene_buffers)
-        except TypeError:
-            raise RadianceError("ResolveMaterials: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
-                                "[, textureArray, sampler]) tuple")
-    sb = scene_buffers._struct("ResolveMaterials")
+    sb = _shading_struct("ResolveMaterials", scene_buffers)
     if out is None:
         out = CreateBuffer(None, max(int(out_offset) + MATERIAL_RECORD_DTYPE.itemsize * int(n), 1))
     elif not isinstance(out, Buffer):
@@ -728,12 +741,7 @@ def LightHits(rays, materials, n, scene, light, lit=None, shadow=True, rays_offs
         lit = CreateBuffer(None, max(int(lit_offset) + 16 * n, 1))
     elif not isinstance(lit, Buffer):
         raise RadianceError("LightHits: lit must be a Buffer or None")
-    if shadow is True:
-        shadow = CreateBuffer(None, max(int(shadow_offset) + RAY_DTYPE.itemsize * n, 1))
-    elif shadow is None or shadow is False:
-        shadow = None
-    elif not isinstance(shadow, Buffer):
-        raise RadianceError("LightHits: shadow must be a Buffer, True or None")
+    shadow = _out_buffer("LightHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
     _check(_lib.lib().rdx_light_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), n, scene.handle, light, lit.handle,
                                      int(lit_offset), shadow.handle if shadow is not None else None, int(shadow_offset)))
     return lit, shadow
@@ -747,17 +755,12 @@ def ResolveMaterialsTorch(tlas, rays_tensor, hits_tensor, scene_buffers, out=Non
     stream is synchronised first; the call blocks.  Returns (out, invalid)."""
     import torch
     r, h = rays_tensor, hits_tensor
-    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
-        raise RadianceError("ResolveMaterialsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(r.shape[0])
-    if not (isinstance(h, torch.Tensor) and h.is_cuda and h.dtype in (torch.int32, torch.float32) and tuple(h.shape) == (n, 8)
-            and h.is_contiguous() and h.device == r.device):
-        raise RadianceError("ResolveMaterialsTorch: hits must be a contiguous int32 / float32 CUDA tensor of shape (n, 8) on the rays' device")
+    n = _cuda_tensor("ResolveMaterialsTorch", r, (torch.float32,), (None, 8), "rays")
+    _cuda_tensor("ResolveMaterialsTorch", h, (torch.int32, torch.float32), (n, 8), "hits", r.device)
     if out is None:
         out = torch.empty((n, 16), dtype=torch.float32, device=r.device)
-    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 16)
-              and out.is_contiguous() and out.device == r.device):
-        raise RadianceError("ResolveMaterialsTorch: out must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device")
+    else:
+        _cuda_tensor("ResolveMaterialsTorch", out, (torch.float32,), (n, 16), "out", r.device)
     torch.cuda.current_stream(r.device).synchronize()
     invalid = 0
     if n:
@@ -776,12 +779,8 @@ def LightHitsTorch(rays_t, materials_t, scene_buffer, light, want_shadow=True):
     blocks."""
     import torch
     r, m = rays_t, materials_t
-    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
-        raise RadianceError("LightHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(r.shape[0])
-    if not (isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float32 and tuple(m.shape) == (n, 16) and m.is_contiguous()
-            and m.device == r.device):
-        raise RadianceError("LightHitsTorch: materials must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device")
+    n = _cuda_tensor("LightHitsTorch", r, (torch.float32,), (None, 8), "rays")
+    _cuda_tensor("LightHitsTorch", m, (torch.float32,), (n, 16), "materials", r.device)
     if not isinstance(scene_buffer, Buffer):
         raise RadianceError("LightHitsTorch: scene_buffer must be a Buffer (the SceneProperties of descriptor slot 4)")
     light = int(light)
@@ -823,18 +822,9 @@ def ScatterHits(rays, materials, surfaces, keys, n, randoms=None, scatter=None, 
     if keys is not None and randoms is not None:
         raise RadianceError("ScatterHits: both keys and randoms given: only one of the two is allowed")
     n = int(n)
-
-    def out(buf, offset, rec, what, optional):
-        if buf is True or (buf is None and not optional):
-            return CreateBuffer(None, max(int(offset) + rec * n, 1))
-        if buf is None or buf is False:
-            return None
-        if not isinstance(buf, Buffer):
-            raise RadianceError("ScatterHits: %s must be a Buffer or None" % what)
-        return buf
-    scatter = out(scatter, scatter_offset, SCATTER_DTYPE.itemsize, "scatter", False)
-    next = out(next, next_offset, RAY_DTYPE.itemsize, "next", False)
-    src = out(True if (src is None and compact) else src, src_offset, 4, "src", True)
+    scatter = _out_buffer("ScatterHits", n, scatter, scatter_offset, SCATTER_DTYPE.itemsize, "scatter", False)
+    next = _out_buffer("ScatterHits", n, next, next_offset, RAY_DTYPE.itemsize, "next", False)
+    src = _out_buffer("ScatterHits", n, True if (src is None and compact) else src, src_offset, 4, "src", True, or_true=False)
     live = C.c_uint32(0)
     h = lambda b: b.handle if b is not None else None
     _check(_lib.lib().rdx_scatter_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), surfaces.handle, int(surfaces_offset),
@@ -852,21 +842,15 @@ def ScatterHitsTorch(rays_t, materials_t, surfaces_t, keys_t=None, randoms_t=Non
     cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
     import torch
     r, m, s, k, u = rays_t, materials_t, surfaces_t, keys_t, randoms_t
-    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
-        raise RadianceError("ScatterHitsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(r.shape[0])
+    n = _cuda_tensor("ScatterHitsTorch", r, (torch.float32,), (None, 8), "rays")
     for what, t in (("materials", m), ("surfaces", s)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (n, 16) and t.is_contiguous()
-                and t.device == r.device):
-            raise RadianceError("ScatterHitsTorch: %s must be a contiguous float32 CUDA tensor of shape (n, 16) on the rays' device" % what)
+        _cuda_tensor("ScatterHitsTorch", t, (torch.float32,), (n, 16), what, r.device)
     if (k is None) == (u is None):
         raise RadianceError("ScatterHitsTorch: exactly one of keys and randoms must be given")
-    if k is not None and not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
-                              and k.device == r.device):
-        raise RadianceError("ScatterHitsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
-    if u is not None and not (isinstance(u, torch.Tensor) and u.is_cuda and u.dtype == torch.float32 and tuple(u.shape) == (n, 4) and u.is_contiguous()
-                              and u.device == r.device):
-        raise RadianceError("ScatterHitsTorch: randoms must be a contiguous float32 CUDA tensor of shape (n, 4) on the rays' device")
+    if k is not None:
+        _cuda_tensor("ScatterHitsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
+    if u is not None:
+        _cuda_tensor("ScatterHitsTorch", u, (torch.float32,), (n, 4), "randoms", r.device)
     scatter = torch.empty((n, 4), dtype=torch.float32, device=r.device)
     nxt = torch.empty((n, 8), dtype=torch.float32, device=r.device)
     src = torch.empty((n,), dtype=torch.int32, device=r.device) if compact else None
@@ -928,16 +912,13 @@ def GenerateRaysTorch(camera, n_or_pixels, frame_id, total_samples, seeds=None):
     px = None
     if isinstance(n_or_pixels, torch.Tensor):
         px = n_or_pixels
-        if not (px.is_cuda and px.dtype == torch.int32 and px.dim() == 1 and px.is_contiguous()):
-            raise RadianceError("GenerateRaysTorch: pixels must be a contiguous int32 CUDA tensor of shape (n,)")
-        n, device = int(px.shape[0]), px.device
+        n, device = _cuda_tensor("GenerateRaysTorch", px, (torch.int32,), (None,), "pixels"), px.device
     elif isinstance(n_or_pixels, (int, np.integer)) and not isinstance(n_or_pixels, bool) and n_or_pixels >= 0:
         n, device = int(n_or_pixels), torch.device("cuda", torch.cuda.current_device())
     else:
         raise RadianceError("GenerateRaysTorch: the second argument is a ray count or an int32 CUDA tensor of pixel numbers")
-    if seeds is not None and not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and tuple(seeds.shape) == (n, 4)
-                                  and seeds.is_contiguous() and seeds.device == device):
-        raise RadianceError("GenerateRaysTorch: seeds must be a contiguous int32 CUDA tensor of shape (n, 4) on the pixels' device")
+    if seeds is not None:
+        _cuda_tensor("GenerateRaysTorch", seeds, (torch.int32,), (n, 4), "seeds", device, owner="pixels")
     rays = torch.empty((n, 8), dtype=torch.float32, device=device)
     keys = torch.empty((n, 4), dtype=torch.int32, device=device)
     torch.cuda.current_stream(device).synchronize()
@@ -970,12 +951,9 @@ def AccumulateTorch(colors, frame_id, scratch, image=None, pixels=None, debug=Fa
     current stream is synchronised first; the call blocks."""
     import torch
     c = colors
-    if not (isinstance(c, torch.Tensor) and c.is_cuda and c.dtype == torch.float32 and c.dim() == 2 and c.shape[1] == 4 and c.is_contiguous()):
-        raise RadianceError("AccumulateTorch: colors must be a contiguous float32 CUDA tensor of shape (n, 4)")
-    n = int(c.shape[0])
-    if pixels is not None and not (isinstance(pixels, torch.Tensor) and pixels.is_cuda and pixels.dtype == torch.int32 and tuple(pixels.shape) == (n,)
-                                   and pixels.is_contiguous() and pixels.device == c.device):
-        raise RadianceError("AccumulateTorch: pixels must be a contiguous int32 CUDA tensor of shape (n,) on the colours' device")
+    n = _cuda_tensor("AccumulateTorch", c, (torch.float32,), (None, 4), "colors")
+    if pixels is not None:
+        _cuda_tensor("AccumulateTorch", pixels, (torch.int32,), (n,), "pixels", c.device, owner="colours")
 
     def frame(t, dtype, what):
         if t is None or isinstance(t, Buffer):
@@ -1011,13 +989,7 @@ def TracePaths(tlas, rays, keys, n, max_depth, scene_buffers, radiance=None, hit
     (the hit buffer is `hits` where the caller passed one; rd.TracePaths(..., hits=True) returns (radiance, hits))."""
     if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
         raise RadianceError("TracePaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    if not isinstance(scene_buffers, ShadingBuffers):
-        try:
-            scene_buffers = ShadingBuffers(*scene_buffers)
-        except TypeError:
-            raise RadianceError("TracePaths: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
-                                "[, textureArray, sampler]) tuple")
-    sb = scene_buffers._struct("TracePaths")
+    sb = _shading_struct("TracePaths", scene_buffers)
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
             or max_depth < 0:
         raise RadianceError("TracePaths: n and max_depth must be non-negative integers")
@@ -1044,12 +1016,8 @@ def TracePathsTorch(tlas, rays_t, keys_t, max_depth, scene_buffers, want_hits=Fa
     The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
     import torch
     r, k = rays_t, keys_t
-    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
-        raise RadianceError("TracePathsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(r.shape[0])
-    if not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
-            and k.device == r.device):
-        raise RadianceError("TracePathsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
+    n = _cuda_tensor("TracePathsTorch", r, (torch.float32,), (None, 8), "rays")
+    _cuda_tensor("TracePathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
     if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
         raise RadianceError("TracePathsTorch: max_depth must be a non-negative integer")
     radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
@@ -1076,13 +1044,7 @@ def TraceLightPaths(tlas, rays, keys, n, max_depth, light_count, scene_buffers, 
     radiance_offset + 16 n bytes).  Device buffers in and out.  Returns (radiance, invalid)."""
     if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
         raise RadianceError("TraceLightPaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    if not isinstance(scene_buffers, ShadingBuffers):
-        try:
-            scene_buffers = ShadingBuffers(*scene_buffers)
-        except TypeError:
-            raise RadianceError("TraceLightPaths: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
-                                "[, textureArray, sampler]) tuple")
-    sb = scene_buffers._struct("TraceLightPaths")
+    sb = _shading_struct("TraceLightPaths", scene_buffers)
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
             or max_depth < 0:
         raise RadianceError("TraceLightPaths: n and max_depth must be non-negative integers")
@@ -1104,12 +1066,8 @@ def TraceLightPathsTorch(tlas, rays_t, keys_t, max_depth, light_count, scene_buf
     stream, so the current stream is synchronised first; the call blocks."""
     import torch
     r, k = rays_t, keys_t
-    if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.dim() == 2 and r.shape[1] == 8 and r.is_contiguous()):
-        raise RadianceError("TraceLightPathsTorch: rays must be a contiguous float32 CUDA tensor of shape (n, 8)")
-    n = int(r.shape[0])
-    if not (isinstance(k, torch.Tensor) and k.is_cuda and k.dtype == torch.int32 and tuple(k.shape) == (n, 4) and k.is_contiguous()
-            and k.device == r.device):
-        raise RadianceError("TraceLightPathsTorch: keys must be a contiguous int32 CUDA tensor of shape (n, 4) on the rays' device")
+    n = _cuda_tensor("TraceLightPathsTorch", r, (torch.float32,), (None, 8), "rays")
+    _cuda_tensor("TraceLightPathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
     if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
         raise RadianceError("TraceLightPathsTorch: max_depth must be a non-negative integer")
     light_count = _light_count("TraceLightPathsTorch", light_count)
