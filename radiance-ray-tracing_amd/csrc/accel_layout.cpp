@@ -185,7 +185,7 @@ void quad_order(int arr, int ord[4])
     ord[2] = h1 + ((arr >> 2) & 1); ord[3] = h1 + 1 - ((arr >> 2) & 1);
 }
 
-struct BlasInfo { uint32_t nodeBase; uint32_t need; uint32_t coopNeed; uint32_t anyNeed; uint32_t triBase; uint32_t rootDesc0, rootDesc1; float rootMin[3], rootMax[3];
+struct BlasInfo { uint32_t nodeBase; uint32_t need; uint32_t coopNeed; uint32_t coopPieces; uint32_t anyNeed; uint32_t triBase; uint32_t rootDesc0, rootDesc1; float rootMin[3], rootMax[3];
                   uint32_t nTris; uint32_t users;
                   uint32_t quadNeed;        // pool-stack need of the quad walk from its root (0: leaf root, or no quad records)
                   uint32_t owner;           // DTri._p0 of its triangles: the slot of its one instance (group / unified tree), or 0xffffffff
@@ -381,6 +381,11 @@ int Deriver::blas_wide_records(const BlobNode* bn, uint32_t nNodes, uint32_t tri
     // max(1 + left, right).  Children have larger indices than their parent (DFS pre-order).
     std::vector<uint32_t> aneed(nNodes, 0);                     // any push order: 1 + the deeper inner child
     std::vector<uint32_t> cneed(nNodes, 0), wneed(nNodes, 0);   // wneed: per-lane wide kernel on the same records (pushes leaves too)
+    std::vector<uint32_t> pneed(nNodes, 0);                     // cneed + the leaf pieces the cooperative kernel stacks
+    auto leaf_pieces = [](const BlobNode& n) {                  // stack entries of a leaf child: all but its last 8-triangle piece
+        const uint32_t cnt = n.w2 == TYPE_TRIG ? std::min(n.w0 & 0x7fffffffu, (uint32_t)WIDE_MAX_LEAF_TRIS) : 0u;
+        return cnt ? (cnt - 1u) / 8u : 0u;
+    };
     for (uint32_t i = nNodes; i-- > 0;) {
         if (bn[i].w0 & LEAF_BIT) continue;
         uint32_t a = bn[i].w0, b = bn[i].w1;
@@ -393,7 +398,13 @@ int Deriver::blas_wide_records(const BlobNode* bn, uint32_t nNodes, uint32_t tri
             cneed[i] = la ? (lb ? 0u : cneed[b]) : cneed[a];
             aneed[i] = la ? (lb ? 0u : aneed[b]) : aneed[a];
         }
-        wneed[i] = std::max(1u + wneed[a], wneed[b]);
+        // Kernels that keep a lane's work on a stack (per-lane wide kernel, cooperative kernel) put all but the last 8-triangle
+        // piece of an oversized leaf child there, and those entries stay while the record's other child is walked: the pieces
+        // of every oversized leaf along a path are on the stack together, so they are part of the recurrence.  (The pool
+        // engine queues leaf triangles and keeps no such entries: cneed / aneed stay free of them.)
+        const uint32_t pieces = (la ? leaf_pieces(bn[a]) : 0u) + (lb ? leaf_pieces(bn[b]) : 0u);
+        wneed[i] = pieces + std::max(1u + wneed[a], wneed[b]);
+        pneed[i] = pieces + ((!la && !lb) ? std::max(1u + pneed[a], pneed[b]) : (la ? (lb ? 0u : pneed[b]) : pneed[a]));
         DWide& w = dW[wideBase + wideIdx[i]];
         const BlobNode& Ln = bn[a]; const BlobNode& Rn = bn[b];
         for (int k = 0; k < 3; ++k) { w.lmin[k] = Ln.bottom[k]; w.lmax[k] = Ln.top[k]; w.rmin[k] = Rn.bottom[k]; w.rmax[k] = Rn.top[k]; }
@@ -401,6 +412,7 @@ int Deriver::blas_wide_records(const BlobNode* bn, uint32_t nNodes, uint32_t tri
         desc(b, w.rd0, w.rd1);
     }
     info.need = std::max(blas_need(bn, 0), wneed[0]); info.coopNeed = cneed[0]; info.anyNeed = aneed[0];
+    info.coopPieces = pneed[0] - cneed[0];
     desc(0, info.rootDesc0, info.rootDesc1);
     return 0;
 }
@@ -750,15 +762,16 @@ int Deriver::top_level_needs()
         const BlobNode& n = tnodes[i];
         if (n.w0 & LEAF_BIT) {
             const uint32_t cnt = n.w0 & 0x7fffffffu;
-            uint32_t mx = 0, mxc = 0;
+            uint32_t mx = 0, mxc = 0, mxp = 0;
             for (uint32_t k = 0; k < cnt; ++k) {
                 const BlasInfo& bi = blasAt[binst[n.w1 + k].instanceOffset];
                 mx = std::max(mx, bi.need); mxc = std::max(mxc, bi.coopNeed); maxBlasAny = std::max(maxBlasAny, bi.anyNeed);
+                mxp = std::max(mxp, bi.coopNeed + bi.coopPieces);
             }
             maxBlasCoop = std::max(maxBlasCoop, mxc);
             needTopOnly[i] = (cnt + 15u) / 16u;
             needT[i] = (cnt ? cnt - 1 : 0) + mx;
-            needC[i] = (cnt + 15u) / 16u + mxc;
+            needC[i] = (cnt + 15u) / 16u + mxp;       // (the cooperative kernel's stack: with the leaf pieces along a path)
         } else {
             needT[i] = std::max(1u + needT[n.w0], needT[n.w1]);   // children have larger indices (DFS pre-order)
             // cooperative kernel: its own copy of the top-level nodes with the smaller-need child in the followed slot
@@ -815,7 +828,7 @@ void Deriver::make_book()
         AccelBlasBlock b{};
         b.relOffset = (uint32_t)(kv.first - regionStart);
         b.nodeBase = bi.nodeBase; b.triBase = bi.triBase; b.nTris = bi.nTris;
-        b.need = bi.need; b.coopNeed = bi.coopNeed; b.anyNeed = bi.anyNeed; b.quadNeed = bi.quadNeed;
+        b.need = bi.need; b.coopNeed = bi.coopNeed; b.anyNeed = bi.anyNeed; b.quadNeed = bi.quadNeed; b.coopPieces = bi.coopPieces;
         b.rootDesc0 = bi.rootDesc0; b.rootDesc1 = bi.rootDesc1;
         for (int k = 0; k < 3; ++k) { b.rootMin[k] = bi.rootMin[k]; b.rootMax[k] = bi.rootMax[k]; }
         b.owner = bi.owner;
@@ -856,7 +869,7 @@ int update_accel_layout(const void* blob, size_t size, const AccelOptions& opt, 
     for (const AccelBlasBlock& b : B.blocks) {
         BlasInfo bi{};
         bi.nodeBase = b.nodeBase; bi.triBase = b.triBase; bi.nTris = b.nTris;
-        bi.need = b.need; bi.coopNeed = b.coopNeed; bi.anyNeed = b.anyNeed; bi.quadNeed = b.quadNeed;
+        bi.need = b.need; bi.coopNeed = b.coopNeed; bi.anyNeed = b.anyNeed; bi.quadNeed = b.quadNeed; bi.coopPieces = b.coopPieces;
         bi.rootDesc0 = b.rootDesc0; bi.rootDesc1 = b.rootDesc1;
         for (int k = 0; k < 3; ++k) { bi.rootMin[k] = b.rootMin[k]; bi.rootMax[k] = b.rootMax[k]; }
         bi.users = 0; bi.owner = 0xffffffffu;

@@ -26,6 +26,7 @@ struct AccelBlasBlock {
     uint32_t relOffset;                // byte offset of the BLAS inside the blob's BLAS region (which starts behind the instance records)
     uint32_t nodeBase, triBase, nTris; // its blocks in bnodes / tris
     uint32_t need, coopNeed, anyNeed, quadNeed;      // stack needs of the engines inside this BLAS
+    uint32_t coopPieces;               // what the cooperative kernel's stack needs on top of coopNeed: leaf pieces along a path
     uint32_t rootDesc0, rootDesc1;     // root of its wide records, as in DInst
     float rootMin[3], rootMax[3];
     uint32_t owner;                    // DTri._p0 of its triangles as the arrays stand: an instance slot, or 0xffffffff

@@ -18,7 +18,9 @@
 // depend on evaluation order except for the sign of a zero, and a zero's sign cannot change a
 // `cost < minCost` decision, so the chosen (axis, plane) is identical; the boxes that are WRITTEN to
 // the blob are then recomputed in the reference's own sequential order, which makes them
-// bit-identical including zero signs.
+// bit-identical including zero signs.  A node that holds a primitive with a NaN or infinite box or
+// centroid coordinate is outside that argument and evaluates its candidates in the reference's literal
+// order (Builder::sweep_literal); it is never binned on the GPU.
 //
 // Compiled with -ffp-contract=off: every float expression below is evaluated exactly as written.
 #include "bvh_build.h"
@@ -49,6 +51,8 @@ const V3 kSmall{-FLT_MAX, -FLT_MAX, -FLT_MAX};
 
 struct Prim { V3 lo, hi, c; uint32_t id; };
 struct Box { V3 lo, hi; };
+inline bool all_finite(const V3& v) { return std::isfinite(v.x) && std::isfinite(v.y) && std::isfinite(v.z); }
+inline bool is_hostile(const Prim& p) { return !(all_finite(p.lo) && all_finite(p.hi) && all_finite(p.c)); }
 inline float half_area(const Box& b)
 {
     float s1 = b.hi.x - b.lo.x, s2 = b.hi.y - b.lo.y, s3 = b.hi.z - b.lo.z;
@@ -81,7 +85,7 @@ inline uint32_t bin_of(const std::vector<float>& t, float start, float invStep, 
 {
     const size_t K = t.size();
     float e = (c - start) * invStep - 1.0f;           // t_k ~ start + (k + 1) step
-    size_t b = e <= 0.0f ? 0 : (e >= (float)K ? K : (size_t)e);
+    size_t b = !(e > 0.0f) ? 0 : (e >= (float)K ? K : (size_t)e);       // (a NaN estimate is never converted: it starts at 0)
     while (b < K && !(c < t[b])) ++b;
     while (b > 0 && c < t[b - 1]) --b;
     return (uint32_t)b;
@@ -154,6 +158,7 @@ inline int helper_limit()
 
 struct Builder {
     const std::vector<Prim>& P;
+    const std::vector<uint8_t>& hostile;     // per primitive: a box or centroid coordinate is NaN or infinite (empty: none is)
     std::string& err;
     uint64_t gpuHandle;             // the BLAS's primitives on the GPU (0 = none)
     // scratch reused across nodes
@@ -161,7 +166,7 @@ struct Builder {
     std::vector<Box> suf;
     std::vector<float> gpuOut;
 
-    Builder(const std::vector<Prim>& p, std::string& e, uint64_t gh) : P(p), err(e), gpuHandle(gh) {}
+    Builder(const std::vector<Prim>& p, const std::vector<uint8_t>& h, std::string& e, uint64_t gh) : P(p), hostile(h), err(e), gpuHandle(gh) {}
 
     std::unique_ptr<Node> make_leaf(const std::vector<uint32_t>& work)
     {
@@ -172,7 +177,26 @@ struct Builder {
         return n;
     }
 
-    std::unique_ptr<Node> recurse(const std::vector<uint32_t>& work, int depth)
+    // bvh.cpp:123-205 as written: every candidate re-scans the work list, boxes grow in work order
+    void sweep_literal(const std::vector<uint32_t>& work, const std::vector<float>& t, int axis, SplitChoice& best)
+    {
+        for (float testSplit : t) {
+            Box l{kBig, kSmall}, r{kBig, kSmall};
+            int countLeft = 0, countRight = 0;
+            for (uint32_t w : work) {
+                const Prim& p = P[w];
+                if (comp(p.c, axis) < testSplit) { l.lo = vmin(l.lo, p.lo); l.hi = vmax(l.hi, p.hi); countLeft++; }
+                else { r.lo = vmin(r.lo, p.lo); r.hi = vmax(r.hi, p.hi); countRight++; }
+            }
+            if (countLeft <= 1 || countRight <= 1) continue;
+            float totalCost = half_area(l) * countLeft + half_area(r) * countRight;
+            if (totalCost < best.minCost) { best.minCost = totalCost; best.bestSplit = testSplit; best.bestAxis = axis; }
+        }
+    }
+
+    // mayBeHostile: the parent's work list held a hostile primitive (the root: the mesh does).  Finite meshes, and finite subtrees
+    // of the others, never look at the flags.
+    std::unique_ptr<Node> recurse(const std::vector<uint32_t>& work, int depth, bool mayBeHostile)
     {
         const size_t n = work.size();
         if (n < 8) return make_leaf(work);
@@ -193,8 +217,13 @@ struct Builder {
             if (!make_candidates(start, stop, depth, cand[axis], steps[axis], err)) return nullptr;
             axisOn[axis] = true;
         }
+        // A primitive whose box or centroid is not finite: min / max then depend on the order of evaluation (`a < b ? a : b`
+        // keeps or drops a NaN by its position), so the bins' prefix / suffix unions are not the reference's boxes.  Such a
+        // node evaluates every candidate in the reference's literal order, on the host.
+        bool literal = false;
+        if (mayBeHostile) for (uint32_t w : work) literal = literal || hostile[w] != 0;
         bool onGpu = false;
-        if (gpuHandle && g_gpuBinner && n >= g_gpuMin) {
+        if (!literal && gpuHandle && g_gpuBinner && n >= g_gpuMin) {
             // layout of the answer: per axis [K + 1] counts, then [K + 1] x {lo.xyz, hi.xyz}
             onGpu = g_gpuBinner->bin(gpuHandle, work.data(), n, cand, gpuOut);
         }
@@ -202,6 +231,7 @@ struct Builder {
         for (int axis = 0; axis < 3; ++axis) {
             if (!axisOn[axis]) continue;
             const size_t K = cand[axis].size();
+            if (literal) { sweep_literal(work, cand[axis], axis, best); continue; }
             bins.t.swap(cand[axis]);
             if (onGpu) {
                 bins.cnt.resize(K + 1); bins.box.resize(K + 1);
@@ -248,21 +278,21 @@ struct Builder {
             if (g_helpers.fetch_add(1) < helper_limit()) {
                 try {
                     helper = std::thread([&]() {
-                        Builder B2(P, rightErr, gpuHandle);
-                        rightNode = B2.recurse(right, depth + 1);
+                        Builder B2(P, hostile, rightErr, gpuHandle);
+                        rightNode = B2.recurse(right, depth + 1, literal);
                     });
                     spawned = true;
                 } catch (const std::system_error&) { spawned = false; }      // (no thread to be had: this one does both)
             }
             if (!spawned) g_helpers.fetch_sub(1);
         }
-        inner->left = recurse(left, depth + 1);
+        inner->left = recurse(left, depth + 1, literal);
         if (spawned) {
             helper.join();
             g_helpers.fetch_sub(1);
             if (!rightNode && err.empty()) err = rightErr;
         } else if (inner->left) {
-            rightNode = recurse(right, depth + 1);
+            rightNode = recurse(right, depth + 1, literal);
         }
         if (!inner->left || !rightNode) return nullptr;
         inner->left->lo = lb.lo; inner->left->hi = lb.hi;
@@ -308,6 +338,7 @@ Blas* build_blas(const float* v, uint32_t nverts, const uint32_t* idx, uint32_t 
         if (idx[i] >= nverts) { err = "BuildAccelStruct(Mesh): vertex index out of range"; return nullptr; }
 
     std::vector<Prim> prims(ntris);
+    std::vector<uint8_t> hostile;
     V3 bottom = kBig, top = kSmall;
     for (uint32_t j = 0; j < ntris; ++j) {
         Prim& b = prims[j];
@@ -319,6 +350,7 @@ Blas* build_blas(const float* v, uint32_t nverts, const uint32_t* idx, uint32_t 
         b.hi = vmax(b.hi, p0); b.hi = vmax(b.hi, p1); b.hi = vmax(b.hi, p2);
         bottom = vmin(bottom, b.lo); top = vmax(top, b.hi);
         b.c = V3{(b.hi.x + b.lo.x) * 0.5f, (b.hi.y + b.lo.y) * 0.5f, (b.hi.z + b.lo.z) * 0.5f};
+        if (is_hostile(b)) { if (hostile.empty()) hostile.assign(ntris, 0); hostile[j] = 1; }
     }
     std::vector<uint32_t> work(ntris);
     std::iota(work.begin(), work.end(), 0u);
@@ -333,8 +365,8 @@ Blas* build_blas(const float* v, uint32_t nverts, const uint32_t* idx, uint32_t 
         }
         gpuHandle = g_gpuBinner->upload(flat.data(), ntris);
     }
-    Builder B(prims, err, gpuHandle);
-    std::unique_ptr<Node> root = B.recurse(work, 0);
+    Builder B(prims, hostile, err, gpuHandle);
+    std::unique_ptr<Node> root = B.recurse(work, 0, !hostile.empty());
     if (gpuHandle) g_gpuBinner->release(gpuHandle);
     if (!root) return nullptr;
     root->lo = bottom; root->hi = top;
@@ -371,6 +403,7 @@ static bool build_tlas_impl(const InstanceDesc* inst, uint32_t ninst, std::vecto
 {
     if (ninst == 0) { err = "BuildAccelStruct(instances): empty instance list"; return false; }
     std::vector<Prim> prims(ninst);
+    std::vector<uint8_t> hostile;
     V3 bottom = kBig, top = kSmall;
     for (uint32_t k = 0; k < ninst; ++k) {
         const Blas* bl = inst[k].blas;
@@ -400,12 +433,13 @@ static bool build_tlas_impl(const InstanceDesc* inst, uint32_t ninst, std::vecto
         b.hi = vmax(vmax(vmax(hiCol[3], hiCol[2]), vmax(hiCol[1], hiCol[0])),
                     vmax(vmax(loCol[3], loCol[2]), vmax(loCol[1], loCol[0])));
         b.c = V3{(b.hi.x + b.lo.x) * 0.5f, (b.hi.y + b.lo.y) * 0.5f, (b.hi.z + b.lo.z) * 0.5f};
+        if (is_hostile(b)) { if (hostile.empty()) hostile.assign(ninst, 0); hostile[k] = 1; }
         bottom = vmin(bottom, b.lo); top = vmax(top, b.hi);
     }
     std::vector<uint32_t> work(ninst);
     std::iota(work.begin(), work.end(), 0u);
-    Builder B(prims, err, 0);
-    std::unique_ptr<Node> root = B.recurse(work, 0);
+    Builder B(prims, hostile, err, 0);
+    std::unique_ptr<Node> root = B.recurse(work, 0, !hostile.empty());
     if (!root) return false;
     root->lo = bottom; root->hi = top;
 

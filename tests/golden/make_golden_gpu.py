@@ -29,6 +29,16 @@ Third entry point:
 
     python tests/golden/make_golden_gpu.py shadeedges [DIR]   # on the MI355X; writes DIR/refgpu_shade_edges.npz
 
+Fourth entry point:
+
+    python tests/golden/make_golden_gpu.py meshedges [DIR]    # on the MI355X; writes DIR/refgpu_meshedges.npz
+
+refgpu_meshedges.npz  the reference's intersectTop on hostile geometry: every case of tests/mesh_edge_cases.py (NaN / infinite /
+                      overflowing / denormal coordinates, degenerate and identical triangles, flat meshes, centroids on candidate
+                      planes, signed zeros, lopsided deep trees, hostile instances), its rays at the stock interval and at
+                      (0, FLT_MAX), closest hit (sbt 1: full HitData) and any hit (sbt 2: flags), and the blob's SHA-256.  Data only:
+                      meshes and rays are rebuilt from mesh_edge_cases.py at test time.  Layout: as refgpu_rayedges.npz, per case.
+
 refgpu_shade_edges.npz  the reference's `material`, microfacetBRDF, raygen (frames, the tone map alone at batchSize 0, the running
                       mean alone at depth 0) and generateRay on the edge inputs of tests/shade_edge_cases.py (layout: there).
 
@@ -148,6 +158,25 @@ def rayedges(out_dir=OUT):
     print("refgpu_rayedges.npz: %d bytes" % os.path.getsize(path), flush=True)
 
 
+def meshedges(out_dir=OUT):
+    import mesh_edge_cases as mec
+    import ray_edge_cases as rec
+    os.makedirs(out_dir, exist_ok=True)
+    ref = rg.RefGpu("p")
+    out = {}
+    for c in mec.all_cases():
+        blob = mec.product_blob(rd, c)[0]
+        tl = rg.DevBuf.of(np.frombuffer(blob, np.uint8))
+        cells = mec.cells(c)
+        results = [(ref.trace(tl, x.o, x.d, x.tmin, x.tmax, 1), ref.trace(tl, x.o, x.d, x.tmin, x.tmax, 2)) for x in cells]
+        out.update(rec.pack_scene(c.name, gc.sha(blob), {}, results))
+        print("%s: %d cells, %d rays, %d closest hits, %d any hits" % (c.name, len(cells), sum(x.n for x in cells),
+              sum(int((r["hit"] == 1).sum()) for r, _ in results), sum(int((r["hit"] == 1).sum()) for _, r in results)), flush=True)
+    path = os.path.join(out_dir, "refgpu_meshedges.npz")
+    save_npz_reproducibly(path, out)
+    print("refgpu_meshedges.npz: %d arrays, %d bytes" % (len(out), os.path.getsize(path)), flush=True)
+
+
 def shadeedges(out_dir=OUT):
     import shade_edge_cases as se
     os.makedirs(out_dir, exist_ok=True)
@@ -160,6 +189,8 @@ def shadeedges(out_dir=OUT):
 if __name__ == "__main__":
     if sys.argv[1:2] == ["rayedges"]:
         rayedges(*[os.path.abspath(a) for a in sys.argv[2:3]])
+    elif sys.argv[1:2] == ["meshedges"]:
+        meshedges(*[os.path.abspath(a) for a in sys.argv[2:3]])
     elif sys.argv[1:2] == ["shadeedges"]:
         shadeedges(*[os.path.abspath(a) for a in sys.argv[2:3]])
     else:
