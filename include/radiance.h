@@ -211,6 +211,17 @@ inline void LightHits(Platform*, Buffer rays, Buffer materials, uint32_t n, Buff
     if (rdx_light_hits(rays, raysOffset, materials, materialsOffset, n, scene, light, lit, litOffset, shadow, shadowOffset)) detail::fatal("LightHits");
 }
 
+// Extension (no reference counterpart; rdx_punctual_light_hits): LightHits for record `index` of the caller's light table `lights`
+// (rdx_punctual_light records in device memory, the first at lightsOffset): directional, point or spot.  The shadow ray towards a
+// point or spot light ends at the light; a record that is dark at a hit gives zeros in `lit` and `shadow`.
+inline void PunctualLightHits(Platform*, Buffer rays, Buffer materials, uint32_t n, Buffer lights, uint32_t index, Buffer lit, Buffer shadow = nullptr,
+                              size_t raysOffset = 0, size_t materialsOffset = 0, size_t lightsOffset = 0, size_t litOffset = 0, size_t shadowOffset = 0)
+{
+    if (rdx_punctual_light_hits(rays, raysOffset, materials, materialsOffset, n, lights, lightsOffset + sizeof(rdx_punctual_light) * (size_t)index, lit,
+                                litOffset, shadow, shadowOffset))
+        detail::fatal("PunctualLightHits");
+}
+
 // Extension (no reference counterpart; rdx_scatter_hits): the next ray of the `n` material records `materials` (rdx_resolve_materials')
 // and surface records `surfaces` (rdx_resolve_hits') and the directions of `rays` -- the stock shader's next-direction sample, with
 // pcg3d of the rdx_shade_key records `keys` as the random numbers, or with the float4 records `randoms` (exactly one of the two is
@@ -278,6 +289,21 @@ inline uint32_t TraceLightPaths(Platform*, TopAccelStruct accelStruct, Buffer ra
     uint32_t invalid = 0;
     if (rdx_trace_paths_lights(accelStruct, rays, raysOffset, keys, keysOffset, n, maxDepth, lightCount, &scene, radiance, radianceOffset, &invalid))
         detail::fatal("TraceLightPaths");
+    return invalid;
+}
+
+// Extension (no reference counterpart; rdx_trace_paths_punctual): TraceLightPaths with the first `lightCount` (0 ..
+// RDX_MAX_PATH_LIGHTS) records of the caller's light table `lights` sampled at every hit in the place of the scene's directional
+// lights -- the path tracer over ResolveHits / ResolveMaterials / PunctualLightHits / ScatterHits in one call.  Returns the number
+// of hits that `scene` does not describe (they count as misses).
+inline uint32_t TracePunctualPaths(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer keys, uint32_t n, uint32_t maxDepth, Buffer lights,
+                                   uint32_t lightCount, const rdx_shading_buffers& scene, Buffer radiance, size_t raysOffset = 0, size_t keysOffset = 0,
+                                   size_t lightsOffset = 0, size_t radianceOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_trace_paths_punctual(accelStruct, rays, raysOffset, keys, keysOffset, n, maxDepth, lights, lightsOffset, lightCount, &scene, radiance,
+                                 radianceOffset, &invalid))
+        detail::fatal("TracePunctualPaths");
     return invalid;
 }
 

@@ -585,7 +585,8 @@ int         rdx_trace_paths(rdx_buffer tlas,
  * materials (csrc/shade.h shade_in_bounds, asked before and after the index gather) and must name an instance the TLAS carries, so
  * `scene` buffers that do not describe the scene of `tlas` cannot make a kernel read outside a buffer: such a hit is a miss and is
  * counted in *invalid_out (optional).  Textures follow the rule of rdx_shade_hits (option "textures" 1 and a textureArray; uv
- * required then).  User closest-hit programs do not run here; point and area lights do not exist; one device.
+ * required then).  User closest-hit programs do not run here; lights with a position are rdx_trace_paths_punctual's (below), area lights do not
+ * exist; one device.
  * Nothing is staged through the host: the library reads back ONE 32-bit word per bounce, the survivors' count that sizes the next
  * launches.  Internal streams of 192 + 80 light_count bytes per path of a chunk grow on first use and are reused.  More than
  * "chunk_paths" paths are traced in chunks of that many.  The call blocks, derives the traversal layout if none exists yet, sees
@@ -606,7 +607,68 @@ int         rdx_trace_paths_lights(rdx_buffer tlas,
                                    rdx_buffer radiance, size_t radiance_offset,  /* out: float4 per path: rgb, w = 0 */
                                    uint32_t* invalid_out);                       /* optional */
 
-/* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_lights applies to the byte ranges it is given, on plain
+/* Point and spot lights, from a light TABLE of the caller's own in device memory: records of 64 bytes, each directional, point or
+ * spot, read ON THE DEVICE by every call.  Two calls on the two levels of the light API above: rdx_punctual_light_hits is
+ * rdx_light_hits for one record of the table, rdx_trace_paths_punctual is rdx_trace_paths_lights over its first light_count
+ * records.  Neither changes rdx_light_hits or rdx_trace_paths_lights.
+ * rdx_punctual_light_hits: rays, materials, n, lit and shadow are those of rdx_light_hits; the light is the ONE record at byte
+ * offset light_offset (index * 64) of `lights`.  For a material record with hit == 1, every float32 operation rounded on its own,
+ * with N, V, normalize (v_rsq_f32 based, as everywhere in the library), microfacetBRDF and clamp exactly those of rdx_light_hits:
+ *   type 0  L = normalize(-direction), E = color, tmax = 1000.0f: bit for bit rdx_light_hits on a DirLight {direction, color};
+ *   type 1, 2  v = position - above (three subtractions); d2 = (v.x * v.x + v.y * v.y) + v.z * v.z (plain products and sums, not
+ *           fused); L = normalize(v); att = 1.0f / d2; E = color * att; tmax = sqrtf(d2) -- the shadow ray ends AT the light;
+ *   type 2  in addition S = normalize(direction); c = -((S.x * L.x + S.y * L.y) + S.z * L.z); f = clamp(c * coneScale + coneOffset,
+ *           0.0f, 1.0f) (a multiplication, then an addition); E = E * (f * f);
+ *   DARK    the record is dark at the hit if type > 2; or, types 1 and 2, !(d2 > 0.0f), !(d2 < INFINITY), or range > 0.0f &&
+ *           !(d2 < range * range); or, type 2, !(f > 0.0f);
+ *   else    lit.rgb = (0, 0, 0) + microfacetBRDF(L, V, N, albedo, metallic, roughness, transmission) * E, lit.w = 0, and the shadow
+ *           record (optional) is (above | 0.001f, L | tmax), ready for rdx_query_rays(..., RDX_QUERY_ANY, ...).
+ * A dark record and any other value of `hit` give 16 zero bytes in `lit` and 32 in `shadow` (tmax 0 accepts nothing).  The kernel
+ * gathers nothing but the one record, so no record can make it read outside a buffer; non-finite fields give unspecified colours,
+ * never a fault.  The call blocks; rdx_get_trace_stats().ms_shade is the kernel time.  Refused, before anything is launched: what
+ * rdx_light_hits refuses for rays / materials / lit / shadow; a NULL or unknown `lights`; a light_offset that is not a multiple of
+ * 16; 64 bytes at light_offset that do not fit `lights`; an output range that overlaps the light.  n == 0 succeeds and touches
+ * nothing.
+ * rdx_trace_paths_punctual: the per-path specification of rdx_trace_paths_lights, word for word, with "light j of the
+ * SceneProperties via rdx_light_hits" read as "record j of the table (at lights_offset + 64 j) via rdx_punctual_light_hits", and
+ * the shadow rays carrying that call's tmax: direct = ((0 + x_0) + x_1) + ..., x_j = occluded_j ? 0 : lit_j; a record that is dark
+ * at a hit contributes its zero `lit` through a shadow ray that accepts nothing.  radiance[i].rgb is `color` of the README's loop
+ * over rdx_punctual_light_hits, bit for bit; with type-0 records alone it has the bits of rdx_trace_paths_lights on the same lights
+ * as DirLights.  Fenced gathers, the miss colour at depth 0, one 32-bit word read back per bounce, the engine options, the stats
+ * and the bounce counts: as for rdx_trace_paths_lights.  scene->scene is still required (slot 4); its lights are not read.  The
+ * internal streams take 192 + 80 light_count bytes per path of a chunk, in the allocation rdx_trace_paths_lights uses; beyond 5
+ * records a chunk is min("chunk_paths", "chunk_paths" * 592 / (192 + 80 light_count)) paths, so that the allocation is no larger
+ * than that call's worst case; no result depends on chunking.  Refused, before anything is launched: everything
+ * rdx_trace_paths_lights refuses (its light_count rule aside); light_count > RDX_MAX_PATH_LIGHTS; a NULL or unknown `lights`; a
+ * lights_offset that is not a multiple of 16; 64 light_count bytes at lights_offset that do not fit `lights`; a radiance range
+ * that overlaps the table.  n == 0 succeeds and touches nothing. */
+#define RDX_LIGHT_DIRECTIONAL 0u
+#define RDX_LIGHT_POINT       1u
+#define RDX_LIGHT_SPOT        2u
+typedef struct rdx_punctual_light {              /* 64 B, four float4 */
+    float position[3];  uint32_t type;           /* point / spot: world-space position */
+    float direction[3]; float range;             /* the direction the light shines ALONG (as DirLight.direction); range: 0 = unlimited */
+    float color[3];     float _0;                /* directional: as DirLight.color; point / spot: the colour at distance 1 */
+    float coneScale, coneOffset, _1, _2;         /* spot: 1 / max(0.001, cosInner - cosOuter), -cosOuter * coneScale (the caller computes them) */
+} rdx_punctual_light;
+#define RDX_MAX_PATH_LIGHTS 16u
+int         rdx_punctual_light_hits(rdx_buffer rays, size_t rays_offset,            /* rdx_ray: only the direction is read */
+                                    rdx_buffer materials, size_t materials_offset,  /* rdx_material_record per ray */
+                                    uint32_t n,
+                                    rdx_buffer lights, size_t light_offset,         /* ONE rdx_punctual_light at this byte offset (index * 64) */
+                                    rdx_buffer lit, size_t lit_offset,              /* out float4 per ray: rgb, w = 0 */
+                                    rdx_buffer shadow, size_t shadow_offset);       /* optional out: rdx_ray per ray */
+int         rdx_trace_paths_punctual(rdx_buffer tlas,
+                                     rdx_buffer rays, size_t rays_offset,          /* rdx_ray per path: the first segment, with ITS tmin / tmax */
+                                     rdx_buffer keys, size_t keys_offset,          /* rdx_shade_key per path: frameID, pixel (depth, _0 ignored) */
+                                     uint32_t n, uint32_t max_depth,               /* 0 .. 62 */
+                                     rdx_buffer lights, size_t lights_offset,      /* the table: rdx_punctual_light records */
+                                     uint32_t light_count,                         /* 0 .. RDX_MAX_PATH_LIGHTS records */
+                                     const rdx_shading_buffers* scene,             /* slots 4, 5, 7, 8, 9, 10, 11, 12 as for rdx_shade_hits */
+                                     rdx_buffer radiance, size_t radiance_offset,  /* out: float4 per path: rgb, w = 0 */
+                                     uint32_t* invalid_out);                       /* optional */
+
+/* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_punctual applies to the byte ranges it is given, on plain
  * numbers (needs no device and no initialised library; no address is dereferenced) -> 0, or -1 with the refusal in
  * rdx_last_error().  A row is one range: `bytes` at `offset` of a buffer of `size` bytes at `address`; `align` (a power of two)
  * is the multiple required of the offset and of the address; present == 0: an optional buffer that was not given, the row is

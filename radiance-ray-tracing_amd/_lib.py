@@ -99,6 +99,12 @@ class rdx_material_record(C.Structure):
                 ("above", C.c_float * 3), ("_0", C.c_uint32)]
 
 
+class rdx_punctual_light(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("type", C.c_uint32), ("direction", C.c_float * 3), ("range", C.c_float),
+                ("color", C.c_float * 3), ("_0", C.c_float), ("coneScale", C.c_float), ("coneOffset", C.c_float), ("_1", C.c_float),
+                ("_2", C.c_float)]
+
+
 class rdx_scatter(C.Structure):
     _fields_ = [("nextFactor", C.c_float * 3), ("slot", C.c_uint32)]
 
@@ -188,6 +194,10 @@ SIGNATURES = {
                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "rdx_trace_paths_lights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rdx_punctual_light_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_size_t]),
+    "rdx_trace_paths_punctual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                           C.c_uint32, C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "rdx_debug_check_ranges": (C.c_int, [C.POINTER(rdx_debug_range), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),

@@ -41,6 +41,7 @@
 #include "material_eval.h"
 #include "scatter.h"
 #include "paths.h"
+#include "punctual.h"
 #include "raygen.h"
 #include "rdx_types.h"
 #include "shade.h"
@@ -2675,38 +2676,24 @@ extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_off
     return 0;
 }
 
-// Radiance along the caller's own rays with every light of the scene sampled at every hit (include/rdx.h; light_paths.hip).  Per
-// chunk of "chunk_paths" paths and per depth: launch_query_rays (closest) -> k_lights_shade -> launch_query_rays (any) on the live x L
-// shadow rays, one contiguous range -> k_lights_fold.  launch_query_rays sizes its grid on the host, so ONE word -- the survivors
-// of the depth -- is read back per bounce; nothing else passes through the host.  The chunk's streams are one allocation that
-// grows on first use and is reused: 192 + 80 L bytes per path.
-extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
-                                      uint32_t max_depth, uint32_t light_count, const rdx_shading_buffers* scene, rdx_buffer radiance,
-                                      size_t radiance_offset, uint32_t* invalid_out)
+// The bounces of rdx_trace_paths_lights and rdx_trace_paths_punctual, after their checks (include/rdx.h; light_paths.hip, punctual.hip).
+// Per chunk of paths and per depth: launch_query_rays (closest) -> `shade`, the call's shade kernel over its L lights ->
+// launch_query_rays (any) on the live x L shadow rays, one contiguous range, each under its own interval -> k_lights_fold.
+// launch_query_rays sizes its grid on the host, so ONE word -- the survivors of the depth -- is read back per bounce; nothing else
+// passes through the host.  The chunk's streams are one allocation that grows on first use and is reused: 192 + 80 L bytes per path
+// (DESIGN 4.15, 4.16).
+namespace {
+template <class ShadeLaunch>
+int trace_light_paths(const char* who, rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
+                      uint32_t max_depth, uint32_t L, const ShadeScene& sc, rdx_buffer radiance, size_t radiance_offset, uint32_t* invalid_out,
+                      ShadeLaunch&& shade)
 {
-    const char* who = "rdx_trace_paths_lights";
-    if (!g.initialized) return fail("rdx_trace_paths_lights: rdx_init has not been called");
-    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_lights: invalid TLAS handle");
-    // the SceneProperties is a row because the kernels of every depth read its lights: optional here only so that a NULL `scene` or
-    // a NULL handle in it is left to check_shading_handles
-    const CallRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
-                            {scene ? scene->scene : nullptr, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, false},
-                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
-    uint32_t samplerBits = 0;
-    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
-    if (max_depth > 62) return fail("rdx_trace_paths_lights: depth %u exceeds the supported maximum of 62", max_depth);
-    if (light_count > 5) return fail("rdx_trace_paths_lights: light_count %u exceeds the 5 lights of a SceneProperties", light_count);
-    static_assert(sizeof(((SceneProperties*)nullptr)->lights) == 5 * sizeof(DirLight), "five DirLights");
-    if (check_call_ranges(who, R, 3, n, {invalid_out}, shading_aligned(scene))) return -1;
-    if (!n) return 0;
-    ShadeScene sc;
-    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
     const AccelCache& ac = *acc(tlas);
-    const DirLight* lights = sc.scene->lights;       // a device address: read by the kernels of every call
-
-    const uint32_t L = light_count;
-    // a chunk's shadow rays are one launch_query_rays range, whose count is 32 bits
-    const uint32_t chunk = (uint32_t)std::min<int64_t>(std::min<int64_t>(n, g.opt.chunkPaths), 0xffffffffll / std::max<uint32_t>(L, 1u));
+    // a chunk's shadow rays are one launch_query_rays range, whose count is 32 bits; beyond the five lights of a SceneProperties a
+    // chunk shrinks so that its streams are no larger than five lights' (592 bytes per path): no shorter for L <= 5
+    const int64_t chunkPaths = std::min<int64_t>(g.opt.chunkPaths, 0xffffffffll);
+    const uint32_t chunk = (uint32_t)std::min<int64_t>(std::min<int64_t>(std::min<int64_t>(n, chunkPaths), std::max<int64_t>(chunkPaths * 592 / (192 + 80 * (int64_t)L), 1)),
+                                                       0xffffffffll / std::max<uint32_t>(L, 1u));
     Context::Group& G = g.groups[0];
     // the chunk's streams, each a multiple of 256 bytes: hits 32 | rays x 2 64 | ids x 2 32 | weight x 2 32 | foldF 16 | foldA 16 |
     // lit 16 L | shadow 32 L | any 32 L
@@ -2774,13 +2761,13 @@ extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t r
             g_timer.end(G.s0);
             g.stats.launches_extend++;
             g_timer.begin(&g.stats.ms_shade, G.s0);
-            launch_lights_shade(G.s0, ac.insts, ac.slotOf, ac.s.nInst, sc, lights, L, io, liveRays, d, !last, G.dCounts + d + 1, g.dShadeCounts + 1);
+            shade(G.s0, ac, io, liveRays, d, !last, G.dCounts + d + 1, g.dShadeCounts + 1);
             g_timer.end(G.s0);
             // the one word per bounce: launch_query_rays and the fold are sized on the host
             HIP_OK(hipMemcpyAsync(G.hCounts + d + 1, G.dCounts + d + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, G.s0));
             HIP_OK(hipStreamSynchronize(G.s0));
             const uint32_t survivors = G.hCounts[d + 1];
-            if (survivors > liveRays) return fail("rdx_trace_paths_lights: internal error: %u survivors of %u live rays", survivors, liveRays);
+            if (survivors > liveRays) return fail("%s: internal error: %u survivors of %u live rays", who, survivors, liveRays);
             if (survivors && L) {
                 g_timer.begin(&g.stats.ms_shadow, G.s0);
                 launch_query_rays(G.s0, av, sShadow, survivors * L, RDX_QUERY_ANY, sAny, G.dCounts + 128 + d);
@@ -2801,13 +2788,95 @@ extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t r
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(g.stream));
     mark_written({radiance});
-    if (take_status()) return fail("rdx_trace_paths_lights: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
+    if (take_status()) return fail("%s: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete", who);
     uint32_t invalid = 0;
     HIP_OK(hipMemcpy(&invalid, g.dShadeCounts + 1, sizeof invalid, hipMemcpyDeviceToHost));
     if (invalid_out) *invalid_out = invalid;
     HIP_OK(hipEventElapsedTime(&g.stats.ms_total, g.evA, g.evB));
     g_timer.resolve();
     return 0;
+}
+} // namespace
+
+// Radiance along the caller's own rays with every light of the scene sampled at every hit (include/rdx.h; light_paths.hip): the
+// checks, then trace_light_paths with k_lights_shade over the DirLights of the SceneProperties
+extern "C" int rdx_trace_paths_lights(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
+                                      uint32_t max_depth, uint32_t light_count, const rdx_shading_buffers* scene, rdx_buffer radiance,
+                                      size_t radiance_offset, uint32_t* invalid_out)
+{
+    const char* who = "rdx_trace_paths_lights";
+    if (!g.initialized) return fail("rdx_trace_paths_lights: rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_lights: invalid TLAS handle");
+    // the SceneProperties is a row because the kernels of every depth read its lights: optional here only so that a NULL `scene` or
+    // a NULL handle in it is left to check_shading_handles
+    const CallRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
+                            {scene ? scene->scene : nullptr, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, false},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths_lights: depth %u exceeds the supported maximum of 62", max_depth);
+    if (light_count > 5) return fail("rdx_trace_paths_lights: light_count %u exceeds the 5 lights of a SceneProperties", light_count);
+    static_assert(sizeof(((SceneProperties*)nullptr)->lights) == 5 * sizeof(DirLight), "five DirLights");
+    if (check_call_ranges(who, R, 3, n, {invalid_out}, shading_aligned(scene))) return -1;
+    if (!n) return 0;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
+    const DirLight* lights = sc.scene->lights;       // a device address: read by the kernels of every call
+    return trace_light_paths(who, tlas, rays, rays_offset, keys, keys_offset, n, max_depth, light_count, sc, radiance, radiance_offset, invalid_out,
+                             [&](hipStream_t st, const AccelCache& ac, const LightPathStreams& io, uint32_t live, uint32_t d, bool sampleNext, uint32_t* cursor,
+                                 uint32_t* invalid) {
+                                 launch_lights_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, lights, light_count, io, live, d, sampleNext, cursor, invalid); });
+}
+
+// One record of a caller's light table on material records (punctual.hip).  As rdx_light_hits: no TLAS and no scene streams, so the
+// checks are those of the ranges alone; the one record stands in the table at light_offset
+extern "C" int rdx_punctual_light_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer materials, size_t materials_offset, uint32_t n, rdx_buffer lights,
+                                       size_t light_offset, rdx_buffer lit, size_t lit_offset, rdx_buffer shadow, size_t shadow_offset)
+{
+    const char* who = "rdx_punctual_light_hits";
+    if (!g.initialized) return fail("rdx_punctual_light_hits: rdx_init has not been called");
+    static_assert(sizeof(rdx_punctual_light) == sizeof(PunctualLight) && RDX_MAX_PATH_LIGHTS == MAX_PATH_LIGHTS && RDX_LIGHT_SPOT == LIGHT_SPOT, "light table record");
+    // the first three are read, the others written
+    const CallRange R[5] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true},
+                            {materials, materials_offset, (size_t)n * sizeof(rdx_material_record), "material-record", 16, true},
+                            {lights, light_offset, sizeof(PunctualLight), "light", 16, true},
+                            {lit, lit_offset, (size_t)n * 4 * sizeof(float), "lit", 16, true}, {shadow, shadow_offset, (size_t)n * sizeof(rdx_ray), "shadow-ray", 16, false}};
+    if (check_call_handles(who, R)) return -1;
+    if (check_call_ranges(who, R, 3, n)) return -1;
+    if (!n) return 0;
+    return timed_launch(&rdx_trace_stats::ms_shade, {lit, shadow}, [&] {
+        launch_punctual_light_hits(g.stream, at<const float4>(rays, rays_offset), at<const float4>(materials, materials_offset), n,
+                                   at<const PunctualLight>(lights, light_offset), at<float4>(lit, lit_offset), at<float4>(shadow, shadow_offset)); });
+}
+
+// rdx_trace_paths_lights over the first light_count records of a caller's light table (include/rdx.h; punctual.hip): the checks, then
+// trace_light_paths with k_punctual_shade.  The SceneProperties stays a row although its lights are not read, so that what
+// rdx_trace_paths_lights refuses is refused here
+extern "C" int rdx_trace_paths_punctual(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
+                                        uint32_t max_depth, rdx_buffer lights, size_t lights_offset, uint32_t light_count,
+                                        const rdx_shading_buffers* scene, rdx_buffer radiance, size_t radiance_offset, uint32_t* invalid_out)
+{
+    const char* who = "rdx_trace_paths_punctual";
+    if (!g.initialized) return fail("rdx_trace_paths_punctual: rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_punctual: invalid TLAS handle");
+    if (light_count > MAX_PATH_LIGHTS)
+        return fail("rdx_trace_paths_punctual: light_count %u exceeds the %u records a path samples (RDX_MAX_PATH_LIGHTS)", light_count, MAX_PATH_LIGHTS);
+    const CallRange R[5] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
+                            {lights, lights_offset, (size_t)light_count * sizeof(PunctualLight), "light-table", 16, true},
+                            {scene ? scene->scene : nullptr, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, false},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths_punctual: depth %u exceeds the supported maximum of 62", max_depth);
+    if (check_call_ranges(who, R, 4, n, {invalid_out}, shading_aligned(scene))) return -1;
+    if (!n) return 0;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
+    const PunctualLight* table = at<const PunctualLight>(lights, lights_offset);      // a device address: read by the kernels of every call
+    return trace_light_paths(who, tlas, rays, rays_offset, keys, keys_offset, n, max_depth, light_count, sc, radiance, radiance_offset, invalid_out,
+                             [&](hipStream_t st, const AccelCache& ac, const LightPathStreams& io, uint32_t live, uint32_t d, bool sampleNext, uint32_t* cursor,
+                                 uint32_t* invalid) {
+                                 launch_punctual_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, table, light_count, io, live, d, sampleNext, cursor, invalid); });
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,

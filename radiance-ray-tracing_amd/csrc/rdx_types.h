@@ -32,6 +32,11 @@ struct DirLight { float direction[4]; float color[4]; };
 struct SceneProperties { uint32_t lightCount[4]; DirLight lights[5]; };
 struct PhysicalCamera { float widthPixel, heightPixel, focalLength, sensorWidth, focalDistance, fStop,
                         x, y, z, wx, wy, wz; };
+// a record of a caller's light table (include/rdx.h rdx_punctual_light; no reference counterpart): four float4
+enum : uint32_t { LIGHT_DIRECTIONAL = 0u, LIGHT_POINT = 1u, LIGHT_SPOT = 2u, MAX_PATH_LIGHTS = 16u };
+struct PunctualLight { float position[3]; uint32_t type; float direction[3]; float range; float color[3]; float _0;
+                       float coneScale, coneOffset, _1, _2; };
+static_assert(sizeof(PunctualLight) == 64, "light table record");
 
 static_assert(sizeof(BlobNode) == 48 && sizeof(BlobTri) == 16 && sizeof(BlobInst) == 80, "blob layout");
 static_assert(sizeof(Material) == 48 && sizeof(MeshInfo) == 32 && sizeof(SceneProperties) == 176 &&

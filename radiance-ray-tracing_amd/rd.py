@@ -1079,6 +1079,133 @@ def TraceLightPathsTorch(tlas, rays_t, keys_t, max_depth, light_count, scene_buf
     return radiance
 
 
+# ---- point and spot lights from a caller's light table (rdx_punctual_light_hits, rdx_trace_paths_punctual) -----------------
+PUNCTUAL_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("type", "<u4"), ("direction", "<f4", 3), ("range", "<f4"), ("color", "<f4", 3),
+                                 ("_0", "<f4"), ("coneScale", "<f4"), ("coneOffset", "<f4"), ("_1", "<f4"), ("_2", "<f4")])
+assert PUNCTUAL_LIGHT_DTYPE.itemsize == C.sizeof(_lib.rdx_punctual_light) == 64
+LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
+MAX_PATH_LIGHTS = 16     # the records of a table one TracePunctualPaths call samples
+
+
+def SpotCone(inner_rad, outer_rad):
+    """(coneScale, coneOffset) of a spot record as float32, for the cone's inner and outer half angles in radians:
+    coneScale = 1 / max(0.001, cos(inner) - cos(outer)), coneOffset = -cos(outer) * coneScale, each operation in float32.  The
+    light is full inside the inner cone, dark outside the outer one and f * f of f = clamp(cos * coneScale + coneOffset, 0, 1)
+    between them."""
+    ci, co = np.float32(np.cos(np.float32(inner_rad))), np.float32(np.cos(np.float32(outer_rad)))
+    scale = np.float32(1.0) / np.maximum(np.float32(0.001), np.float32(ci - co))
+    return np.float32(scale), np.float32(np.float32(-co) * scale)
+
+
+def _light_index(who, index, what="index"):
+    if isinstance(index, bool) or not isinstance(index, (int, np.integer)) or index < 0:
+        raise RadianceError("%s: %s must be a non-negative integer" % (who, what))
+    return int(index)
+
+
+def _path_light_count(who, light_count):
+    if isinstance(light_count, bool) or not isinstance(light_count, (int, np.integer)) or not 0 <= light_count <= MAX_PATH_LIGHTS:
+        raise RadianceError("%s: light_count must be an integer from 0 to %d (MAX_PATH_LIGHTS)" % (who, MAX_PATH_LIGHTS))
+    return int(light_count)
+
+
+def PunctualLightHits(rays, materials, n, lights, index, lit=None, shadow=True, rays_offset=0, materials_offset=0, lights_offset=0, lit_offset=0,
+                      shadow_offset=0):
+    """Extension: LightHits for record `index` of the light table `lights`, a device Buffer of PUNCTUAL_LIGHT_DTYPE records that
+    begins at lights_offset: directional (as LightHits, bit for bit), point or spot.  The shadow ray towards a point or spot light
+    ends at the light (tmax = the distance); a record that is dark at a hit -- out of range, outside the cone, an unknown type --
+    gives zeros in `lit` and `shadow`, as does a record whose `hit` is not 1.  lit / shadow as for LightHits.  Returns
+    (lit, shadow)."""
+    if not all(isinstance(b, Buffer) for b in (rays, materials, lights)):
+        raise RadianceError("PunctualLightHits: rays, materials and lights must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    n, index = int(n), _light_index("PunctualLightHits", index)
+    if lit is None:
+        lit = CreateBuffer(None, max(int(lit_offset) + 16 * n, 1))
+    elif not isinstance(lit, Buffer):
+        raise RadianceError("PunctualLightHits: lit must be a Buffer or None")
+    shadow = _out_buffer("PunctualLightHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
+    _check(_lib.lib().rdx_punctual_light_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), n, lights.handle,
+                                              int(lights_offset) + PUNCTUAL_LIGHT_DTYPE.itemsize * index, lit.handle, int(lit_offset),
+                                              shadow.handle if shadow is not None else None, int(shadow_offset)))
+    return lit, shadow
+
+
+def _light_table_tensor(who, lights_t):
+    """an (L, 16) float32 CUDA tensor of PUNCTUAL_LIGHT_DTYPE records -> L.  The table is looked at before the rays, so a refusal
+    of a bad table names it"""
+    import torch
+    return _cuda_tensor(who, lights_t, (torch.float32,), (None, 16), "lights")
+
+
+def PunctualLightHitsTorch(rays_t, materials_t, lights_t, index, want_shadow=True):
+    """Extension: PunctualLightHits on CUDA tensors -- rays and materials as for LightHitsTorch, lights a contiguous float32 (L, 16)
+    tensor of PUNCTUAL_LIGHT_DTYPE records (`.view(torch.int32)` shows `type` in column 3), index < L.  Returns (lit, shadow) as
+    LightHitsTorch.  The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
+    import torch
+    r, m = rays_t, materials_t
+    count = _light_table_tensor("PunctualLightHitsTorch", lights_t)
+    n = _cuda_tensor("PunctualLightHitsTorch", r, (torch.float32,), (None, 8), "rays", lights_t.device, "lights")
+    _cuda_tensor("PunctualLightHitsTorch", m, (torch.float32,), (n, 16), "materials", r.device)
+    index = _light_index("PunctualLightHitsTorch", index)
+    if index >= count:
+        raise RadianceError("PunctualLightHitsTorch: index %d is not one of the %d records of the table" % (index, count))
+    lit = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device) if want_shadow else None
+    torch.cuda.current_stream(r.device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+        table = WrapDeviceMemory(None, lights_t.data_ptr(), count * 64, keepalive=lights_t)
+        PunctualLightHits(wrap(r, 32), wrap(m, 64), n, table, index, wrap(lit, 16), wrap(shadow, 32))
+    return lit, shadow
+
+
+def TracePunctualPaths(tlas, rays, keys, n, max_depth, lights, light_count, scene_buffers, radiance=None, rays_offset=0, keys_offset=0, lights_offset=0,
+                       radiance_offset=0):
+    """Extension: TraceLightPaths with the first `light_count` (0 .. MAX_PATH_LIGHTS) records of the light table `lights` -- a device
+    Buffer of PUNCTUAL_LIGHT_DTYPE records that begins at lights_offset -- sampled at every hit in the place of the scene's
+    directional lights: the path tracer over QueryRays / ResolveHits / ResolveMaterials / PunctualLightHits / ScatterHits in one
+    call, with its bits.  The table is read on the device by every call; scene_buffers.scene is still required, its lights are not
+    read.  Everything else as for TraceLightPaths.  Returns (radiance, invalid)."""
+    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys, lights)):
+        raise RadianceError("TracePunctualPaths: tlas, rays, keys and lights must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    sb = _shading_struct("TracePunctualPaths", scene_buffers)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
+            or max_depth < 0:
+        raise RadianceError("TracePunctualPaths: n and max_depth must be non-negative integers")
+    light_count = _path_light_count("TracePunctualPaths", light_count)
+    n = int(n)
+    if radiance is None:
+        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
+    elif not isinstance(radiance, Buffer):
+        raise RadianceError("TracePunctualPaths: radiance must be a Buffer or None")
+    invalid = C.c_uint32(0)
+    _check(_lib.lib().rdx_trace_paths_punctual(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), lights.handle,
+                                               int(lights_offset), light_count, C.byref(sb), radiance.handle, int(radiance_offset), C.byref(invalid)))
+    return radiance, int(invalid.value)
+
+
+def TracePunctualPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, scene_buffers):
+    """Extension: TracePunctualPaths on CUDA tensors -- rays and keys as for TraceLightPathsTorch, lights a contiguous float32
+    (L, 16) tensor of PUNCTUAL_LIGHT_DTYPE records, L <= MAX_PATH_LIGHTS: every record is sampled.  Returns radiance float32
+    (n, 4): rgb, 0.  The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
+    import torch
+    r, k = rays_t, keys_t
+    count = _path_light_count("TracePunctualPathsTorch", _light_table_tensor("TracePunctualPathsTorch", lights_t))
+    n = _cuda_tensor("TracePunctualPathsTorch", r, (torch.float32,), (None, 8), "rays", lights_t.device, "lights")
+    _cuda_tensor("TracePunctualPathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
+        raise RadianceError("TracePunctualPathsTorch: max_depth must be a non-negative integer")
+    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    torch.cuda.current_stream(r.device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t)
+        # an empty table has no address to wrap: one record of zeros stands in, and none of it is read
+        table_t = lights_t if count else torch.zeros((1, 16), dtype=torch.float32, device=r.device)
+        table = WrapDeviceMemory(None, table_t.data_ptr(), max(count, 1) * 64, keepalive=table_t)
+        TracePunctualPaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, table, count, scene_buffers, wrap(radiance, 16))
+    return radiance
+
+
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
 _DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
 _DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),
