@@ -307,6 +307,34 @@ inline uint32_t TracePunctualPaths(Platform*, TopAccelStruct accelStruct, Buffer
     return invalid;
 }
 
+// Extension (no reference counterpart; rdx_area_light_hits): PunctualLightHits for record `index` of the caller's AREA light table
+// `lights` (rdx_area_light records in device memory, the first at lightsOffset): a quad or a triangle, sampled at one point per
+// ray with pcg3d of the rdx_shade_key records `keys` on random stream `stream`, or with x and y of the float4 records `randoms`
+// (exactly one of the two is nullptr).  The shadow ray stops short of the emitter; a record that is dark at a hit gives zeros.
+inline void AreaLightHits(Platform*, Buffer rays, Buffer materials, uint32_t n, Buffer lights, uint32_t index, Buffer keys, uint32_t stream, Buffer randoms,
+                          Buffer lit, Buffer shadow = nullptr, size_t raysOffset = 0, size_t materialsOffset = 0, size_t lightsOffset = 0,
+                          size_t keysOffset = 0, size_t randomsOffset = 0, size_t litOffset = 0, size_t shadowOffset = 0)
+{
+    if (rdx_area_light_hits(rays, raysOffset, materials, materialsOffset, n, lights, lightsOffset + sizeof(rdx_area_light) * (size_t)index, keys, keysOffset,
+                            stream, randoms, randomsOffset, lit, litOffset, shadow, shadowOffset))
+        detail::fatal("AreaLightHits");
+}
+
+// Extension (no reference counterpart; rdx_trace_paths_area): TracePunctualPaths over two tables -- the first `lightCount` records
+// of `lights`, then the first `areaCount` rdx_area_light records of `area` (record j on random stream j), lightCount + areaCount
+// <= RDX_MAX_PATH_LIGHTS; a table of no records may be nullptr.  The emitters are not geometry: no ray sees them.  Returns the
+// number of hits that `scene` does not describe (they count as misses).
+inline uint32_t TraceAreaPaths(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer keys, uint32_t n, uint32_t maxDepth, Buffer lights,
+                               uint32_t lightCount, Buffer area, uint32_t areaCount, const rdx_shading_buffers& scene, Buffer radiance,
+                               size_t raysOffset = 0, size_t keysOffset = 0, size_t lightsOffset = 0, size_t areaOffset = 0, size_t radianceOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_trace_paths_area(accelStruct, rays, raysOffset, keys, keysOffset, n, maxDepth, lights, lightsOffset, lightCount, area, areaOffset, areaCount,
+                             &scene, radiance, radianceOffset, &invalid))
+        detail::fatal("TraceAreaPaths");
+    return invalid;
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

@@ -585,8 +585,8 @@ int         rdx_trace_paths(rdx_buffer tlas,
  * materials (csrc/shade.h shade_in_bounds, asked before and after the index gather) and must name an instance the TLAS carries, so
  * `scene` buffers that do not describe the scene of `tlas` cannot make a kernel read outside a buffer: such a hit is a miss and is
  * counted in *invalid_out (optional).  Textures follow the rule of rdx_shade_hits (option "textures" 1 and a textureArray; uv
- * required then).  User closest-hit programs do not run here; lights with a position are rdx_trace_paths_punctual's (below), area lights do not
- * exist; one device.
+ * required then).  User closest-hit programs do not run here; lights with a position are rdx_trace_paths_punctual's, area lights
+ * rdx_trace_paths_area's (both below); one device.
  * Nothing is staged through the host: the library reads back ONE 32-bit word per bounce, the survivors' count that sizes the next
  * launches.  Internal streams of 192 + 80 light_count bytes per path of a chunk grow on first use and are reused.  More than
  * "chunk_paths" paths are traced in chunks of that many.  The call blocks, derives the traversal layout if none exists yet, sees
@@ -668,7 +668,90 @@ int         rdx_trace_paths_punctual(rdx_buffer tlas,
                                      rdx_buffer radiance, size_t radiance_offset,  /* out: float4 per path: rgb, w = 0 */
                                      uint32_t* invalid_out);                       /* optional */
 
-/* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_punctual applies to the byte ranges it is given, on plain
+/* Area lights, from a SECOND light table of the caller's own in device memory: records of 64 bytes, each a parallelogram or a
+ * triangle that emits a constant radiance, read ON THE DEVICE by every call.  An emitter is sampled at ONE point per (hit, light),
+ * uniformly over its area, so its shadows are soft over frames.  Two calls on the two levels of the light API above:
+ * rdx_area_light_hits is rdx_punctual_light_hits for one area record, rdx_trace_paths_area is rdx_trace_paths_punctual over a
+ * punctual table AND an area table.  Neither changes any other call.
+ * The emitters are NOT geometry: a camera ray does not see them, and a path that reaches lamp geometry of the scene shades that
+ * geometry's ordinary material.  The estimator is next-event only -- a light is counted where it is sampled, never where a path
+ * happens to arrive --, so nothing is counted twice.  No textured or spherical emitters, no multiple-importance sampling, one
+ * sample per light per hit.
+ * The emitter is corner + s * edgeU + t * edgeV with s, t in [0, 1] (RDX_AREA_QUAD) or the triangle corner, corner + edgeU, corner +
+ * edgeV (RDX_AREA_TRIANGLE).  n = cross(edgeU, edgeV) points away from the emitting face, into the half-space the record lights
+ * (edgeU = +x, edgeV = +z: a lamp that shines down); a one-sided record is dark from behind; flags bit 0 (RDX_AREA_TWO_SIDED) makes
+ * it emit from both faces.
+ * rdx_area_light_hits: rays, materials, n, lit and shadow are those of rdx_punctual_light_hits; the light is the ONE record at byte
+ * offset light_offset (index * 64) of `lights`.  Exactly one of `keys` and `randoms` is given, by rdx_scatter_hits' rule: keys are
+ * rdx_shade_key records, randoms one float4 per ray of which x and y are used.  For a material record with hit == 1, every float32
+ * operation rounded on its own, with N, V, normalize (v_rsq_f32 based), microfacetBRDF and clamp exactly those of rdx_light_hits:
+ *   keys     r = pcg3d(key.frameID, key.pixel, key.depth + ((stream + 1u) << 16)) in uint32 arithmetic; u = r.x, v = r.y.  Paths are
+ *            at most 62 deep and sample at most 16 records, so no (depth, stream) pair meets the pcg3d(frameID, pixel, depth) that
+ *            rdx_scatter_hits draws from, or another stream's;
+ *   randoms  u = randoms[i].x, v = randoms[i].y, as they are;
+ *   type 1   if (u + v > 1.0f) { u = 1.0f - u; v = 1.0f - v; }
+ *   p.c = (corner.c + edgeU.c * u) + edgeV.c * v for c = x, y, z (plain products and sums, not fused);
+ *   n.x = edgeU.y * edgeV.z - edgeU.z * edgeV.y; n.y = edgeU.z * edgeV.x - edgeU.x * edgeV.z; n.z = edgeU.x * edgeV.y - edgeU.y * edgeV.x;
+ *   w = p - above; d2 = (w.x * w.x + w.y * w.y) + w.z * w.z; L = normalize(w);
+ *   g = -((n.x * L.x + n.y * L.y) + n.z * L.z); type 1: g = g * 0.5f; flags bit 0: g = fabsf(g) -- emitter area x cosine at the
+ *            emitter: |n| is the parallelogram's area, so nothing is normalised and no square root is taken;
+ *   E = radiance * (g / d2): one division, three products -- the one-sample estimator under the pdf 1 / area; microfacetBRDF
+ *            carries the receiver's cosine, as for every other light;
+ *   tmax = sqrtf(d2) * 0.999f: the shadow ray STOPS SHORT of the emitter, so lamp geometry that lies in the light's own plane --
+ *            the quad under a Cornell box's ceiling -- does not shadow its own light (nor does anything else within the last
+ *            thousandth of the distance);
+ *   DARK     the record is dark at the hit if type > 1, !(d2 > 0.0f), !(d2 < INFINITY) or !(g > 0.0f) -- the back face of a
+ *            one-sided record, a degenerate emitter, NaNs;
+ *   else     lit.rgb = (0, 0, 0) + microfacetBRDF(L, V, N, albedo, metallic, roughness, transmission) * E, lit.w = 0, and the shadow
+ *            record (optional) is (above | 0.001f, L | tmax), ready for rdx_query_rays(..., RDX_QUERY_ANY, ...).
+ * A dark record and any other value of `hit` give 16 zero bytes in `lit` and 32 in `shadow`.  The kernel gathers nothing but the
+ * one record and the ray's key or randoms; non-finite fields give unspecified colours, never a fault.  The call blocks;
+ * rdx_get_trace_stats().ms_shade is the kernel time.  Refused, before anything is launched: what rdx_punctual_light_hits refuses,
+ * with the 64 bytes of the area record in the place of the punctual one; both of keys and randoms, or neither; a keys_offset or
+ * randoms_offset that is not a multiple of 16, or 16 n bytes there that do not fit; an output range that overlaps the keys or the
+ * randoms; stream > 0xfffe.  n == 0 succeeds and touches nothing.
+ * rdx_trace_paths_area: the per-path specification of rdx_trace_paths_punctual over BOTH tables.  At every hit the light_count
+ * records of `lights` are evaluated first, as that call evaluates them; then the area_count records of `area`, record j via
+ * rdx_area_light_hits on the keys route with stream = j and the path's own (frameID, pixel, depth); they are folded in that order:
+ * direct = ((0 + x_0) + x_1) + ..., x = occluded ? 0 : lit.  light_count + area_count <= RDX_MAX_PATH_LIGHTS; either count may be
+ * 0, and its table may then be NULL.  radiance[i].rgb is `color` of the README's loop over the two per-hit calls, bit for bit; with
+ * area_count == 0 it has the bits of rdx_trace_paths_punctual.  Streams, chunking, stats, bounce counts, the one word read back per
+ * bounce, the fenced gathers, the miss colour and the engine options: as for rdx_trace_paths_punctual with light_count +
+ * area_count in the place of light_count.  Refused, before anything is launched: everything rdx_trace_paths_punctual refuses (a NULL
+ * table of no records aside); light_count + area_count > RDX_MAX_PATH_LIGHTS; a NULL or unknown `area` with area_count != 0; an
+ * area_offset that is not a multiple of 16; 64 area_count bytes at area_offset that do not fit `area`; a radiance range that
+ * overlaps either table.  n == 0 succeeds and touches nothing. */
+#define RDX_AREA_QUAD      0u   /* the parallelogram corner + s * edgeU + t * edgeV, s, t in [0, 1] */
+#define RDX_AREA_TRIANGLE  1u   /* the triangle corner, corner + edgeU, corner + edgeV */
+#define RDX_AREA_TWO_SIDED 1u   /* flags bit 0: emits from both faces */
+typedef struct rdx_area_light {                  /* 64 B, four float4 */
+    float corner[3];   uint32_t type;
+    float edgeU[3];    uint32_t flags;
+    float edgeV[3];    float _0;
+    float radiance[3]; float _1;                 /* emitted radiance, constant over the emitter */
+} rdx_area_light;
+int         rdx_area_light_hits(rdx_buffer rays, size_t rays_offset,              /* rdx_ray: only the direction is read */
+                                rdx_buffer materials, size_t materials_offset,    /* rdx_material_record per ray */
+                                uint32_t n,
+                                rdx_buffer lights, size_t light_offset,           /* ONE rdx_area_light at this byte offset (index * 64) */
+                                rdx_buffer keys, size_t keys_offset,              /* rdx_shade_key per ray, or NULL */
+                                uint32_t stream,                                  /* keys route: 0 .. 0xfffe, the record's random stream */
+                                rdx_buffer randoms, size_t randoms_offset,        /* float4 per ray (x, y used), or NULL */
+                                rdx_buffer lit, size_t lit_offset,                /* out float4 per ray: rgb, w = 0 */
+                                rdx_buffer shadow, size_t shadow_offset);         /* optional out: rdx_ray per ray */
+int         rdx_trace_paths_area(rdx_buffer tlas,
+                                 rdx_buffer rays, size_t rays_offset,             /* rdx_ray per path: the first segment, with ITS tmin / tmax */
+                                 rdx_buffer keys, size_t keys_offset,             /* rdx_shade_key per path: frameID, pixel (depth, _0 ignored) */
+                                 uint32_t n, uint32_t max_depth,                  /* 0 .. 62 */
+                                 rdx_buffer lights, size_t lights_offset,         /* the table of rdx_punctual_light records */
+                                 uint32_t light_count,
+                                 rdx_buffer area, size_t area_offset,             /* the table of rdx_area_light records */
+                                 uint32_t area_count,                             /* light_count + area_count <= RDX_MAX_PATH_LIGHTS */
+                                 const rdx_shading_buffers* scene,                /* slots 4, 5, 7, 8, 9, 10, 11, 12 as for rdx_shade_hits */
+                                 rdx_buffer radiance, size_t radiance_offset,     /* out: float4 per path: rgb, w = 0 */
+                                 uint32_t* invalid_out);                          /* optional */
+
+/* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_area applies to the byte ranges it is given, on plain
  * numbers (needs no device and no initialised library; no address is dereferenced) -> 0, or -1 with the refusal in
  * rdx_last_error().  A row is one range: `bytes` at `offset` of a buffer of `size` bytes at `address`; `align` (a power of two)
  * is the multiple required of the offset and of the address; present == 0: an optional buffer that was not given, the row is

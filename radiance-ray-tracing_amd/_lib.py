@@ -105,6 +105,11 @@ class rdx_punctual_light(C.Structure):
                 ("_2", C.c_float)]
 
 
+class rdx_area_light(C.Structure):
+    _fields_ = [("corner", C.c_float * 3), ("type", C.c_uint32), ("edgeU", C.c_float * 3), ("flags", C.c_uint32),
+                ("edgeV", C.c_float * 3), ("_0", C.c_float), ("radiance", C.c_float * 3), ("_1", C.c_float)]
+
+
 class rdx_scatter(C.Structure):
     _fields_ = [("nextFactor", C.c_float * 3), ("slot", C.c_uint32)]
 
@@ -198,6 +203,11 @@ SIGNATURES = {
                                           C.c_void_p, C.c_size_t]),
     "rdx_trace_paths_punctual": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                            C.c_uint32, C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rdx_area_light_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                      C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rdx_trace_paths_area": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                       C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_uint32)]),
     "rdx_debug_check_ranges": (C.c_int, [C.POINTER(rdx_debug_range), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),

@@ -34,6 +34,7 @@
 #endif
 #include RDX_SBT_HEADER
 #include "accel_layout.h"
+#include "area.h"
 #include "bvh_build.h"
 #include "device_math.h"
 #include "kernels.h"
@@ -2676,7 +2677,8 @@ extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_off
     return 0;
 }
 
-// The bounces of rdx_trace_paths_lights and rdx_trace_paths_punctual, after their checks (include/rdx.h; light_paths.hip, punctual.hip).
+// The bounces of rdx_trace_paths_lights, rdx_trace_paths_punctual and rdx_trace_paths_area, after their checks (include/rdx.h;
+// light_paths.hip, punctual.hip, area.hip).
 // Per chunk of paths and per depth: launch_query_rays (closest) -> `shade`, the call's shade kernel over its L lights ->
 // launch_query_rays (any) on the live x L shadow rays, one contiguous range, each under its own interval -> k_lights_fold.
 // launch_query_rays sizes its grid on the host, so ONE word -- the survivors of the depth -- is read back per bounce; nothing else
@@ -2877,6 +2879,68 @@ extern "C" int rdx_trace_paths_punctual(rdx_buffer tlas, rdx_buffer rays, size_t
                              [&](hipStream_t st, const AccelCache& ac, const LightPathStreams& io, uint32_t live, uint32_t d, bool sampleNext, uint32_t* cursor,
                                  uint32_t* invalid) {
                                  launch_punctual_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, table, light_count, io, live, d, sampleNext, cursor, invalid); });
+}
+
+// One record of a caller's area light table on material records (area.hip).  As rdx_punctual_light_hits, plus the one key or the
+// one float4 of randoms per ray that rdx_scatter_hits reads, by its rule: exactly one of the two
+extern "C" int rdx_area_light_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer materials, size_t materials_offset, uint32_t n, rdx_buffer lights,
+                                   size_t light_offset, rdx_buffer keys, size_t keys_offset, uint32_t stream, rdx_buffer randoms, size_t randoms_offset,
+                                   rdx_buffer lit, size_t lit_offset, rdx_buffer shadow, size_t shadow_offset)
+{
+    const char* who = "rdx_area_light_hits";
+    if (!g.initialized) return fail("rdx_area_light_hits: rdx_init has not been called");
+    static_assert(sizeof(rdx_area_light) == sizeof(AreaLight) && RDX_AREA_TRIANGLE == AREA_TRIANGLE && RDX_AREA_TWO_SIDED == AREA_TWO_SIDED, "area light table record");
+    // the first five are read, the others written
+    const CallRange R[7] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true},
+                            {materials, materials_offset, (size_t)n * sizeof(rdx_material_record), "material-record", 16, true},
+                            {lights, light_offset, sizeof(AreaLight), "area-light", 16, true},
+                            {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, false}, {randoms, randoms_offset, (size_t)n * 4 * sizeof(float), "randoms", 16, false},
+                            {lit, lit_offset, (size_t)n * 4 * sizeof(float), "lit", 16, true}, {shadow, shadow_offset, (size_t)n * sizeof(rdx_ray), "shadow-ray", 16, false}};
+    if (check_call_handles(who, R)) return -1;
+    if (!keys && !randoms) return fail("rdx_area_light_hits: neither keys nor randoms given: one of the two is required");
+    if (keys && randoms) return fail("rdx_area_light_hits: both keys and randoms given: only one of the two is allowed");
+    if (stream > 0xfffeu) return fail("rdx_area_light_hits: stream %u exceeds the supported maximum of 65534", stream);
+    if (check_call_ranges(who, R, 5, n)) return -1;
+    if (!n) return 0;
+    return timed_launch(&rdx_trace_stats::ms_shade, {lit, shadow}, [&] {
+        launch_area_light_hits(g.stream, at<const float4>(rays, rays_offset), at<const float4>(materials, materials_offset), n,
+                               at<const AreaLight>(lights, light_offset), at<const uint4>(keys, keys_offset), stream, at<const float4>(randoms, randoms_offset),
+                               at<float4>(lit, lit_offset), at<float4>(shadow, shadow_offset)); });
+}
+
+// rdx_trace_paths_punctual over two tables (include/rdx.h; area.hip): the checks, then trace_light_paths with k_area_shade over
+// light_count punctual records followed by area_count area records.  A table whose count is 0 may be NULL: its row is optional then
+extern "C" int rdx_trace_paths_area(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
+                                    uint32_t max_depth, rdx_buffer lights, size_t lights_offset, uint32_t light_count, rdx_buffer area,
+                                    size_t area_offset, uint32_t area_count, const rdx_shading_buffers* scene, rdx_buffer radiance,
+                                    size_t radiance_offset, uint32_t* invalid_out)
+{
+    const char* who = "rdx_trace_paths_area";
+    if (!g.initialized) return fail("rdx_trace_paths_area: rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_area: invalid TLAS handle");
+    if (light_count > MAX_PATH_LIGHTS || area_count > MAX_PATH_LIGHTS || light_count + area_count > MAX_PATH_LIGHTS)
+        return fail("rdx_trace_paths_area: light_count %u + area_count %u exceeds the %u records a path samples (RDX_MAX_PATH_LIGHTS)", light_count, area_count,
+                    MAX_PATH_LIGHTS);
+    const CallRange R[6] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
+                            {lights, lights_offset, (size_t)light_count * sizeof(PunctualLight), "light-table", 16, light_count != 0},
+                            {area, area_offset, (size_t)area_count * sizeof(AreaLight), "area-light-table", 16, area_count != 0},
+                            {scene ? scene->scene : nullptr, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, false},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths_area: depth %u exceeds the supported maximum of 62", max_depth);
+    if (check_call_ranges(who, R, 5, n, {invalid_out}, shading_aligned(scene))) return -1;
+    if (!n) return 0;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
+    // device addresses: read by the kernels of every call.  A table of no records is never read
+    const PunctualLight* table = light_count ? at<const PunctualLight>(lights, lights_offset) : nullptr;
+    const AreaLight* areaTable = area_count ? at<const AreaLight>(area, area_offset) : nullptr;
+    return trace_light_paths(who, tlas, rays, rays_offset, keys, keys_offset, n, max_depth, light_count + area_count, sc, radiance, radiance_offset, invalid_out,
+                             [&](hipStream_t st, const AccelCache& ac, const LightPathStreams& io, uint32_t live, uint32_t d, bool sampleNext, uint32_t* cursor,
+                                 uint32_t* invalid) {
+                                 launch_area_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, table, light_count, areaTable, area_count, io, live, d, sampleNext, cursor,
+                                                   invalid); });
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,

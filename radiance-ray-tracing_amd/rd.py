@@ -1206,6 +1206,171 @@ def TracePunctualPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, scene_buf
     return radiance
 
 
+# ---- quad and triangle area lights from a second table of the caller's (rdx_area_light_hits, rdx_trace_paths_area) ---------
+AREA_LIGHT_DTYPE = np.dtype([("corner", "<f4", 3), ("type", "<u4"), ("edgeU", "<f4", 3), ("flags", "<u4"), ("edgeV", "<f4", 3), ("_0", "<f4"),
+                             ("radiance", "<f4", 3), ("_1", "<f4")])
+assert AREA_LIGHT_DTYPE.itemsize == C.sizeof(_lib.rdx_area_light) == 64
+AREA_QUAD, AREA_TRIANGLE = 0, 1
+AREA_TWO_SIDED = 1       # flags bit 0
+MAX_AREA_STREAM = 0xfffe
+
+
+def _area_record(type, corner, edge_u, edge_v, radiance, two_sided):
+    r = np.zeros((), AREA_LIGHT_DTYPE)
+    r["type"], r["corner"], r["edgeU"], r["edgeV"], r["radiance"] = type, corner, edge_u, edge_v, radiance
+    r["flags"] = AREA_TWO_SIDED if two_sided else 0
+    return r
+
+
+def QuadLight(corner, edge_u, edge_v, radiance, two_sided=False):
+    """one AREA_LIGHT_DTYPE record: the parallelogram corner + s * edge_u + t * edge_v, s, t in [0, 1], of constant `radiance`.  It
+    emits into the half-space that cross(edge_u, edge_v) points into (a quad under a ceiling with edge_u = +x, edge_v = +z shines
+    down) and is dark from behind; two_sided: it emits from both faces."""
+    return _area_record(AREA_QUAD, corner, edge_u, edge_v, radiance, two_sided)
+
+
+def TriangleLight(corner, edge_u, edge_v, radiance, two_sided=False):
+    """one AREA_LIGHT_DTYPE record: the triangle corner, corner + edge_u, corner + edge_v; everything else as QuadLight"""
+    return _area_record(AREA_TRIANGLE, corner, edge_u, edge_v, radiance, two_sided)
+
+
+def _area_stream(who, stream, index):
+    if stream is None:
+        stream = index
+    if isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= stream <= MAX_AREA_STREAM:
+        raise RadianceError("%s: stream must be an integer from 0 to %d" % (who, MAX_AREA_STREAM))
+    return int(stream)
+
+
+def AreaLightHits(rays, materials, n, lights, index, keys=None, randoms=None, stream=None, lit=None, shadow=True, rays_offset=0, materials_offset=0,
+                  lights_offset=0, keys_offset=0, randoms_offset=0, lit_offset=0, shadow_offset=0):
+    """Extension: PunctualLightHits for record `index` of the AREA light table `lights`, a device Buffer of AREA_LIGHT_DTYPE records
+    (QuadLight / TriangleLight) that begins at lights_offset.  The emitter is sampled at one point per ray: the random pair is
+    pcg3d(frameID, pixel, depth + ((stream + 1) << 16)).xy of the SHADE_KEY_DTYPE records of `keys` -- `stream` defaults to `index`,
+    which is what TraceAreaPaths uses -- or, keys None, x and y of the float4 records of `randoms`: exactly one of the two is given.
+    The shadow ray stops at 0.999 of the distance to the sampled point; a record that is dark at a hit -- the back face of a
+    one-sided emitter, a degenerate emitter, an unknown type -- gives zeros in `lit` and `shadow`, as does a record whose `hit` is
+    not 1.  lit / shadow as for LightHits.  Returns (lit, shadow)."""
+    if not all(isinstance(b, Buffer) for b in (rays, materials, lights)):
+        raise RadianceError("AreaLightHits: rays, materials and lights must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    for what, b in (("keys", keys), ("randoms", randoms)):
+        if b is not None and not isinstance(b, Buffer):
+            raise RadianceError("AreaLightHits: %s must be a Buffer or None" % what)
+    if keys is None and randoms is None:
+        raise RadianceError("AreaLightHits: neither keys nor randoms given: one of the two is required")
+    if keys is not None and randoms is not None:
+        raise RadianceError("AreaLightHits: both keys and randoms given: only one of the two is allowed")
+    n, index = int(n), _light_index("AreaLightHits", index)
+    stream = _area_stream("AreaLightHits", stream, index if keys is not None else 0)
+    if lit is None:
+        lit = CreateBuffer(None, max(int(lit_offset) + 16 * n, 1))
+    elif not isinstance(lit, Buffer):
+        raise RadianceError("AreaLightHits: lit must be a Buffer or None")
+    shadow = _out_buffer("AreaLightHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
+    h = lambda b: b.handle if b is not None else None
+    _check(_lib.lib().rdx_area_light_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), n, lights.handle,
+                                          int(lights_offset) + AREA_LIGHT_DTYPE.itemsize * index, h(keys), int(keys_offset), stream, h(randoms),
+                                          int(randoms_offset), lit.handle, int(lit_offset), h(shadow), int(shadow_offset)))
+    return lit, shadow
+
+
+def AreaLightHitsTorch(rays_t, materials_t, area_t, index, keys=None, randoms=None, stream=None, want_shadow=True):
+    """Extension: AreaLightHits on CUDA tensors -- rays and materials as for LightHitsTorch, area_t a contiguous float32 (A, 16)
+    tensor of AREA_LIGHT_DTYPE records (`.view(torch.int32)` shows `type` in column 3 and `flags` in column 7), index < A, and
+    exactly one of keys, a contiguous int32 (n, 4) tensor (frameID, pixel, depth, 0), and randoms, a contiguous float32 (n, 4)
+    tensor (x, y used).  Returns (lit, shadow) as LightHitsTorch.  The library cannot see torch's stream, so the current stream is
+    synchronised first; the call blocks."""
+    import torch
+    r, m = rays_t, materials_t
+    count = _cuda_tensor("AreaLightHitsTorch", area_t, (torch.float32,), (None, 16), "area lights")
+    n = _cuda_tensor("AreaLightHitsTorch", r, (torch.float32,), (None, 8), "rays", area_t.device, "area lights")
+    _cuda_tensor("AreaLightHitsTorch", m, (torch.float32,), (n, 16), "materials", r.device)
+    if (keys is None) == (randoms is None):
+        raise RadianceError("AreaLightHitsTorch: exactly one of keys and randoms must be given")
+    if keys is not None:
+        _cuda_tensor("AreaLightHitsTorch", keys, (torch.int32,), (n, 4), "keys", r.device)
+    if randoms is not None:
+        _cuda_tensor("AreaLightHitsTorch", randoms, (torch.float32,), (n, 4), "randoms", r.device)
+    index = _light_index("AreaLightHitsTorch", index)
+    if index >= count:
+        raise RadianceError("AreaLightHitsTorch: index %d is not one of the %d records of the table" % (index, count))
+    stream = _area_stream("AreaLightHitsTorch", stream, index if keys is not None else 0)
+    lit = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device) if want_shadow else None
+    torch.cuda.current_stream(r.device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
+        table = WrapDeviceMemory(None, area_t.data_ptr(), count * 64, keepalive=area_t)
+        AreaLightHits(wrap(r, 32), wrap(m, 64), n, table, index, wrap(keys, 16), wrap(randoms, 16), stream, wrap(lit, 16), wrap(shadow, 32))
+    return lit, shadow
+
+
+def _area_path_counts(who, light_count, area_count):
+    for what, c in (("light_count", light_count), ("area_count", area_count)):
+        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0:
+            raise RadianceError("%s: %s must be a non-negative integer" % (who, what))
+    if light_count + area_count > MAX_PATH_LIGHTS:
+        raise RadianceError("%s: light_count + area_count must not exceed %d (MAX_PATH_LIGHTS)" % (who, MAX_PATH_LIGHTS))
+    return int(light_count), int(area_count)
+
+
+def TraceAreaPaths(tlas, rays, keys, n, max_depth, lights, light_count, area, area_count, scene_buffers, radiance=None, rays_offset=0, keys_offset=0,
+                   lights_offset=0, area_offset=0, radiance_offset=0):
+    """Extension: TracePunctualPaths over TWO tables: at every hit the first `light_count` PUNCTUAL_LIGHT_DTYPE records of `lights`,
+    then the first `area_count` AREA_LIGHT_DTYPE records of `area` -- record j sampled at one point with stream j and the path's
+    own (frameID, pixel, depth) --, folded in that order: the path tracer over QueryRays / ResolveHits / ResolveMaterials /
+    PunctualLightHits / AreaLightHits / ScatterHits in one call, with its bits.  light_count + area_count <= MAX_PATH_LIGHTS; a
+    table whose count is 0 may be None.  With area_count 0 the result has the bits of TracePunctualPaths.  The emitters are not
+    geometry: no ray sees them.  Everything else as for TracePunctualPaths.  Returns (radiance, invalid)."""
+    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
+        raise RadianceError("TraceAreaPaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    sb = _shading_struct("TraceAreaPaths", scene_buffers)
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
+            or max_depth < 0:
+        raise RadianceError("TraceAreaPaths: n and max_depth must be non-negative integers")
+    light_count, area_count = _area_path_counts("TraceAreaPaths", light_count, area_count)
+    for what, b, c in (("lights", lights, light_count), ("area", area, area_count)):
+        if not (isinstance(b, Buffer) or (b is None and c == 0)):
+            raise RadianceError("TraceAreaPaths: %s must be a Buffer (or None with a count of 0)" % what)
+    n = int(n)
+    if radiance is None:
+        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
+    elif not isinstance(radiance, Buffer):
+        raise RadianceError("TraceAreaPaths: radiance must be a Buffer or None")
+    invalid = C.c_uint32(0)
+    h = lambda b: b.handle if b is not None else None
+    _check(_lib.lib().rdx_trace_paths_area(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), h(lights),
+                                           int(lights_offset), light_count, h(area), int(area_offset), area_count, C.byref(sb), radiance.handle,
+                                           int(radiance_offset), C.byref(invalid)))
+    return radiance, int(invalid.value)
+
+
+def TraceAreaPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, area_t, scene_buffers):
+    """Extension: TraceAreaPaths on CUDA tensors -- rays and keys as for TraceLightPathsTorch, lights_t a contiguous float32 (L, 16)
+    tensor of PUNCTUAL_LIGHT_DTYPE records or None, area_t a contiguous float32 (A, 16) tensor of AREA_LIGHT_DTYPE records or None,
+    L + A <= MAX_PATH_LIGHTS: every record is sampled.  Returns radiance float32 (n, 4): rgb, 0.  The library cannot see torch's
+    stream, so the current stream is synchronised first; the call blocks."""
+    import torch
+    r, k = rays_t, keys_t
+    L = _light_table_tensor("TraceAreaPathsTorch", lights_t) if lights_t is not None else 0
+    A = _cuda_tensor("TraceAreaPathsTorch", area_t, (torch.float32,), (None, 16), "area lights") if area_t is not None else 0
+    L, A = _area_path_counts("TraceAreaPathsTorch", L, A)
+    n = _cuda_tensor("TraceAreaPathsTorch", r, (torch.float32,), (None, 8), "rays")
+    for what, t in (("lights", lights_t), ("area lights", area_t)):
+        if t is not None and t.device != r.device:
+            raise RadianceError("TraceAreaPathsTorch: %s must be on the rays' device" % what)
+    _cuda_tensor("TraceAreaPathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
+        raise RadianceError("TraceAreaPathsTorch: max_depth must be a non-negative integer")
+    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
+    torch.cuda.current_stream(r.device).synchronize()
+    if n:
+        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t)
+        table = lambda t, c: WrapDeviceMemory(None, t.data_ptr(), c * 64, keepalive=t) if c else None      # an empty table has no address to wrap
+        TraceAreaPaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, table(lights_t, L), L, table(area_t, A), A, scene_buffers, wrap(radiance, 16))
+    return radiance
+
+
 # the derived traversal layout (csrc/rdx_types.h), in the order rdx_debug_accel_layout returns its arrays
 _DNODE = np.dtype([("bmin", "<f4", 4), ("bmax", "<f4", 4), ("w", "<u4", 4)])
 _DWIDE = np.dtype([("lmin", "<f4", 3), ("ld0", "<u4"), ("lmax", "<f4", 3), ("ld1", "<u4"), ("rmin", "<f4", 3), ("rd0", "<u4"),
