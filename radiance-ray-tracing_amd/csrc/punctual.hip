@@ -2,281 +2,44 @@
 // light table -- directional, point or spot (include/rdx.h rdx_punctual_light) -- on material records, and the shade kernel of a
 // bounce that samples every record of the table at every hit:
 //
-//   closest-hit query -> k_punctual_shade -> any-hit query of live x L shadow rays -> k_lights_fold (light_paths.hip, unchanged)
+//   closest-hit query -> k_punctual_shade -> any-hit query of live x L shadow rays -> k_lights_fold (light_paths.hip)
 //
-// A translation unit of its own, like its siblings and for the same reason: the code objects of kernels.hip, surface.hip,
-// shade.hip, material.hip, scatter.hip, light_paths.hip, paths.hip, raygen.hip and tlas_update.hip stay the ones they were, bit for
-// bit (profiles/punctual_kernels.txt).  k_punctual_shade is k_lights_shade (light_paths.hip) with another light loop; its body is
-// restated here operation for operation rather than shared as a template, because k_lights_shade does not keep its machine code
-// once its body is an inlined function (the kernel arguments are then loaded in another pattern; profiles/punctual_kernels.txt 3).
-// What a record emits at a hit is ONE function, punctual_emit, for both kernels, so the per-path call has the bits of the per-hit
-// call; the PBR, frame and RNG functions are those of stages.h / device_math.h, called as k_light_hits (material.hip) and
-// k_scatter_hits (scatter.hip) call them.
+// Both kernels are callers of shared text: what a record emits at a hit is punctual_emit and the record it leaves is light_record
+// (light_emit.h), for the per-hit kernel and the shade kernel alike, so the per-path call has the bits of the per-hit call; the
+// shade kernel is path_shade.h's body over the table.  A translation unit of its own, so that the code objects of kernels.hip,
+// surface.hip, shade.hip, scatter.hip, paths.hip, raygen.hip and tlas_update.hip stay the ones they were, bit for bit
+// (profiles/punctual_kernels.txt).
 #include "kernels.h"
 
-#include "device_math.h"
-#include "light_paths.h"
+#include "path_shade.h"
 #include "punctual.h"
-#include "shade.h"
-#include "stages.h"
-#include "surface.h"
 
 namespace rdx {
 
-constexpr uint32_t PUNCTUAL_BLOCK = 256;
-
-// Record `lt` seen from `above`: L = the unit direction towards it, E = what it emits there, tmax = the end of the shadow ray's
-// interval (the distance to a light that has a position); false: the record is dark there.  Every float32 operation is rounded on
-// its own (this unit is compiled with -ffp-contract=off), and d2 and the cone's cosine are plain products and sums, NOT dot3, which
-// is fused: numpy float32 restates them (tests/punctual_cases.py `emitted`).  Type 0 is k_light_hits' L and colour and the stock
-// interval.  `lt` is the same address in every lane, so its fields arrive through the scalar cache and the branches on `type` are
-// uniform; the ones on d2, range and the cone are per lane.
-__device__ __forceinline__ bool punctual_emit(const PunctualLight* __restrict__ lt, const f3& above, f3& L, f3& E, float& tmax)
-{
-    const uint32_t type = lt->type;
-    if (type > LIGHT_SPOT) return false;
-    E = mk3(lt->color[0], lt->color[1], lt->color[2]);
-    if (type == LIGHT_DIRECTIONAL) {
-        L = normalize3(mk3(-lt->direction[0], -lt->direction[1], -lt->direction[2]));
-        tmax = 1000.0f;
-        return true;
-    }
-    const f3 v = mk3(lt->position[0] - above.x, lt->position[1] - above.y, lt->position[2] - above.z);
-    const float d2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
-    if (!(d2 > 0.0f)) return false;
-    if (!(d2 < __builtin_inff())) return false;
-    const float range = lt->range;
-    if (range > 0.0f && !(d2 < range * range)) return false;
-    L = normalize3(v);
-    const float att = 1.0f / d2;
-    E = E * att;
-    tmax = sqrtf(d2);
-    if (type == LIGHT_SPOT) {
-        const f3 S = normalize3(mk3(lt->direction[0], lt->direction[1], lt->direction[2]));
-        const float c = -((S.x * L.x + S.y * L.y) + S.z * L.z);
-        const float f = cl_clamp(c * lt->coneScale + lt->coneOffset, 0.0f, 1.0f);
-        if (!(f > 0.0f)) return false;
-        E = E * (f * f);
-    }
-    return true;
-}
-
-// One record per thread, as k_light_hits (material.hip): the direction of ray i = rays[2i + 1], material record i = mats[4i .. 4i +
-// 3]; lit[i] = (rgb, 0), shadow record i = shadow[2i], shadow[2i + 1].  Nothing is gathered, so nothing is fenced; no atomics, no
-// LDS.
-__global__ void __launch_bounds__(PUNCTUAL_BLOCK)
+// light_hits (light_emit.h) with one record of the table.
+__global__ void __launch_bounds__(LIGHT_HITS_BLOCK)
 k_punctual_light_hits(const float4* __restrict__ rays, const float4* __restrict__ mats, uint32_t n, const PunctualLight* __restrict__ light,
                       float4* __restrict__ lit, float4* __restrict__ shadow)
 {
-    const uint32_t i = blockIdx.x * PUNCTUAL_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const float4 rd = rays[2 * (size_t)i + 1];
-    const float4 m0 = mats[4 * (size_t)i], m1 = mats[4 * (size_t)i + 1], m2 = mats[4 * (size_t)i + 2], m3 = mats[4 * (size_t)i + 3];
-    // a dark record, any other value of `hit`: zeros (a shadow ray with tmax 0 accepts nothing)
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f), s0 = c, s1 = c;
-    if (__float_as_uint(m0.w) == 1u) {
-        const f3 above = mk3(m3.x, m3.y, m3.z);
-        f3 L, E;
-        float tmax;
-        if (punctual_emit(light, above, L, E, tmax)) {
-            const f3 N = mk3(m0.x, m0.y, m0.z), albedo = mk3(m1.x, m1.y, m1.z);
-            const float metallic = m2.x, roughness = m2.y, transmission = m2.z;
-            const f3 V = normalize3(-mk3(rd.x, rd.y, rd.z));
-            NFrame FN;
-            make_frame(N, FN);
-            const f3 direct = mk3(0.0f, 0.0f, 0.0f) + microfacet_brdf(FN, L, V, N, albedo, metallic, roughness, transmission) * E;
-            c = make_float4(direct.x, direct.y, direct.z, 0.0f);
-            s0 = make_float4(above.x, above.y, above.z, 0.001f);
-            s1 = make_float4(L.x, L.y, L.z, tmax);
-        }
-    }
-    lit[i] = c;
-    if (shadow) { shadow[2 * (size_t)i] = s0; shadow[2 * (size_t)i + 1] = s1; }
+    light_hits(rays, mats, n, lit, shadow,
+               [=](uint32_t, const f3& above, f3& L, f3& E, float& tmax) { return punctual_emit(light, above, L, E, tmax); });
 }
 
-// k_lights_shade (light_paths.hip) over the caller's table.  One live ray per lane.  Every gather of a hit is fenced by
-// shade_in_bounds (shade.h), asked before and after the index gather exactly as k_resolve_materials asks it, plus the slotOf check;
-// a hit that fails is a miss and is counted -- one ballot per wave, one atomic by its first lane, and only where the wave has such
-// a hit.  The survivors are compacted by k_scatter_hits' rule -- the survivors of 64 consecutive live rays stay together and in
-// order: a lane's record is the block's base from ONE atomic on *live per BLOCK, plus the survivors of the block's earlier waves,
-// plus the lane's rank in its wave's ballot.  `lights` is the table: the same address in every lane and a loop counter that is
-// uniform, so each record's sixteen words arrive through the scalar cache; the loop stays rolled, so microfacet_brdf is in the code
-// once.  The table is the one thing the caller's records can point the kernel at, and the host has checked its nLights records
-// into their buffer.  20 bytes of LDS: the block's four survivor counts and its base.
-__global__ void __launch_bounds__(PUNCTUAL_BLOCK)
+// path_shade over records 0 .. nLights - 1 of the table: k_punctual_light_hits for record j.
+__global__ void __launch_bounds__(PATH_SHADE_BLOCK)
 k_punctual_shade(const DInst* __restrict__ insts, const uint32_t* __restrict__ slotOf, uint32_t nInst, ShadeScene sc,
                  const PunctualLight* __restrict__ lights, uint32_t nLights, LightPathStreams io, uint32_t n, uint32_t depth, uint32_t sampleNext,
                  uint32_t* __restrict__ live, uint32_t* __restrict__ invalid)
 {
-    const uint32_t i = blockIdx.x * PUNCTUAL_BLOCK + threadIdx.x;
-    bool alive = false, bad = false;
-    uint4 id = make_uint4(0u, 0u, 0u, 0u);
-    float4 w = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-    float4 ro = make_float4(0.f, 0.f, 0.f, 0.f), rd = ro, ha = ro;
-    uint32_t prim = 0u, inst = 0u, slot = 0xffffffffu, idx[3] = {0u, 0u, 0u};
-    const bool texOn = (sc.tex.flags & TEX_ENABLED) != 0u;
-    if (i < n) {
-        ro = io.rays[2 * (size_t)i]; rd = io.rays[2 * (size_t)i + 1];
-        ha = io.hits[2 * (size_t)i];
-        const float4 hb = io.hits[2 * (size_t)i + 1];
-        if (depth == 0u) {
-            const uint4 key = io.keys[i];
-            id = make_uint4(i, key.x, key.y, 0u);
-        } else {
-            id = io.ids[i];
-            w = io.weight[i];
-        }
-        if (__float_as_uint(ha.w) == 1u) {
-            prim = __float_as_uint(hb.x); inst = __float_as_uint(hb.y);
-            bool ok = shade_in_bounds(sc.s.meshInfo, nInst, sc.s.nMeshInfo, inst, prim, nullptr, sc.s.nIndex, sc.s.nNormal, sc.s.nUv, sc.materials,
-                                      sc.nMaterials, texOn, sc.tex.layers);
-            if (ok) {
-                slot = slotOf[inst];        // 0xffffffff: no instance of the TLAS carries this index (a foreign blob)
-                const int64_t first = (int64_t)sc.s.meshInfo[inst].indexOffset + (int64_t)prim * 3;
-                idx[0] = sc.s.index[first]; idx[1] = sc.s.index[first + 1]; idx[2] = sc.s.index[first + 2];
-                ok = slot < nInst && shade_in_bounds(sc.s.meshInfo, nInst, sc.s.nMeshInfo, inst, prim, idx, sc.s.nIndex, sc.s.nNormal, sc.s.nUv,
-                                                     sc.materials, sc.nMaterials, texOn, sc.tex.layers);
-            }
-            alive = ok;
-            bad = !ok;
-        }
-        // a path's colour starts at zero; a miss at depth 0 shows the stock miss colour (stages.h `environment`)
-        if (depth == 0u) io.radiance[i] = alive ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(0.2f, 0.2f, 0.5f, 0.0f);
-    }
-    // wave64 ballots: every lane of the wave is here (no thread has returned)
-    const unsigned long long mb = __ballot(bad);
-    if (mb != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(invalid, (uint32_t)__popcll(mb));
-    const unsigned long long m = __ballot(alive);
-    const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6;
-    // the block's four ballots are summed in LDS and the cursor moves ONCE per block, as in k_lights_shade
-    __shared__ uint32_t s_count[PUNCTUAL_BLOCK / 64], s_base;
-    if (lane == 0u) s_count[wave] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint32_t total = 0u;
-        for (uint32_t v = 0; v < PUNCTUAL_BLOCK / 64; ++v) total += s_count[v];
-        s_base = total ? atomicAdd(live, total) : 0u;
-    }
-    __syncthreads();
-    if (!alive) return;
-    uint32_t base = s_base;
-    for (uint32_t v = 0; v < wave; ++v) base += s_count[v];
-    const size_t k = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-
-    // ---- the material record of k_resolve_materials and the `below` of k_resolve_hits, in registers ----
-    const MeshInfo mi = sc.s.meshInfo[inst];
-    const Material mt = sc.materials[mi.materialIndex];
-    const DInst& I = insts[slot];
-    // HitData.hitPoint = localOrigin + localDir * t and barycentric, as kernels.hip fill_hit_info (radiance.cl:243)
-    HitInfo h;
-    const f3 lo = mat4_mul3(I.inv, ro.x, ro.y, ro.z, 1.0f);
-    const f3 ld = mat4_mul3(I.inv, rd.x, rd.y, rd.z, 0.0f);
-    h.hitPoint = lo + ld * ha.x;
-    h.bx = 1 - ha.y - ha.z; h.by = ha.y; h.bz = ha.z;
-    h.primitiveIndex = prim;
-    h.instanceIndex = inst;
-    h.fwd = I.fwd;
-    // interpolated vertex normal -> world by the object->world matrix, w = 0 (shader.cl:340-368); the positions are those
-    // shade_in_bounds proved inside, in 64 bits
-    const float* nb = sc.s.normal + (int64_t)mi.normalOffset;
-    const int64_t v0 = (int64_t)idx[0] * 3, v1 = (int64_t)idx[1] * 3, v2 = (int64_t)idx[2] * 3;
-    const f3 n0 = mk3(nb[v0], nb[v0 + 1], nb[v0 + 2]);
-    const f3 n1 = mk3(nb[v1], nb[v1 + 1], nb[v1 + 2]);
-    const f3 n2 = mk3(nb[v2], nb[v2 + 1], nb[v2 + 2]);
-    const f3 nl = mk3(h.bx * n0.x + h.by * n1.x + h.bz * n2.x, h.bx * n0.y + h.by * n1.y + h.bz * n2.y,
-                      h.bx * n0.z + h.by * n1.z + h.bz * n2.z);
-    const float nw = h.bx * 0.0f + h.by * 0.0f + h.bz * 0.0f;
-    const f3 faceN = normalize3(mat4_mul3(h.fwd, nl.x, nl.y, nl.z, nw));
-    // getHitPosition(hitData, +-faceN) (shader.cl:453-468): transform * (hitPoint, 1), pushed off the surface along N and along -N
-    const f3 P = mat4_mul3(h.fwd, h.hitPoint.x, h.hitPoint.y, h.hitPoint.z, 1.0f);
-    const f3 above = P + faceN * 0.00001f;
-    const f3 below = P + (-faceN) * 0.00001f;
-
-    // texels are read only when option "textures" is on and an image array is given (TEX_ENABLED); otherwise a material with a
-    // texture index sees texel 0, as in the live reference shader (stages.h:255-257)
-    float tu = 0.0f, tv = 0.0f;
-    if (texOn) {     // getUV, shader.cl:323-338
-        const float* ub = sc.s.uv + (int64_t)mi.uvOffset;
-        tu = h.bx * ub[v0] + h.by * ub[v1] + h.bz * ub[v2];
-        tv = h.bx * ub[v0 + 1] + h.by * ub[v1 + 1] + h.bz * ub[v2 + 1];
-    }
-    f3 N = faceN;       // getMatNormal, shader.cl:369-395
-    if (mt.normalTexIdx != -1) {
-        uint32_t tx[4] = {0u, 0u, 0u, 0u};
-        if (texOn) tex_read_ui(sc.tex, tu, 1.0f - tv, (float)mt.normalTexIdx, tx);
-        f4 t; t.x = cl_clamp((float)tx[0] / 255.0f, 0.0f, 1.0f) * 2.0f - 1.0f; t.y = cl_clamp((float)tx[1] / 255.0f, 0.0f, 1.0f) * 2.0f - 1.0f;
-        t.z = cl_clamp((float)tx[2] / 255.0f, 0.0f, 1.0f) * 2.0f - 1.0f; t.w = 0.0f * 2.0f - 1.0f;
-        t = normalize4(t);
-        float tbn[16];
-        normal_space(faceN, tbn);
-        N = normalize3(mat4_mul3(tbn, t.x, t.y, t.z, t.w));
-    }
-    float metallic = mt.metallic;       // getMaterialProp, shader.cl:398-430
-    if (mt.metallicTexIdx != -1) {
-        uint32_t tx[4] = {0u, 0u, 0u, 0u};
-        if (texOn) tex_read_ui(sc.tex, tu, 1.0f - tv, (float)mt.metallicTexIdx, tx);
-        metallic = cl_clamp((float)tx[2] / 255.0f, 0.0f, 1.0f);                   // .z (shader.cl:412)
-    }
-    float roughness = cl_clamp(mt.roughness, 0.0f, 1.0f);
-    if (mt.roughnessTexIdx != -1) {
-        uint32_t tx[4] = {0u, 0u, 0u, 0u};
-        if (texOn) tex_read_ui(sc.tex, tu, 1.0f - tv, (float)mt.roughnessTexIdx, tx);
-        roughness = cl_clamp((float)tx[1] / 255.0f, 0.05f, 1.0f);                 // .y (shader.cl:422)
-    }
-    const float transmission = cl_clamp(mt.transmission, 0.0f, 1.0f);
-    const float ior = cl_clamp(mt.ior, 0.0f, 10.0f);
-    f3 albedo = mk3(mt.albedo[0], mt.albedo[1], mt.albedo[2]);       // getAlbedo, shader.cl:432-451
-    if (mt.albedoTexIdx != -1) {
-        uint32_t tx[4] = {0u, 0u, 0u, 0u};
-        if (texOn) tex_read_ui(sc.tex, tu, 1.0f - tv, (float)mt.albedoTexIdx, tx);
-        albedo = mk3(cl_clamp((float)tx[0] / 255.0f, 0.0f, 1.0f), cl_clamp((float)tx[1] / 255.0f, 0.0f, 1.0f), cl_clamp((float)tx[2] / 255.0f, 0.0f, 1.0f));
-    }
-
-    // ---- one frame for all lights and the sample (k_punctual_light_hits and k_scatter_hits each build this one from the record's N) ----
-    const f3 V = normalize3(-mk3(rd.x, rd.y, rd.z));
-    NFrame FN;
-    make_frame(N, FN);
-
-    // ---- k_punctual_light_hits for record j = 0 .. L - 1: records k * L + j, ray-major ----
-#pragma unroll 1
-    for (uint32_t j = 0; j < nLights; ++j) {
-        float4 c = make_float4(0.f, 0.f, 0.f, 0.f), s0 = c, s1 = c;      // a dark record: zeros
-        f3 L, E;
-        float tmax;
-        if (punctual_emit(lights + j, above, L, E, tmax)) {
-            const f3 direct = mk3(0.0f, 0.0f, 0.0f) + microfacet_brdf(FN, L, V, N, albedo, metallic, roughness, transmission) * E;
-            c = make_float4(direct.x, direct.y, direct.z, 0.0f);
-            s0 = make_float4(above.x, above.y, above.z, 0.001f);
-            s1 = make_float4(L.x, L.y, L.z, tmax);
-        }
-        const size_t r = k * nLights + j;
-        io.lit[r] = c;
-        io.shadow[2 * r] = s0;
-        io.shadow[2 * r + 1] = s1;
-    }
-
-    // ---- k_scatter_hits with the key (frameID, pixel, depth) ----
-    f3 nf = mk3(0.f, 0.f, 0.f);
-    if (sampleNext) {
-        const f3 rnd = pcg3d(id.y, id.z, depth);
-        const f3 nd = sample_brdf_transm(FN, V, N, albedo, metallic, roughness, transmission, ior, rnd, nf);
-        const f3 origin = dot3(nd, N) < 0 ? below : above;      // getHitPosition(hitData, -+faceN)
-        io.nRays[2 * k] = make_float4(origin.x, origin.y, origin.z, 0.001f);
-        io.nRays[2 * k + 1] = make_float4(nd.x, nd.y, nd.z, 1000.0f);
-    }
-    const f3 ambient = albedo * 0.1f;
-    io.nIds[k] = id;
-    io.nWeight[k] = w;
-    io.foldF[k] = make_float4(nf.x, nf.y, nf.z, 0.0f);
-    io.foldA[k] = make_float4(ambient.x, ambient.y, ambient.z, 0.0f);
+    path_shade(insts, slotOf, nInst, sc, PunctualSource{lights, nLights}, io, n, depth, sampleNext, live, invalid);
 }
 
 void launch_punctual_light_hits(hipStream_t st, const float4* rays, const float4* materials, uint32_t n, const PunctualLight* light, float4* lit,
                                 float4* shadow)
 {
     if (!n) return;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + PUNCTUAL_BLOCK - 1) / PUNCTUAL_BLOCK);
-    hipLaunchKernelGGL(k_punctual_light_hits, dim3(blocks), dim3(PUNCTUAL_BLOCK), 0, st, rays, materials, n, light, lit, shadow);
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + LIGHT_HITS_BLOCK - 1) / LIGHT_HITS_BLOCK);
+    hipLaunchKernelGGL(k_punctual_light_hits, dim3(blocks), dim3(LIGHT_HITS_BLOCK), 0, st, rays, materials, n, light, lit, shadow);
 }
 
 void launch_punctual_shade(hipStream_t st, const DInst* insts, const uint32_t* slotOf, uint32_t nInst, const ShadeScene& sc, const PunctualLight* lights,
@@ -284,8 +47,8 @@ void launch_punctual_shade(hipStream_t st, const DInst* insts, const uint32_t* s
                            uint32_t* invalid)
 {
     if (!n) return;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + PUNCTUAL_BLOCK - 1) / PUNCTUAL_BLOCK);
-    hipLaunchKernelGGL(k_punctual_shade, dim3(blocks), dim3(PUNCTUAL_BLOCK), 0, st, insts, slotOf, nInst, sc, lights, nLights, io, n, depth,
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + PATH_SHADE_BLOCK - 1) / PATH_SHADE_BLOCK);
+    hipLaunchKernelGGL(k_punctual_shade, dim3(blocks), dim3(PATH_SHADE_BLOCK), 0, st, insts, slotOf, nInst, sc, lights, nLights, io, n, depth,
                        sampleNext ? 1u : 0u, live, invalid);
 }
 

@@ -148,3 +148,14 @@ def test_every_symbol_is_present(mods):
     assert C.sizeof(_lib.rdx_debug_range) == 40
     assert hasattr(rd, "DebugCheckRanges")
     assert rd.DebugCheckRanges([], 0, 1) is None
+
+
+def test_every_header_of_csrc_is_a_dependency_of_the_library(built):
+    """editing any csrc/*.h must rebuild librdx.so: build.py compares the library's time stamp with SOURCES + HEADERS only"""
+    import rrt_amd  # noqa: F401
+    from radiance_ray_tracing_amd import build
+    csrc = os.path.join(ROOT, "radiance-ray-tracing_amd", "csrc")
+    on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".h"))
+    assert len(on_disk) >= 20 and all(os.path.exists(os.path.join(csrc, h)) for h in build.HEADERS)
+    assert [h for h in on_disk if h not in build.HEADERS] == []
+    assert len(set(build.HEADERS)) == len(build.HEADERS)
