@@ -420,11 +420,147 @@ def TraceBatch(tlas, origins, dirs, tmin=0.001, tmax=1000.0, sbtRecordOffset=1, 
     return (out, visit) if count_visits else out
 
 
+# ---- the argument layer of the device-resident calls, QueryRays .. TraceAreaPathsTorch -----------------------
+# Every call below has a Buffer route (device buffers in and out) and a torch route (CUDA tensors, wrapped and handed to the Buffer
+# route).  What the two routes decide about their arguments is decided here once: the formats of the records, the rules of Buffer
+# arguments and of created outputs, the integer checks, and the steps of a call on tensors.
+_RECORDS = {}
+
+
+def _record(kind, dtype, *torch_dtypes):
+    """one row of the record table: a record kind's bytes, its torch columns (4-byte words; None: a one-dimensional tensor) and the
+    names of the torch dtypes accepted for it, first the one a created tensor gets"""
+    _RECORDS[kind] = (dtype.itemsize, dtype.itemsize // 4 if dtype.itemsize > 4 else None, torch_dtypes)
+
+
+_record("float4", np.dtype(("<f4", 4)), "float32")       # lit, radiance, randoms, colours
+_record("src", np.dtype("<u4"), "int32")
+_record("pixel", np.dtype("<u4"), "int32")
+
+
+def _buffers(who, **named):
+    """the arguments of `who` that must be Buffers, by name"""
+    if not all(isinstance(b, Buffer) for b in named.values()):
+        *most, last = named
+        if not most:
+            raise RadianceError("%s: %s must be a Buffer (CreateBuffer / WrapDeviceMemory)" % (who, last))
+        raise RadianceError("%s: %s and %s must be Buffers (CreateBuffer / WrapDeviceMemory)" % (who, ", ".join(most), last))
+
+
+def _optional_buffer(who, buf, what):
+    """-> the handle of an argument that is a Buffer or None"""
+    if buf is not None and not isinstance(buf, Buffer):
+        raise RadianceError("%s: %s must be a Buffer or None" % (who, what))
+    return _h(buf)
+
+
+def _h(buf):
+    return buf.handle if buf is not None else None
+
+
+def _out_buffer(who, n, buf, offset, kind, what, optional, or_true=None, flags=True):
+    """an output argument: a Buffer; True, or None where it is not optional: created for n records of `kind` behind `offset`;
+    None / False where it is optional: not wanted.  or_true: the refusal names True as a choice (default: where optional).
+    flags=False: the position takes a Buffer or None alone, and True / False are refused like any other value"""
+    if (buf is True and flags) or (buf is None and not optional):
+        return CreateBuffer(None, max(int(offset) + _RECORDS[kind][0] * int(n), 1))
+    if buf is None or (buf is False and flags):
+        return None
+    if not isinstance(buf, Buffer):
+        raise RadianceError("%s: %s must be a Buffer%s" % (who, what, ", True or None" if (optional if or_true is None else or_true) else " or None"))
+    return buf
+
+
+def _is_count(x, most=None):
+    """x is a non-negative integer, no bool, and at most `most`"""
+    return not isinstance(x, bool) and isinstance(x, (int, np.integer)) and 0 <= x and (most is None or x <= most)
+
+
+def _count(who, x, rule, most=None):
+    """-> int(x), or the refusal `rule` in the words of the caller"""
+    if not _is_count(x, most):
+        raise RadianceError("%s: %s" % (who, rule))
+    return int(x)
+
+
+def _keys_or_randoms(who, keys, randoms):
+    """-> the handles of `keys` and `randoms`, exactly one of which is a Buffer and the other None"""
+    handles = _optional_buffer(who, keys, "keys"), _optional_buffer(who, randoms, "randoms")
+    if keys is None and randoms is None:
+        raise RadianceError("%s: neither keys nor randoms given: one of the two is required" % who)
+    if keys is not None and randoms is not None:
+        raise RadianceError("%s: both keys and randoms given: only one of the two is allowed" % who)
+    return handles
+
+
+def _cuda_tensor(who, t, kind, what, rows=None, device=None, owner="rays"):
+    """-> the rows of `t`: a contiguous CUDA tensor of records of `kind`, of `rows` rows (None: any number), on `device` (the device
+    of the owner's tensor) if one is given; anything else is a RadianceError"""
+    import torch
+    _, cols, names = _RECORDS[kind]
+    shape = () if cols is None else (cols,)
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and str(t.dtype).replace("torch.", "") in names and t.dim() == 1 + len(shape)
+            and tuple(t.shape[1:]) == shape and rows in (None, t.shape[0]) and t.is_contiguous() and (device is None or t.device == device)):
+        raise RadianceError("%s: %s must be a contiguous %s CUDA tensor of shape (n,%s)%s"
+                            % (who, what, " / ".join(names), "" if cols is None else " %d" % cols, " on the %s' device" % owner if device is not None else ""))
+    return int(t.shape[0])
+
+
+class _TorchCall:
+    """the torch route of one call.  `first` fixes n and the device; `also` holds a further tensor to them; `new` allocates an output;
+    `begin` synchronises; `wrap` adopts a tensor as the Buffer the Buffer route takes"""
+
+    def __init__(self, who):
+        import torch
+        self.torch, self.who, self.n, self.device = torch, who, None, None
+
+    def first(self, t, kind, what, device=None, owner="rays"):
+        self.n, self.device = _cuda_tensor(self.who, t, kind, what, None, device, owner), t.device
+
+    def also(self, t, kind, what, owner="rays"):
+        _cuda_tensor(self.who, t, kind, what, self.n, self.device, owner)
+
+    def keys_or_randoms(self, keys, randoms):
+        if (keys is None) == (randoms is None):
+            raise RadianceError("%s: exactly one of keys and randoms must be given" % self.who)
+        if keys is not None:
+            self.also(keys, "key", "keys")
+        if randoms is not None:
+            self.also(randoms, "float4", "randoms")
+
+    def new(self, kind, wanted=True):
+        """an output tensor of n records of `kind`, or None where it is not wanted"""
+        _, cols, names = _RECORDS[kind]
+        if not wanted:
+            return None
+        shape = (self.n,) if cols is None else (self.n, cols)
+        return self.torch.empty(shape, dtype=getattr(self.torch, names[0]), device=self.device)
+
+    def given_or_new(self, t, kind, what):
+        """an output tensor of the caller's, held to n and the device, or None: a new one"""
+        if t is None:
+            return self.new(kind)
+        self.also(t, kind, what)
+        return t
+
+    def begin(self):
+        """The library cannot see torch's stream, so the current stream is synchronised.  -> whether there is anything to do: with
+        n == 0 nothing is wrapped and the library is not called"""
+        self.torch.cuda.current_stream(self.device).synchronize()
+        return self.n != 0
+
+    def wrap(self, t, kind, rows=None):
+        """the Buffer over the first `rows` (default: n) records of tensor `t`, which it keeps alive; None for None"""
+        return WrapDeviceMemory(None, t.data_ptr(), (self.n if rows is None else rows) * _RECORDS[kind][0], keepalive=t) if t is not None else None
+
+
 # ---- ray queries on device memory (rdx_query_rays) ---------------------------------------------------------------
 RAY_DTYPE = np.dtype([("origin", "<f4", 3), ("tmin", "<f4"), ("direction", "<f4", 3), ("tmax", "<f4")])
 RAY_HIT_DTYPE = np.dtype([("t", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("hit", "<u4"), ("primitiveIndex", "<u4"),
                           ("instanceIndex", "<u4"), ("instanceCustomIndex", "<u4"), ("instanceSBTOffset", "<u4")])
 assert RAY_DTYPE.itemsize == C.sizeof(_lib.rdx_ray) == 32 and RAY_HIT_DTYPE.itemsize == C.sizeof(_lib.rdx_ray_hit) == 32
+_record("ray", RAY_DTYPE, "float32")
+_record("hit", RAY_HIT_DTYPE, "int32", "float32")
 QUERY_CLOSEST, QUERY_ANY = 1, 2
 
 
@@ -433,44 +569,21 @@ def QueryRays(tlas, rays, n, kind=QUERY_CLOSEST, hits=None, rays_offset=0, hits_
     against `tlas`; one RAY_HIT_DTYPE record per ray goes to the device buffer `hits` at byte `hits_offset` (created when None:
     hits_offset + 32 n bytes).  kind: QUERY_CLOSEST (sbtRecordOffset 1) or QUERY_ANY (2: only `hit` is meaningful).  Nothing
     passes through the host.  Returns `hits`."""
-    if not isinstance(rays, Buffer) or not isinstance(tlas, Buffer):
-        raise RadianceError("QueryRays: tlas and rays must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    if hits is None:
-        hits = CreateBuffer(None, max(int(hits_offset) + RAY_HIT_DTYPE.itemsize * int(n), 1))
-    elif not isinstance(hits, Buffer):
-        raise RadianceError("QueryRays: hits must be a Buffer or None")
+    _buffers("QueryRays", tlas=tlas, rays=rays)
+    hits = _out_buffer("QueryRays", n, hits, hits_offset, "hit", "hits", False, flags=False)
     _check(_lib.lib().rdx_query_rays(tlas.handle, rays.handle, int(rays_offset), int(n), int(kind), hits.handle, int(hits_offset)))
     return hits
-
-
-def _cuda_tensor(who, t, dtypes, shape, what, device=None, owner="rays"):
-    """-> n, the rows of `t`: a contiguous CUDA tensor of one of `dtypes` and of `shape` (shape[0] None: any n), on `device` (the
-    device of the owner's tensor) if one is given; anything else is a RadianceError"""
-    import torch
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:])
-            and shape[0] in (None, t.shape[0]) and t.is_contiguous() and (device is None or t.device == device)):
-        raise RadianceError("%s: %s must be a contiguous %s CUDA tensor of shape (n,%s)%s"
-                            % (who, what, " / ".join(str(d).replace("torch.", "") for d in dtypes), "".join(" %d" % s for s in shape[1:]),
-                               " on the %s' device" % owner if device is not None else ""))
-    return int(t.shape[0])
 
 
 def QueryRaysTorch(tlas, rays_tensor, kind=QUERY_CLOSEST, out=None):
     """Extension: rays from a contiguous float32 CUDA tensor of shape (n, 8) -- origin, tmin, direction, tmax per row; the records
     land in `out`, an int32 (or float32) CUDA tensor of shape (n, 8) (created when None: int32; `.view(torch.float32)` shows t,
     b1, b2).  The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
-    import torch
-    t = rays_tensor
-    n = _cuda_tensor("QueryRaysTorch", t, (torch.float32,), (None, 8), "rays")
-    if out is None:
-        out = torch.empty((n, 8), dtype=torch.int32, device=t.device)
-    else:
-        _cuda_tensor("QueryRaysTorch", out, (torch.int32, torch.float32), (n, 8), "out", t.device)
-    torch.cuda.current_stream(t.device).synchronize()
-    if n:
-        rays = WrapDeviceMemory(None, t.data_ptr(), n * 32, keepalive=t)
-        hits = WrapDeviceMemory(None, out.data_ptr(), n * 32, keepalive=out)
-        QueryRays(tlas, rays, n, kind, hits)
+    t = _TorchCall("QueryRaysTorch")
+    t.first(rays_tensor, "ray", "rays")
+    out = t.given_or_new(out, "hit", "out")
+    if t.begin():
+        QueryRays(tlas, t.wrap(rays_tensor, "ray"), t.n, kind, t.wrap(out, "hit"))
     return out
 
 
@@ -478,6 +591,7 @@ def QueryRaysTorch(tlas, rays_tensor, kind=QUERY_CLOSEST, out=None):
 SURFACE_DTYPE = np.dtype([("position", "<f4", 3), ("hit", "<u4"), ("normal", "<f4", 3), ("materialIndex", "<u4"),
                           ("above", "<f4", 3), ("u", "<f4"), ("below", "<f4", 3), ("v", "<f4")])
 assert SURFACE_DTYPE.itemsize == C.sizeof(_lib.rdx_surface) == 64
+_record("surface", SURFACE_DTYPE, "float32")
 
 
 class SurfaceBuffers:
@@ -502,18 +616,14 @@ def ResolveHits(tlas, rays, hits, n, scene_buffers, out=None, rays_offset=0, hit
     device buffers in, device buffer out (created when None: out_offset + 64 n bytes).  scene_buffers: a SurfaceBuffers, or a
     (meshInfo, index, uv, normal) tuple of Buffers.  Misses are 64 zero bytes; so are hits that would read outside a scene
     buffer, which are counted.  Returns (out, invalid)."""
-    if not (isinstance(tlas, Buffer) and isinstance(rays, Buffer) and isinstance(hits, Buffer)):
-        raise RadianceError("ResolveHits: tlas, rays and hits must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    _buffers("ResolveHits", tlas=tlas, rays=rays, hits=hits)
     if not isinstance(scene_buffers, SurfaceBuffers):
         try:
             scene_buffers = SurfaceBuffers(*scene_buffers)
         except TypeError:
             raise RadianceError("ResolveHits: scene_buffers must be a SurfaceBuffers or a (meshInfo, index, uv, normal) tuple")
     sb = scene_buffers._struct()
-    if out is None:
-        out = CreateBuffer(None, max(int(out_offset) + SURFACE_DTYPE.itemsize * int(n), 1))
-    elif not isinstance(out, Buffer):
-        raise RadianceError("ResolveHits: out must be a Buffer or None")
+    out = _out_buffer("ResolveHits", n, out, out_offset, "surface", "out", False, flags=False)
     invalid = C.c_uint32(0)
     _check(_lib.lib().rdx_resolve_hits(tlas.handle, rays.handle, int(rays_offset), hits.handle, int(hits_offset), int(n), C.byref(sb),
                                        out.handle, int(out_offset), C.byref(invalid)))
@@ -525,32 +635,33 @@ def ResolveHitsTorch(tlas, rays_tensor, hits_tensor, scene_buffers, out=None):
     tensor QueryRaysTorch returned for them; the records land in `out`, a contiguous float32 CUDA tensor of shape (n, 16)
     (created when None; `.view(torch.int32)` shows hit and materialIndex in columns 3 and 7).  The library cannot see torch's
     stream, so the current stream is synchronised first; the call blocks.  Returns (out, invalid)."""
-    import torch
-    r, h = rays_tensor, hits_tensor
-    n = _cuda_tensor("ResolveHitsTorch", r, (torch.float32,), (None, 8), "rays")
-    _cuda_tensor("ResolveHitsTorch", h, (torch.int32, torch.float32), (n, 8), "hits", r.device)
-    if out is None:
-        out = torch.empty((n, 16), dtype=torch.float32, device=r.device)
-    else:
-        _cuda_tensor("ResolveHitsTorch", out, (torch.float32,), (n, 16), "out", r.device)
-    torch.cuda.current_stream(r.device).synchronize()
+    t = _TorchCall("ResolveHitsTorch")
+    t.first(rays_tensor, "ray", "rays")
+    t.also(hits_tensor, "hit", "hits")
+    out = t.given_or_new(out, "surface", "out")
     invalid = 0
-    if n:
-        rays = WrapDeviceMemory(None, r.data_ptr(), n * 32, keepalive=r)
-        hits = WrapDeviceMemory(None, h.data_ptr(), n * 32, keepalive=h)
-        dst = WrapDeviceMemory(None, out.data_ptr(), n * 64, keepalive=out)
-        _, invalid = ResolveHits(tlas, rays, hits, n, scene_buffers, dst)
+    if t.begin():
+        _, invalid = ResolveHits(tlas, t.wrap(rays_tensor, "ray"), t.wrap(hits_tensor, "hit"), t.n, scene_buffers, t.wrap(out, "surface"))
     return out, invalid
 
 
 def DebugSurfaceInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv, nmeshinfo=None):
     """Test seam (rdx_debug_surface_in_bounds): the bounds rule of ResolveHits for one record, on the host -> bool.  meshInfo: a
     MeshInfo array (nmeshinfo defaults to its length), idx3: the triangle's three vertex numbers or None."""
+    shared = _bounds_arguments(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv, nmeshinfo)
+    return _in_bounds(_lib.lib().rdx_debug_surface_in_bounds(*shared))
+
+
+def _bounds_arguments(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv, nmeshinfo):
+    """what DebugSurfaceInBounds and DebugShadeInBounds hand to the library alike, in its order (the pointer keeps its array alive)"""
     mi = np.ascontiguousarray(meshInfo, MeshInfo).reshape(-1)
-    nm = mi.shape[0] if nmeshinfo is None else int(nmeshinfo)
     iv = None if idx3 is None else (C.c_uint32 * 3)(*[int(x) & 0xffffffff for x in idx3])
-    rc = _lib.lib().rdx_debug_surface_in_bounds(mi.ctypes.data_as(C.POINTER(_lib.rdx_mesh_info)), int(ninst), nm, int(instanceIndex) & 0xffffffff,
-                                                int(primitiveIndex) & 0xffffffff, iv, int(nindex), int(nnormal), int(nuv))
+    nm = mi.shape[0] if nmeshinfo is None else int(nmeshinfo)
+    return (mi.ctypes.data_as(C.POINTER(_lib.rdx_mesh_info)), int(ninst), nm, int(instanceIndex) & 0xffffffff, int(primitiveIndex) & 0xffffffff, iv,
+            int(nindex), int(nnormal), int(nuv))
+
+
+def _in_bounds(rc):
     if rc < 0:
         raise RadianceError(_lib.last_error())
     return rc == 1
@@ -575,6 +686,8 @@ SHADE_DTYPE = np.dtype([("color", "<f4", 3), ("hit", "<u4"), ("colorOccluded", "
                         ("nextFactor", "<f4", 3), ("slot", "<u4")])
 assert SHADE_DTYPE.itemsize == C.sizeof(_lib.rdx_shade) == 48 and SHADE_KEY_DTYPE.itemsize == C.sizeof(_lib.rdx_shade_key) == 16
 assert C.sizeof(_lib.rdx_shading_buffers) == 8 * C.sizeof(C.c_void_p)
+_record("key", SHADE_KEY_DTYPE, "int32")
+_record("shade", SHADE_DTYPE, "float32")
 NO_SLOT = 0xffffffff
 
 
@@ -596,9 +709,8 @@ class ShadingBuffers:
                 raise RadianceError("%s: scene_buffers.%s must be a Buffer or None" % (who, name))
         if self.sampler is not None and not isinstance(self.sampler, Sampler):
             raise RadianceError("%s: scene_buffers.sampler must be a Sampler or None" % who)
-        h = lambda x: x.handle if x is not None else None
-        return _lib.rdx_shading_buffers(self.scene.handle, self.meshInfo.handle, self.index.handle, h(self.uv), self.normal.handle,
-                                        self.material.handle, h(self.textureArray), h(self.sampler))
+        return _lib.rdx_shading_buffers(self.scene.handle, self.meshInfo.handle, self.index.handle, _h(self.uv), self.normal.handle,
+                                        self.material.handle, _h(self.textureArray), _h(self.sampler))
 
 
 def _shading_struct(who, scene_buffers):
@@ -610,18 +722,6 @@ def _shading_struct(who, scene_buffers):
             raise RadianceError("%s: scene_buffers must be a ShadingBuffers or a (scene, meshInfo, index, uv, normal, material"
                                 "[, textureArray, sampler]) tuple" % who)
     return scene_buffers._struct(who)
-
-
-def _out_buffer(who, n, buf, offset, rec, what, optional, or_true=None):
-    """an output argument: a Buffer; True, or None where it is not optional: created for n records of `rec` bytes behind `offset`;
-    None / False where it is optional: not wanted.  or_true: the refusal names True as a choice (default: where optional)"""
-    if buf is True or (buf is None and not optional):
-        return CreateBuffer(None, max(int(offset) + rec * n, 1))
-    if buf is None or buf is False:
-        return None
-    if not isinstance(buf, Buffer):
-        raise RadianceError("%s: %s must be a Buffer%s" % (who, what, ", True or None" if (optional if or_true is None else or_true) else " or None"))
-    return buf
 
 
 def ShadeHits(tlas, rays, hits, keys, n, scene_buffers, shade=None, next=True, shadow=True, src=None, compact=False, rays_offset=0,
@@ -637,19 +737,17 @@ def ShadeHits(tlas, rays, hits, keys, n, scene_buffers, shade=None, next=True, s
     in input order, the groups in no fixed order), src[k] = the ray's number, and records from `live` on are untouched; without,
     k = i and the record of a ray that does not survive is zeros.  Returns (shade, next, shadow, src, live, invalid): `live`
     survivors; `invalid` hits that would read outside a scene buffer, zeroed and counted."""
-    if not all(isinstance(b, Buffer) for b in (tlas, rays, hits, keys)):
-        raise RadianceError("ShadeHits: tlas, rays, hits and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    _buffers("ShadeHits", tlas=tlas, rays=rays, hits=hits, keys=keys)
     sb = _shading_struct("ShadeHits", scene_buffers)
     n = int(n)
-    shade = _out_buffer("ShadeHits", n, shade, shade_offset, SHADE_DTYPE.itemsize, "shade", False)
-    next = _out_buffer("ShadeHits", n, next, next_offset, RAY_DTYPE.itemsize, "next", True)
-    shadow = _out_buffer("ShadeHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
-    src = _out_buffer("ShadeHits", n, True if (src is None and compact) else src, src_offset, 4, "src", True)
+    shade = _out_buffer("ShadeHits", n, shade, shade_offset, "shade", "shade", False)
+    next = _out_buffer("ShadeHits", n, next, next_offset, "ray", "next", True)
+    shadow = _out_buffer("ShadeHits", n, shadow, shadow_offset, "ray", "shadow", True)
+    src = _out_buffer("ShadeHits", n, True if (src is None and compact) else src, src_offset, "src", "src", True)
     live, invalid = C.c_uint32(0), C.c_uint32(0)
-    h = lambda b: b.handle if b is not None else None
     _check(_lib.lib().rdx_shade_hits(tlas.handle, rays.handle, int(rays_offset), hits.handle, int(hits_offset), keys.handle, int(keys_offset), n,
-                                     C.byref(sb), shade.handle, int(shade_offset), h(next), int(next_offset), h(shadow), int(shadow_offset),
-                                     h(src), int(src_offset), C.byref(live), C.byref(invalid)))
+                                     C.byref(sb), shade.handle, int(shade_offset), _h(next), int(next_offset), _h(shadow), int(shadow_offset),
+                                     _h(src), int(src_offset), C.byref(live), C.byref(invalid)))
     return shade, next, shadow, src, int(live.value), int(invalid.value)
 
 
@@ -660,21 +758,18 @@ def ShadeHitsTorch(tlas, rays_t, hits_t, keys_t, scene_buffers, compact=True, sa
     7, 11), next / shadow float32 (live, 8) when compacting -- already sliced to the survivors -- else (n, 8), src int32 (live,)
     or None; next is None without sample_next.  The library cannot see torch's stream, so the current stream is synchronised
     first; the call blocks."""
-    import torch
-    r, h, k = rays_t, hits_t, keys_t
-    n = _cuda_tensor("ShadeHitsTorch", r, (torch.float32,), (None, 8), "rays")
-    _cuda_tensor("ShadeHitsTorch", h, (torch.int32, torch.float32), (n, 8), "hits", r.device)
-    _cuda_tensor("ShadeHitsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
-    shade = torch.empty((n, 12), dtype=torch.float32, device=r.device)
-    nxt = torch.empty((n, 8), dtype=torch.float32, device=r.device) if sample_next else None
-    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device)
-    src = torch.empty((n,), dtype=torch.int32, device=r.device) if compact else None
-    torch.cuda.current_stream(r.device).synchronize()
+    t = _TorchCall("ShadeHitsTorch")
+    t.first(rays_t, "ray", "rays")
+    t.also(hits_t, "hit", "hits")
+    t.also(keys_t, "key", "keys")
+    shade = t.new("shade")
+    nxt = t.new("ray", sample_next)
+    shadow = t.new("ray")
+    src = t.new("src", compact)
     live = invalid = 0
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-        _, _, _, _, live, invalid = ShadeHits(tlas, wrap(r, 32), wrap(h, 32), wrap(k, 16), n, scene_buffers, wrap(shade, 48), wrap(nxt, 32),
-                                              wrap(shadow, 32), wrap(src, 4))
+    if t.begin():
+        _, _, _, _, live, invalid = ShadeHits(tlas, t.wrap(rays_t, "ray"), t.wrap(hits_t, "hit"), t.wrap(keys_t, "key"), t.n, scene_buffers,
+                                              t.wrap(shade, "shade"), t.wrap(nxt, "ray"), t.wrap(shadow, "ray"), t.wrap(src, "src"))
     if compact:
         nxt, shadow, src = (nxt[:live] if nxt is not None else None), shadow[:live], src[:live]
     return shade, nxt, shadow, src, live, invalid
@@ -685,23 +780,18 @@ def DebugShadeInBounds(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nin
     """Test seam (rdx_debug_shade_in_bounds): the bounds rule of ShadeHits for one record, on the host -> bool.  As
     DebugSurfaceInBounds, plus `materials`: a Material array (nmaterials defaults to its length), textures: texels are read,
     layers: layers of the image array."""
-    mi = np.ascontiguousarray(meshInfo, MeshInfo).reshape(-1)
     mt = np.ascontiguousarray(materials, Material).reshape(-1)
-    nm = mi.shape[0] if nmeshinfo is None else int(nmeshinfo)
     nmat = mt.shape[0] if nmaterials is None else int(nmaterials)
-    iv = None if idx3 is None else (C.c_uint32 * 3)(*[int(x) & 0xffffffff for x in idx3])
-    rc = _lib.lib().rdx_debug_shade_in_bounds(mi.ctypes.data_as(C.POINTER(_lib.rdx_mesh_info)), int(ninst), nm, int(instanceIndex) & 0xffffffff,
-                                              int(primitiveIndex) & 0xffffffff, iv, int(nindex), int(nnormal), int(nuv),
-                                              mt.ctypes.data_as(C.POINTER(_lib.rdx_material)), nmat, 1 if textures else 0, int(layers))
-    if rc < 0:
-        raise RadianceError(_lib.last_error())
-    return rc == 1
+    shared = _bounds_arguments(meshInfo, ninst, instanceIndex, primitiveIndex, idx3, nindex, nnormal, nuv, nmeshinfo)
+    rc = _lib.lib().rdx_debug_shade_in_bounds(*shared, mt.ctypes.data_as(C.POINTER(_lib.rdx_material)), nmat, 1 if textures else 0, int(layers))
+    return _in_bounds(rc)
 
 
 # ---- the evaluated material of a query's hits, and one light's direct term (rdx_resolve_materials, rdx_light_hits) --------
 MATERIAL_RECORD_DTYPE = np.dtype([("normal", "<f4", 3), ("hit", "<u4"), ("albedo", "<f4", 3), ("materialIndex", "<u4"), ("metallic", "<f4"),
                                   ("roughness", "<f4"), ("transmission", "<f4"), ("ior", "<f4"), ("above", "<f4", 3), ("_0", "<u4")])
 assert MATERIAL_RECORD_DTYPE.itemsize == C.sizeof(_lib.rdx_material_record) == 64
+_record("material", MATERIAL_RECORD_DTYPE, "float32")
 MAX_LIGHTS = 5          # the DirLights of a SceneProperties
 
 
@@ -712,13 +802,9 @@ def ResolveMaterials(tlas, rays, hits, n, scene_buffers, out=None, rays_offset=0
     buffer out (created when None: out_offset + 64 n bytes).  scene_buffers: a ShadingBuffers or a tuple of its constructor's
     arguments, textures by ShadeHits' rule.  Misses are 64 zero bytes; so are hits that would read outside a scene buffer, which
     are counted.  Returns (out, invalid)."""
-    if not (isinstance(tlas, Buffer) and isinstance(rays, Buffer) and isinstance(hits, Buffer)):
-        raise RadianceError("ResolveMaterials: tlas, rays and hits must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    _buffers("ResolveMaterials", tlas=tlas, rays=rays, hits=hits)
     sb = _shading_struct("ResolveMaterials", scene_buffers)
-    if out is None:
-        out = CreateBuffer(None, max(int(out_offset) + MATERIAL_RECORD_DTYPE.itemsize * int(n), 1))
-    elif not isinstance(out, Buffer):
-        raise RadianceError("ResolveMaterials: out must be a Buffer or None")
+    out = _out_buffer("ResolveMaterials", n, out, out_offset, "material", "out", False, flags=False)
     invalid = C.c_uint32(0)
     _check(_lib.lib().rdx_resolve_materials(tlas.handle, rays.handle, int(rays_offset), hits.handle, int(hits_offset), int(n), C.byref(sb),
                                             out.handle, int(out_offset), C.byref(invalid)))
@@ -732,18 +818,25 @@ def LightHits(rays, materials, n, scene, light, lit=None, shadow=True, rays_offs
     light, a RAY_DTYPE record ready for QueryRays(..., QUERY_ANY), to `shadow` (a Buffer, True: created, None / False: not wanted).
     Records whose `hit` is not 1 give zeros.  The ambient term (albedo * 0.1 in the stock shader) stays the caller's.  Returns
     (lit, shadow)."""
-    if not all(isinstance(b, Buffer) for b in (rays, materials, scene)):
-        raise RadianceError("LightHits: rays, materials and scene must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    n, light = int(n), int(light)
-    if not 0 <= light < MAX_LIGHTS:
-        raise RadianceError("LightHits: light %d is not one of the %d lights of a SceneProperties (0 .. %d)" % (light, MAX_LIGHTS, MAX_LIGHTS - 1))
-    if lit is None:
-        lit = CreateBuffer(None, max(int(lit_offset) + 16 * n, 1))
-    elif not isinstance(lit, Buffer):
-        raise RadianceError("LightHits: lit must be a Buffer or None")
-    shadow = _out_buffer("LightHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
+    _buffers("LightHits", rays=rays, materials=materials, scene=scene)
+    n, light = int(n), _scene_light("LightHits", light)
+    lit, shadow = _lit_and_shadow("LightHits", n, lit, lit_offset, shadow, shadow_offset)
     _check(_lib.lib().rdx_light_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), n, scene.handle, light, lit.handle,
-                                     int(lit_offset), shadow.handle if shadow is not None else None, int(shadow_offset)))
+                                     int(lit_offset), _h(shadow), int(shadow_offset)))
+    return lit, shadow
+
+
+def _scene_light(who, light):
+    light = int(light)
+    if not 0 <= light < MAX_LIGHTS:
+        raise RadianceError("%s: light %d is not one of the %d lights of a SceneProperties (0 .. %d)" % (who, light, MAX_LIGHTS, MAX_LIGHTS - 1))
+    return light
+
+
+def _lit_and_shadow(who, n, lit, lit_offset, shadow, shadow_offset):
+    """the outputs of the three per-light calls: lit, a Buffer or None (created); shadow, a Buffer, True (created) or None / False"""
+    lit = _out_buffer(who, n, lit, lit_offset, "float4", "lit", False, flags=False)
+    shadow = _out_buffer(who, n, shadow, shadow_offset, "ray", "shadow", True)
     return lit, shadow
 
 
@@ -753,21 +846,13 @@ def ResolveMaterialsTorch(tlas, rays_tensor, hits_tensor, scene_buffers, out=Non
     (created when None): columns 0-2 the normal, 4-6 the albedo, 8-11 metallic, roughness, transmission, ior, 12-14 `above`;
     `.view(torch.int32)` shows hit and materialIndex in columns 3 and 7.  The library cannot see torch's stream, so the current
     stream is synchronised first; the call blocks.  Returns (out, invalid)."""
-    import torch
-    r, h = rays_tensor, hits_tensor
-    n = _cuda_tensor("ResolveMaterialsTorch", r, (torch.float32,), (None, 8), "rays")
-    _cuda_tensor("ResolveMaterialsTorch", h, (torch.int32, torch.float32), (n, 8), "hits", r.device)
-    if out is None:
-        out = torch.empty((n, 16), dtype=torch.float32, device=r.device)
-    else:
-        _cuda_tensor("ResolveMaterialsTorch", out, (torch.float32,), (n, 16), "out", r.device)
-    torch.cuda.current_stream(r.device).synchronize()
+    t = _TorchCall("ResolveMaterialsTorch")
+    t.first(rays_tensor, "ray", "rays")
+    t.also(hits_tensor, "hit", "hits")
+    out = t.given_or_new(out, "material", "out")
     invalid = 0
-    if n:
-        rays = WrapDeviceMemory(None, r.data_ptr(), n * 32, keepalive=r)
-        hits = WrapDeviceMemory(None, h.data_ptr(), n * 32, keepalive=h)
-        dst = WrapDeviceMemory(None, out.data_ptr(), n * 64, keepalive=out)
-        _, invalid = ResolveMaterials(tlas, rays, hits, n, scene_buffers, dst)
+    if t.begin():
+        _, invalid = ResolveMaterials(tlas, t.wrap(rays_tensor, "ray"), t.wrap(hits_tensor, "hit"), t.n, scene_buffers, t.wrap(out, "material"))
     return out, invalid
 
 
@@ -777,27 +862,22 @@ def LightHitsTorch(rays_t, materials_t, scene_buffer, light, want_shadow=True):
     Returns (lit, shadow): lit float32 (n, 4) (rgb, 0), shadow float32 (n, 8) -- the rays QueryRaysTorch(..., QUERY_ANY) takes --
     or None without want_shadow.  The library cannot see torch's stream, so the current stream is synchronised first; the call
     blocks."""
-    import torch
-    r, m = rays_t, materials_t
-    n = _cuda_tensor("LightHitsTorch", r, (torch.float32,), (None, 8), "rays")
-    _cuda_tensor("LightHitsTorch", m, (torch.float32,), (n, 16), "materials", r.device)
+    t = _TorchCall("LightHitsTorch")
+    t.first(rays_t, "ray", "rays")
+    t.also(materials_t, "material", "materials")
     if not isinstance(scene_buffer, Buffer):
         raise RadianceError("LightHitsTorch: scene_buffer must be a Buffer (the SceneProperties of descriptor slot 4)")
-    light = int(light)
-    if not 0 <= light < MAX_LIGHTS:
-        raise RadianceError("LightHitsTorch: light %d is not one of the %d lights of a SceneProperties (0 .. %d)" % (light, MAX_LIGHTS, MAX_LIGHTS - 1))
-    lit = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device) if want_shadow else None
-    torch.cuda.current_stream(r.device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-        LightHits(wrap(r, 32), wrap(m, 64), n, scene_buffer, light, wrap(lit, 16), wrap(shadow, 32))
+    light = _scene_light("LightHitsTorch", light)
+    lit, shadow = t.new("float4"), t.new("ray", want_shadow)
+    if t.begin():
+        LightHits(t.wrap(rays_t, "ray"), t.wrap(materials_t, "material"), t.n, scene_buffer, light, t.wrap(lit, "float4"), t.wrap(shadow, "ray"))
     return lit, shadow
 
 
 # ---- the next ray of a query's hits from material and surface records (rdx_scatter_hits) --------------------------------
 SCATTER_DTYPE = np.dtype([("nextFactor", "<f4", 3), ("slot", "<u4")])
 assert SCATTER_DTYPE.itemsize == C.sizeof(_lib.rdx_scatter) == 16
+_record("scatter", SCATTER_DTYPE, "float32")
 
 
 def ScatterHits(rays, materials, surfaces, keys, n, randoms=None, scatter=None, next=None, src=None, compact=False, rays_offset=0,
@@ -812,24 +892,16 @@ def ScatterHits(rays, materials, surfaces, keys, n, randoms=None, scatter=None, 
     With `src`, the survivors are packed into records 0 .. live - 1 (those of 64 consecutive input rays contiguous and in input
     order, the groups in no fixed order), src[k] = the ray's number, and records from `live` on are untouched; without, k = i
     and the record of a ray that does not survive is zeros.  Returns (scatter, next, src, live)."""
-    if not all(isinstance(b, Buffer) for b in (rays, materials, surfaces)):
-        raise RadianceError("ScatterHits: rays, materials and surfaces must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    for what, b in (("keys", keys), ("randoms", randoms)):
-        if b is not None and not isinstance(b, Buffer):
-            raise RadianceError("ScatterHits: %s must be a Buffer or None" % what)
-    if keys is None and randoms is None:
-        raise RadianceError("ScatterHits: neither keys nor randoms given: one of the two is required")
-    if keys is not None and randoms is not None:
-        raise RadianceError("ScatterHits: both keys and randoms given: only one of the two is allowed")
+    _buffers("ScatterHits", rays=rays, materials=materials, surfaces=surfaces)
+    hk, hr = _keys_or_randoms("ScatterHits", keys, randoms)
     n = int(n)
-    scatter = _out_buffer("ScatterHits", n, scatter, scatter_offset, SCATTER_DTYPE.itemsize, "scatter", False)
-    next = _out_buffer("ScatterHits", n, next, next_offset, RAY_DTYPE.itemsize, "next", False)
-    src = _out_buffer("ScatterHits", n, True if (src is None and compact) else src, src_offset, 4, "src", True, or_true=False)
+    scatter = _out_buffer("ScatterHits", n, scatter, scatter_offset, "scatter", "scatter", False)
+    next = _out_buffer("ScatterHits", n, next, next_offset, "ray", "next", False)
+    src = _out_buffer("ScatterHits", n, True if (src is None and compact) else src, src_offset, "src", "src", True, or_true=False)
     live = C.c_uint32(0)
-    h = lambda b: b.handle if b is not None else None
     _check(_lib.lib().rdx_scatter_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), surfaces.handle, int(surfaces_offset),
-                                       h(keys), int(keys_offset), h(randoms), int(randoms_offset), n, scatter.handle, int(scatter_offset),
-                                       next.handle, int(next_offset), h(src), int(src_offset), C.byref(live)))
+                                       hk, int(keys_offset), hr, int(randoms_offset), n, scatter.handle, int(scatter_offset),
+                                       next.handle, int(next_offset), _h(src), int(src_offset), C.byref(live)))
     return scatter, next, src, int(live.value)
 
 
@@ -840,25 +912,18 @@ def ScatterHitsTorch(rays_t, materials_t, surfaces_t, keys_t=None, randoms_t=Non
     Returns (scatter, next, src, live): scatter float32 (n, 4) (nextFactor; `.view(torch.int32)` shows slot in column 3), next
     float32 (live, 8) when compacting -- already sliced to the survivors -- else (n, 8), src int32 (live,) or None.  The library
     cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
-    import torch
-    r, m, s, k, u = rays_t, materials_t, surfaces_t, keys_t, randoms_t
-    n = _cuda_tensor("ScatterHitsTorch", r, (torch.float32,), (None, 8), "rays")
-    for what, t in (("materials", m), ("surfaces", s)):
-        _cuda_tensor("ScatterHitsTorch", t, (torch.float32,), (n, 16), what, r.device)
-    if (k is None) == (u is None):
-        raise RadianceError("ScatterHitsTorch: exactly one of keys and randoms must be given")
-    if k is not None:
-        _cuda_tensor("ScatterHitsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
-    if u is not None:
-        _cuda_tensor("ScatterHitsTorch", u, (torch.float32,), (n, 4), "randoms", r.device)
-    scatter = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    nxt = torch.empty((n, 8), dtype=torch.float32, device=r.device)
-    src = torch.empty((n,), dtype=torch.int32, device=r.device) if compact else None
-    torch.cuda.current_stream(r.device).synchronize()
+    t = _TorchCall("ScatterHitsTorch")
+    t.first(rays_t, "ray", "rays")
+    t.also(materials_t, "material", "materials")
+    t.also(surfaces_t, "surface", "surfaces")
+    t.keys_or_randoms(keys_t, randoms_t)
+    scatter = t.new("scatter")
+    nxt = t.new("ray")
+    src = t.new("src", compact)
     live = 0
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-        _, _, _, live = ScatterHits(wrap(r, 32), wrap(m, 64), wrap(s, 64), wrap(k, 16), n, wrap(u, 16), wrap(scatter, 16), wrap(nxt, 32), wrap(src, 4))
+    if t.begin():
+        _, _, _, live = ScatterHits(t.wrap(rays_t, "ray"), t.wrap(materials_t, "material"), t.wrap(surfaces_t, "surface"), t.wrap(keys_t, "key"), t.n,
+                                    t.wrap(randoms_t, "float4"), t.wrap(scatter, "scatter"), t.wrap(nxt, "ray"), t.wrap(src, "src"))
     if compact:
         nxt, src = nxt[:live], src[:live]
     return scatter, nxt, src, live
@@ -867,13 +932,8 @@ def ScatterHitsTorch(rays_t, materials_t, surfaces_t, keys_t=None, randoms_t=Non
 # ---- the two ends of a frame on device memory (rdx_generate_rays, rdx_accumulate) ---------------------------------------
 RAYGEN_SEED_DTYPE = np.dtype([("in", "<u4", 3), ("_0", "<u4")])
 assert RAYGEN_SEED_DTYPE.itemsize == C.sizeof(_lib.rdx_raygen_seed) == 16
+_record("seed", RAYGEN_SEED_DTYPE, "int32")
 ACCUMULATE_DEBUG = 1
-
-
-def _optional_buffer(who, buf, what):
-    if buf is not None and not isinstance(buf, Buffer):
-        raise RadianceError("%s: %s must be a Buffer or None" % (who, what))
-    return buf.handle if buf is not None else None
 
 
 def GenerateRays(camera, n, frame_id, total_samples, first_pixel=0, pixels=None, seeds=None, tmin=0.001, tmax=1000.0, rays=None, keys=True,
@@ -885,20 +945,13 @@ def GenerateRays(camera, n, frame_id, total_samples, first_pixel=0, pixels=None,
     the reference's raygen, or pcg3d of seeds[i] (`seeds`: a Buffer of RAYGEN_SEED_DTYPE).  Every ray has the bits of the frame
     path's generateRay; tmin / tmax are written as given.  rays: a Buffer, or None (created).  keys: a Buffer, True (created) or
     None / False (not wanted).  Nothing passes through the host.  Returns (rays, keys)."""
-    if not isinstance(camera, Buffer):
-        raise RadianceError("GenerateRays: camera must be a Buffer (CreateBuffer / WrapDeviceMemory)")
+    _buffers("GenerateRays", camera=camera)
     n = int(n)
-    if rays is None:
-        rays = CreateBuffer(None, max(int(rays_offset) + RAY_DTYPE.itemsize * n, 1))
-    elif not isinstance(rays, Buffer):
-        raise RadianceError("GenerateRays: rays must be a Buffer or None")
-    if keys is True:
-        keys = CreateBuffer(None, max(int(keys_offset) + SHADE_KEY_DTYPE.itemsize * n, 1))
-    elif keys is False:
-        keys = None
-    hp, hs, hk = (_optional_buffer("GenerateRays", b, w) for b, w in ((pixels, "pixels"), (seeds, "seeds"), (keys, "keys")))
+    rays = _out_buffer("GenerateRays", n, rays, rays_offset, "ray", "rays", False, flags=False)
+    hp, hs = _optional_buffer("GenerateRays", pixels, "pixels"), _optional_buffer("GenerateRays", seeds, "seeds")
+    keys = _out_buffer("GenerateRays", n, keys, keys_offset, "key", "keys", True, or_true=False)
     _check(_lib.lib().rdx_generate_rays(camera.handle, n, int(first_pixel), hp, int(pixels_offset), int(frame_id), int(total_samples), hs,
-                                        int(seeds_offset), float(tmin), float(tmax), rays.handle, int(rays_offset), hk, int(keys_offset)))
+                                        int(seeds_offset), float(tmin), float(tmax), rays.handle, int(rays_offset), _h(keys), int(keys_offset)))
     return rays, keys
 
 
@@ -908,23 +961,20 @@ def GenerateRaysTorch(camera, n_or_pixels, frame_id, total_samples, seeds=None):
     Returns (rays float32 (n, 8): origin, tmin = 0.001, direction, tmax = 1000 per row -- what QueryRaysTorch takes; keys int32
     (n, 4): frame_id, pixel, 0, 0 -- what ShadeHitsTorch takes at depth 0).  The library cannot see torch's stream, so the
     current stream is synchronised first; the call blocks."""
-    import torch
+    t = _TorchCall("GenerateRaysTorch")
     px = None
-    if isinstance(n_or_pixels, torch.Tensor):
+    if isinstance(n_or_pixels, t.torch.Tensor):
         px = n_or_pixels
-        n, device = _cuda_tensor("GenerateRaysTorch", px, (torch.int32,), (None,), "pixels"), px.device
-    elif isinstance(n_or_pixels, (int, np.integer)) and not isinstance(n_or_pixels, bool) and n_or_pixels >= 0:
-        n, device = int(n_or_pixels), torch.device("cuda", torch.cuda.current_device())
+        t.first(px, "pixel", "pixels")
+    elif _is_count(n_or_pixels):
+        t.n, t.device = int(n_or_pixels), t.torch.device("cuda", t.torch.cuda.current_device())
     else:
         raise RadianceError("GenerateRaysTorch: the second argument is a ray count or an int32 CUDA tensor of pixel numbers")
     if seeds is not None:
-        _cuda_tensor("GenerateRaysTorch", seeds, (torch.int32,), (n, 4), "seeds", device, owner="pixels")
-    rays = torch.empty((n, 8), dtype=torch.float32, device=device)
-    keys = torch.empty((n, 4), dtype=torch.int32, device=device)
-    torch.cuda.current_stream(device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-        GenerateRays(camera, n, frame_id, total_samples, 0, wrap(px, 4), wrap(seeds, 16), rays=wrap(rays, 32), keys=wrap(keys, 16))
+        t.also(seeds, "seed", "seeds", owner="pixels")
+    rays, keys = t.new("ray"), t.new("key")
+    if t.begin():
+        GenerateRays(camera, t.n, frame_id, total_samples, 0, t.wrap(px, "pixel"), t.wrap(seeds, "seed"), rays=t.wrap(rays, "ray"), keys=t.wrap(keys, "key"))
     return rays, keys
 
 
@@ -935,8 +985,7 @@ def Accumulate(colors, n, frame_id, scratch, image=None, first_pixel=0, pixels=N
     float32, w kept -- and image (RGBA8, optional) the tone-mapped mean of those pixels (debug: no ACES, no gamma).  One call is
     one frame_id; its pixels must be distinct (of two samples of one pixel one wins, unspecified which).  Returns `invalid`:
     the samples whose pixel number is not below min(scratch.size / 16, image.size / 4); they write nothing."""
-    if not isinstance(colors, Buffer) or not isinstance(scratch, Buffer):
-        raise RadianceError("Accumulate: colors and scratch must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    _buffers("Accumulate", colors=colors, scratch=scratch)
     hi, hp = _optional_buffer("Accumulate", image, "image"), _optional_buffer("Accumulate", pixels, "pixels")
     invalid = C.c_uint32(0)
     _check(_lib.lib().rdx_accumulate(colors.handle, int(colors_offset), int(n), int(first_pixel), hp, int(pixels_offset), int(frame_id),
@@ -949,33 +998,41 @@ def AccumulateTorch(colors, frame_id, scratch, image=None, pixels=None, debug=Fa
     int32 (n,) tensor; scratch / image: Buffers (e.g. a DeviceScene's rdImageScratch / rdImage), or contiguous tensors of shape
     (npix, 4), float32 / uint8, which are updated in place.  Returns `invalid`.  The library cannot see torch's stream, so the
     current stream is synchronised first; the call blocks."""
-    import torch
-    c = colors
-    n = _cuda_tensor("AccumulateTorch", c, (torch.float32,), (None, 4), "colors")
+    t = _TorchCall("AccumulateTorch")
+    torch = t.torch
+    t.first(colors, "float4", "colors")
     if pixels is not None:
-        _cuda_tensor("AccumulateTorch", pixels, (torch.int32,), (n,), "pixels", c.device, owner="colours")
+        t.also(pixels, "pixel", "pixels", owner="colours")
 
-    def frame(t, dtype, what):
-        if t is None or isinstance(t, Buffer):
-            return t
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == 4 and t.is_contiguous()
-                and t.device == c.device):
+    def frame(f, dtype, what):
+        if f is None or isinstance(f, Buffer):
+            return f
+        if not (isinstance(f, torch.Tensor) and f.is_cuda and f.dtype == dtype and f.dim() == 2 and f.shape[1] == 4 and f.is_contiguous()
+                and f.device == t.device):
             raise RadianceError("AccumulateTorch: %s must be a Buffer or a contiguous %s CUDA tensor of shape (npix, 4) on the colours' device"
                                 % (what, str(dtype).replace("torch.", "")))
-        return WrapDeviceMemory(None, t.data_ptr(), t.numel() * t.element_size(), keepalive=t) if t.numel() else None
+        return WrapDeviceMemory(None, f.data_ptr(), f.numel() * f.element_size(), keepalive=f) if f.numel() else None
     if scratch is None:
         raise RadianceError("AccumulateTorch: scratch must be a Buffer or a float32 CUDA tensor of shape (npix, 4)")
     bs, bi = frame(scratch, torch.float32, "scratch"), frame(image, torch.uint8, "image")
-    torch.cuda.current_stream(c.device).synchronize()
-    if not n:
+    if not t.begin():
         return 0
     if bs is None or (image is not None and bi is None):       # a frame of no pixels: every sample is outside it
-        return n
-    wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-    return Accumulate(wrap(c, 16), n, frame_id, bs, bi, 0, wrap(pixels, 4), debug)
+        return t.n
+    return Accumulate(t.wrap(colors, "float4"), t.n, frame_id, bs, bi, 0, t.wrap(pixels, "pixel"), debug)
 
 
 # ---- radiance along the caller's own rays (rdx_trace_paths) -------------------------------------------------------------
+def _path_arguments(who, n, max_depth, scene_buffers, **buffers):
+    """the preamble of the four path calls, in the order of its refusals: the Buffers (tlas, rays, keys and the call's own),
+    scene_buffers, n and max_depth -> the rdx_shading_buffers and int(n).  The path calls type-check n; the per-hit calls coerce it"""
+    _buffers(who, **buffers)
+    sb = _shading_struct(who, scene_buffers)
+    if not (_is_count(n) and _is_count(max_depth)):
+        raise RadianceError("%s: n and max_depth must be non-negative integers" % who)
+    return sb, int(n)
+
+
 def TracePaths(tlas, rays, keys, n, max_depth, scene_buffers, radiance=None, hits=None, rays_offset=0, keys_offset=0, radiance_offset=0,
                hits_offset=0):
     """Extension: the reference's raygen loop for `n` rays of the caller's own, on the frame path's stages.  Path i starts with the
@@ -987,25 +1044,12 @@ def TracePaths(tlas, rays, keys, n, max_depth, scene_buffers, radiance=None, hit
     hits: a Buffer, True (created) or None / False (not wanted): the RAY_HIT_DTYPE records of the first segment, as
     QueryRays(..., QUERY_CLOSEST) writes them.  Device buffers in and out; nothing passes through the host.  Returns `radiance`
     (the hit buffer is `hits` where the caller passed one; rd.TracePaths(..., hits=True) returns (radiance, hits))."""
-    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
-        raise RadianceError("TracePaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    sb = _shading_struct("TracePaths", scene_buffers)
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
-            or max_depth < 0:
-        raise RadianceError("TracePaths: n and max_depth must be non-negative integers")
-    n = int(n)
-    if radiance is None:
-        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
-    elif not isinstance(radiance, Buffer):
-        raise RadianceError("TracePaths: radiance must be a Buffer or None")
+    sb, n = _path_arguments("TracePaths", n, max_depth, scene_buffers, tlas=tlas, rays=rays, keys=keys)
+    radiance = _out_buffer("TracePaths", n, radiance, radiance_offset, "float4", "radiance", False, flags=False)
     made_hits = hits is True
-    if made_hits:
-        hits = CreateBuffer(None, max(int(hits_offset) + RAY_HIT_DTYPE.itemsize * n, 1))
-    elif hits is False:
-        hits = None
-    hh = _optional_buffer("TracePaths", hits, "hits")
+    hits = _out_buffer("TracePaths", n, hits, hits_offset, "hit", "hits", True, or_true=False)
     _check(_lib.lib().rdx_trace_paths(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), C.byref(sb),
-                                      radiance.handle, int(radiance_offset), hh, int(hits_offset)))
+                                      radiance.handle, int(radiance_offset), _h(hits), int(hits_offset)))
     return (radiance, hits) if made_hits else radiance
 
 
@@ -1014,26 +1058,19 @@ def TracePathsTorch(tlas, rays_t, keys_t, max_depth, scene_buffers, want_hits=Fa
     a contiguous int32 (n, 4) tensor (frameID, pixel, -, -): what GenerateRaysTorch returns, or rays of the caller's own.
     Returns radiance float32 (n, 4): rgb, 0 -- what AccumulateTorch takes -- and, with want_hits, (radiance, hits int32 (n, 8)).
     The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
-    import torch
-    r, k = rays_t, keys_t
-    n = _cuda_tensor("TracePathsTorch", r, (torch.float32,), (None, 8), "rays")
-    _cuda_tensor("TracePathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
-    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
-        raise RadianceError("TracePathsTorch: max_depth must be a non-negative integer")
-    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    hits = torch.empty((n, 8), dtype=torch.int32, device=r.device) if want_hits else None
-    torch.cuda.current_stream(r.device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-        TracePaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, scene_buffers, wrap(radiance, 16), wrap(hits, 32))
+    t = _TorchCall("TracePathsTorch")
+    t.first(rays_t, "ray", "rays")
+    t.also(keys_t, "key", "keys")
+    _count("TracePathsTorch", max_depth, "max_depth must be a non-negative integer")
+    radiance, hits = t.new("float4"), t.new("hit", want_hits)
+    if t.begin():
+        TracePaths(tlas, t.wrap(rays_t, "ray"), t.wrap(keys_t, "key"), t.n, max_depth, scene_buffers, t.wrap(radiance, "float4"), t.wrap(hits, "hit"))
     return (radiance, hits) if want_hits else radiance
 
 
 # ---- radiance along the caller's own rays, every light of the scene sampled (rdx_trace_paths_lights) ---------------------
 def _light_count(who, light_count):
-    if isinstance(light_count, bool) or not isinstance(light_count, (int, np.integer)) or not 0 <= light_count <= 5:
-        raise RadianceError("%s: light_count must be an integer from 0 to 5 (the lights of a SceneProperties)" % who)
-    return int(light_count)
+    return _count(who, light_count, "light_count must be an integer from 0 to 5 (the lights of a SceneProperties)", 5)
 
 
 def TraceLightPaths(tlas, rays, keys, n, max_depth, light_count, scene_buffers, radiance=None, rays_offset=0, keys_offset=0, radiance_offset=0):
@@ -1042,18 +1079,9 @@ def TraceLightPaths(tlas, rays, keys, n, max_depth, light_count, scene_buffers, 
     call, with its bits.  Rays and keys as for TracePaths.  The lights are read on the device by every call.  The call gathers
     checked: a hit that scene_buffers does not describe is a miss and is counted.  radiance: a Buffer, or None (created:
     radiance_offset + 16 n bytes).  Device buffers in and out.  Returns (radiance, invalid)."""
-    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
-        raise RadianceError("TraceLightPaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    sb = _shading_struct("TraceLightPaths", scene_buffers)
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
-            or max_depth < 0:
-        raise RadianceError("TraceLightPaths: n and max_depth must be non-negative integers")
+    sb, n = _path_arguments("TraceLightPaths", n, max_depth, scene_buffers, tlas=tlas, rays=rays, keys=keys)
     light_count = _light_count("TraceLightPaths", light_count)
-    n = int(n)
-    if radiance is None:
-        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
-    elif not isinstance(radiance, Buffer):
-        raise RadianceError("TraceLightPaths: radiance must be a Buffer or None")
+    radiance = _out_buffer("TraceLightPaths", n, radiance, radiance_offset, "float4", "radiance", False, flags=False)
     invalid = C.c_uint32(0)
     _check(_lib.lib().rdx_trace_paths_lights(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), light_count,
                                              C.byref(sb), radiance.handle, int(radiance_offset), C.byref(invalid)))
@@ -1064,18 +1092,14 @@ def TraceLightPathsTorch(tlas, rays_t, keys_t, max_depth, light_count, scene_buf
     """Extension: TraceLightPaths on CUDA tensors -- rays a contiguous float32 (n, 8) tensor, keys a contiguous int32 (n, 4) tensor, as
     for TracePathsTorch.  Returns radiance float32 (n, 4): rgb, 0 -- what AccumulateTorch takes.  The library cannot see torch's
     stream, so the current stream is synchronised first; the call blocks."""
-    import torch
-    r, k = rays_t, keys_t
-    n = _cuda_tensor("TraceLightPathsTorch", r, (torch.float32,), (None, 8), "rays")
-    _cuda_tensor("TraceLightPathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
-    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
-        raise RadianceError("TraceLightPathsTorch: max_depth must be a non-negative integer")
+    t = _TorchCall("TraceLightPathsTorch")
+    t.first(rays_t, "ray", "rays")
+    t.also(keys_t, "key", "keys")
+    _count("TraceLightPathsTorch", max_depth, "max_depth must be a non-negative integer")
     light_count = _light_count("TraceLightPathsTorch", light_count)
-    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    torch.cuda.current_stream(r.device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t)
-        TraceLightPaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, light_count, scene_buffers, wrap(radiance, 16))
+    radiance = t.new("float4")
+    if t.begin():
+        TraceLightPaths(tlas, t.wrap(rays_t, "ray"), t.wrap(keys_t, "key"), t.n, max_depth, light_count, scene_buffers, t.wrap(radiance, "float4"))
     return radiance
 
 
@@ -1083,6 +1107,7 @@ def TraceLightPathsTorch(tlas, rays_t, keys_t, max_depth, light_count, scene_buf
 PUNCTUAL_LIGHT_DTYPE = np.dtype([("position", "<f4", 3), ("type", "<u4"), ("direction", "<f4", 3), ("range", "<f4"), ("color", "<f4", 3),
                                  ("_0", "<f4"), ("coneScale", "<f4"), ("coneOffset", "<f4"), ("_1", "<f4"), ("_2", "<f4")])
 assert PUNCTUAL_LIGHT_DTYPE.itemsize == C.sizeof(_lib.rdx_punctual_light) == 64
+_record("light", PUNCTUAL_LIGHT_DTYPE, "float32")
 LIGHT_DIRECTIONAL, LIGHT_POINT, LIGHT_SPOT = 0, 1, 2
 MAX_PATH_LIGHTS = 16     # the records of a table one TracePunctualPaths call samples
 
@@ -1097,16 +1122,12 @@ def SpotCone(inner_rad, outer_rad):
     return np.float32(scale), np.float32(np.float32(-co) * scale)
 
 
-def _light_index(who, index, what="index"):
-    if isinstance(index, bool) or not isinstance(index, (int, np.integer)) or index < 0:
-        raise RadianceError("%s: %s must be a non-negative integer" % (who, what))
-    return int(index)
+def _light_index(who, index):
+    return _count(who, index, "index must be a non-negative integer")
 
 
 def _path_light_count(who, light_count):
-    if isinstance(light_count, bool) or not isinstance(light_count, (int, np.integer)) or not 0 <= light_count <= MAX_PATH_LIGHTS:
-        raise RadianceError("%s: light_count must be an integer from 0 to %d (MAX_PATH_LIGHTS)" % (who, MAX_PATH_LIGHTS))
-    return int(light_count)
+    return _count(who, light_count, "light_count must be an integer from 0 to %d (MAX_PATH_LIGHTS)" % MAX_PATH_LIGHTS, MAX_PATH_LIGHTS)
 
 
 def PunctualLightHits(rays, materials, n, lights, index, lit=None, shadow=True, rays_offset=0, materials_offset=0, lights_offset=0, lit_offset=0,
@@ -1116,46 +1137,37 @@ def PunctualLightHits(rays, materials, n, lights, index, lit=None, shadow=True, 
     ends at the light (tmax = the distance); a record that is dark at a hit -- out of range, outside the cone, an unknown type --
     gives zeros in `lit` and `shadow`, as does a record whose `hit` is not 1.  lit / shadow as for LightHits.  Returns
     (lit, shadow)."""
-    if not all(isinstance(b, Buffer) for b in (rays, materials, lights)):
-        raise RadianceError("PunctualLightHits: rays, materials and lights must be Buffers (CreateBuffer / WrapDeviceMemory)")
+    _buffers("PunctualLightHits", rays=rays, materials=materials, lights=lights)
     n, index = int(n), _light_index("PunctualLightHits", index)
-    if lit is None:
-        lit = CreateBuffer(None, max(int(lit_offset) + 16 * n, 1))
-    elif not isinstance(lit, Buffer):
-        raise RadianceError("PunctualLightHits: lit must be a Buffer or None")
-    shadow = _out_buffer("PunctualLightHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
+    lit, shadow = _lit_and_shadow("PunctualLightHits", n, lit, lit_offset, shadow, shadow_offset)
     _check(_lib.lib().rdx_punctual_light_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), n, lights.handle,
-                                              int(lights_offset) + PUNCTUAL_LIGHT_DTYPE.itemsize * index, lit.handle, int(lit_offset),
-                                              shadow.handle if shadow is not None else None, int(shadow_offset)))
+                                              int(lights_offset) + _RECORDS["light"][0] * index, lit.handle, int(lit_offset), _h(shadow),
+                                              int(shadow_offset)))
     return lit, shadow
 
 
-def _light_table_tensor(who, lights_t):
-    """an (L, 16) float32 CUDA tensor of PUNCTUAL_LIGHT_DTYPE records -> L.  The table is looked at before the rays, so a refusal
-    of a bad table names it"""
-    import torch
-    return _cuda_tensor(who, lights_t, (torch.float32,), (None, 16), "lights")
+def _light_hits_tensors(who, rays_t, materials_t, table, kind, what):
+    """the preamble of the two per-hit calls on a light table of tensors: the table -- looked at before the rays, so a refusal of a bad
+    table names it --, the rays on its device, the materials -> the _TorchCall and the records of the table"""
+    t = _TorchCall(who)
+    count = _cuda_tensor(who, table, kind, what)
+    t.first(rays_t, "ray", "rays", table.device, what)
+    t.also(materials_t, "material", "materials")
+    return t, count
 
 
 def PunctualLightHitsTorch(rays_t, materials_t, lights_t, index, want_shadow=True):
     """Extension: PunctualLightHits on CUDA tensors -- rays and materials as for LightHitsTorch, lights a contiguous float32 (L, 16)
     tensor of PUNCTUAL_LIGHT_DTYPE records (`.view(torch.int32)` shows `type` in column 3), index < L.  Returns (lit, shadow) as
     LightHitsTorch.  The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
-    import torch
-    r, m = rays_t, materials_t
-    count = _light_table_tensor("PunctualLightHitsTorch", lights_t)
-    n = _cuda_tensor("PunctualLightHitsTorch", r, (torch.float32,), (None, 8), "rays", lights_t.device, "lights")
-    _cuda_tensor("PunctualLightHitsTorch", m, (torch.float32,), (n, 16), "materials", r.device)
+    t, count = _light_hits_tensors("PunctualLightHitsTorch", rays_t, materials_t, lights_t, "light", "lights")
     index = _light_index("PunctualLightHitsTorch", index)
     if index >= count:
         raise RadianceError("PunctualLightHitsTorch: index %d is not one of the %d records of the table" % (index, count))
-    lit = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device) if want_shadow else None
-    torch.cuda.current_stream(r.device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-        table = WrapDeviceMemory(None, lights_t.data_ptr(), count * 64, keepalive=lights_t)
-        PunctualLightHits(wrap(r, 32), wrap(m, 64), n, table, index, wrap(lit, 16), wrap(shadow, 32))
+    lit, shadow = t.new("float4"), t.new("ray", want_shadow)
+    if t.begin():
+        table = t.wrap(lights_t, "light", count)
+        PunctualLightHits(t.wrap(rays_t, "ray"), t.wrap(materials_t, "material"), t.n, table, index, t.wrap(lit, "float4"), t.wrap(shadow, "ray"))
     return lit, shadow
 
 
@@ -1166,18 +1178,9 @@ def TracePunctualPaths(tlas, rays, keys, n, max_depth, lights, light_count, scen
     directional lights: the path tracer over QueryRays / ResolveHits / ResolveMaterials / PunctualLightHits / ScatterHits in one
     call, with its bits.  The table is read on the device by every call; scene_buffers.scene is still required, its lights are not
     read.  Everything else as for TraceLightPaths.  Returns (radiance, invalid)."""
-    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys, lights)):
-        raise RadianceError("TracePunctualPaths: tlas, rays, keys and lights must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    sb = _shading_struct("TracePunctualPaths", scene_buffers)
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
-            or max_depth < 0:
-        raise RadianceError("TracePunctualPaths: n and max_depth must be non-negative integers")
+    sb, n = _path_arguments("TracePunctualPaths", n, max_depth, scene_buffers, tlas=tlas, rays=rays, keys=keys, lights=lights)
     light_count = _path_light_count("TracePunctualPaths", light_count)
-    n = int(n)
-    if radiance is None:
-        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
-    elif not isinstance(radiance, Buffer):
-        raise RadianceError("TracePunctualPaths: radiance must be a Buffer or None")
+    radiance = _out_buffer("TracePunctualPaths", n, radiance, radiance_offset, "float4", "radiance", False, flags=False)
     invalid = C.c_uint32(0)
     _check(_lib.lib().rdx_trace_paths_punctual(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), lights.handle,
                                                int(lights_offset), light_count, C.byref(sb), radiance.handle, int(radiance_offset), C.byref(invalid)))
@@ -1188,21 +1191,18 @@ def TracePunctualPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, scene_buf
     """Extension: TracePunctualPaths on CUDA tensors -- rays and keys as for TraceLightPathsTorch, lights a contiguous float32
     (L, 16) tensor of PUNCTUAL_LIGHT_DTYPE records, L <= MAX_PATH_LIGHTS: every record is sampled.  Returns radiance float32
     (n, 4): rgb, 0.  The library cannot see torch's stream, so the current stream is synchronised first; the call blocks."""
-    import torch
-    r, k = rays_t, keys_t
-    count = _path_light_count("TracePunctualPathsTorch", _light_table_tensor("TracePunctualPathsTorch", lights_t))
-    n = _cuda_tensor("TracePunctualPathsTorch", r, (torch.float32,), (None, 8), "rays", lights_t.device, "lights")
-    _cuda_tensor("TracePunctualPathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
-    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
-        raise RadianceError("TracePunctualPathsTorch: max_depth must be a non-negative integer")
-    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    torch.cuda.current_stream(r.device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t)
+    # the table is looked at before the rays, so a refusal of a bad table names it
+    count = _path_light_count("TracePunctualPathsTorch", _cuda_tensor("TracePunctualPathsTorch", lights_t, "light", "lights"))
+    t = _TorchCall("TracePunctualPathsTorch")
+    t.first(rays_t, "ray", "rays", lights_t.device, "lights")
+    t.also(keys_t, "key", "keys")
+    _count("TracePunctualPathsTorch", max_depth, "max_depth must be a non-negative integer")
+    radiance = t.new("float4")
+    if t.begin():
         # an empty table has no address to wrap: one record of zeros stands in, and none of it is read
-        table_t = lights_t if count else torch.zeros((1, 16), dtype=torch.float32, device=r.device)
-        table = WrapDeviceMemory(None, table_t.data_ptr(), max(count, 1) * 64, keepalive=table_t)
-        TracePunctualPaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, table, count, scene_buffers, wrap(radiance, 16))
+        table_t = lights_t if count else t.torch.zeros((1, 16), dtype=t.torch.float32, device=t.device)
+        table = t.wrap(table_t, "light", max(count, 1))
+        TracePunctualPaths(tlas, t.wrap(rays_t, "ray"), t.wrap(keys_t, "key"), t.n, max_depth, table, count, scene_buffers, t.wrap(radiance, "float4"))
     return radiance
 
 
@@ -1210,6 +1210,7 @@ def TracePunctualPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, scene_buf
 AREA_LIGHT_DTYPE = np.dtype([("corner", "<f4", 3), ("type", "<u4"), ("edgeU", "<f4", 3), ("flags", "<u4"), ("edgeV", "<f4", 3), ("_0", "<f4"),
                              ("radiance", "<f4", 3), ("_1", "<f4")])
 assert AREA_LIGHT_DTYPE.itemsize == C.sizeof(_lib.rdx_area_light) == 64
+_record("area light", AREA_LIGHT_DTYPE, "float32")
 AREA_QUAD, AREA_TRIANGLE = 0, 1
 AREA_TWO_SIDED = 1       # flags bit 0
 MAX_AREA_STREAM = 0xfffe
@@ -1235,11 +1236,7 @@ def TriangleLight(corner, edge_u, edge_v, radiance, two_sided=False):
 
 
 def _area_stream(who, stream, index):
-    if stream is None:
-        stream = index
-    if isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= stream <= MAX_AREA_STREAM:
-        raise RadianceError("%s: stream must be an integer from 0 to %d" % (who, MAX_AREA_STREAM))
-    return int(stream)
+    return _count(who, index if stream is None else stream, "stream must be an integer from 0 to %d" % MAX_AREA_STREAM, MAX_AREA_STREAM)
 
 
 def AreaLightHits(rays, materials, n, lights, index, keys=None, randoms=None, stream=None, lit=None, shadow=True, rays_offset=0, materials_offset=0,
@@ -1251,26 +1248,14 @@ def AreaLightHits(rays, materials, n, lights, index, keys=None, randoms=None, st
     The shadow ray stops at 0.999 of the distance to the sampled point; a record that is dark at a hit -- the back face of a
     one-sided emitter, a degenerate emitter, an unknown type -- gives zeros in `lit` and `shadow`, as does a record whose `hit` is
     not 1.  lit / shadow as for LightHits.  Returns (lit, shadow)."""
-    if not all(isinstance(b, Buffer) for b in (rays, materials, lights)):
-        raise RadianceError("AreaLightHits: rays, materials and lights must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    for what, b in (("keys", keys), ("randoms", randoms)):
-        if b is not None and not isinstance(b, Buffer):
-            raise RadianceError("AreaLightHits: %s must be a Buffer or None" % what)
-    if keys is None and randoms is None:
-        raise RadianceError("AreaLightHits: neither keys nor randoms given: one of the two is required")
-    if keys is not None and randoms is not None:
-        raise RadianceError("AreaLightHits: both keys and randoms given: only one of the two is allowed")
+    _buffers("AreaLightHits", rays=rays, materials=materials, lights=lights)
+    hk, hr = _keys_or_randoms("AreaLightHits", keys, randoms)
     n, index = int(n), _light_index("AreaLightHits", index)
     stream = _area_stream("AreaLightHits", stream, index if keys is not None else 0)
-    if lit is None:
-        lit = CreateBuffer(None, max(int(lit_offset) + 16 * n, 1))
-    elif not isinstance(lit, Buffer):
-        raise RadianceError("AreaLightHits: lit must be a Buffer or None")
-    shadow = _out_buffer("AreaLightHits", n, shadow, shadow_offset, RAY_DTYPE.itemsize, "shadow", True)
-    h = lambda b: b.handle if b is not None else None
+    lit, shadow = _lit_and_shadow("AreaLightHits", n, lit, lit_offset, shadow, shadow_offset)
     _check(_lib.lib().rdx_area_light_hits(rays.handle, int(rays_offset), materials.handle, int(materials_offset), n, lights.handle,
-                                          int(lights_offset) + AREA_LIGHT_DTYPE.itemsize * index, h(keys), int(keys_offset), stream, h(randoms),
-                                          int(randoms_offset), lit.handle, int(lit_offset), h(shadow), int(shadow_offset)))
+                                          int(lights_offset) + _RECORDS["area light"][0] * index, hk, int(keys_offset), stream, hr,
+                                          int(randoms_offset), lit.handle, int(lit_offset), _h(shadow), int(shadow_offset)))
     return lit, shadow
 
 
@@ -1280,35 +1265,23 @@ def AreaLightHitsTorch(rays_t, materials_t, area_t, index, keys=None, randoms=No
     exactly one of keys, a contiguous int32 (n, 4) tensor (frameID, pixel, depth, 0), and randoms, a contiguous float32 (n, 4)
     tensor (x, y used).  Returns (lit, shadow) as LightHitsTorch.  The library cannot see torch's stream, so the current stream is
     synchronised first; the call blocks."""
-    import torch
-    r, m = rays_t, materials_t
-    count = _cuda_tensor("AreaLightHitsTorch", area_t, (torch.float32,), (None, 16), "area lights")
-    n = _cuda_tensor("AreaLightHitsTorch", r, (torch.float32,), (None, 8), "rays", area_t.device, "area lights")
-    _cuda_tensor("AreaLightHitsTorch", m, (torch.float32,), (n, 16), "materials", r.device)
-    if (keys is None) == (randoms is None):
-        raise RadianceError("AreaLightHitsTorch: exactly one of keys and randoms must be given")
-    if keys is not None:
-        _cuda_tensor("AreaLightHitsTorch", keys, (torch.int32,), (n, 4), "keys", r.device)
-    if randoms is not None:
-        _cuda_tensor("AreaLightHitsTorch", randoms, (torch.float32,), (n, 4), "randoms", r.device)
+    t, count = _light_hits_tensors("AreaLightHitsTorch", rays_t, materials_t, area_t, "area light", "area lights")
+    t.keys_or_randoms(keys, randoms)
     index = _light_index("AreaLightHitsTorch", index)
     if index >= count:
         raise RadianceError("AreaLightHitsTorch: index %d is not one of the %d records of the table" % (index, count))
     stream = _area_stream("AreaLightHitsTorch", stream, index if keys is not None else 0)
-    lit = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    shadow = torch.empty((n, 8), dtype=torch.float32, device=r.device) if want_shadow else None
-    torch.cuda.current_stream(r.device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t) if t is not None else None
-        table = WrapDeviceMemory(None, area_t.data_ptr(), count * 64, keepalive=area_t)
-        AreaLightHits(wrap(r, 32), wrap(m, 64), n, table, index, wrap(keys, 16), wrap(randoms, 16), stream, wrap(lit, 16), wrap(shadow, 32))
+    lit, shadow = t.new("float4"), t.new("ray", want_shadow)
+    if t.begin():
+        table = t.wrap(area_t, "area light", count)
+        AreaLightHits(t.wrap(rays_t, "ray"), t.wrap(materials_t, "material"), t.n, table, index, t.wrap(keys, "key"), t.wrap(randoms, "float4"), stream,
+                      t.wrap(lit, "float4"), t.wrap(shadow, "ray"))
     return lit, shadow
 
 
 def _area_path_counts(who, light_count, area_count):
     for what, c in (("light_count", light_count), ("area_count", area_count)):
-        if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or c < 0:
-            raise RadianceError("%s: %s must be a non-negative integer" % (who, what))
+        _count(who, c, "%s must be a non-negative integer" % what)
     if light_count + area_count > MAX_PATH_LIGHTS:
         raise RadianceError("%s: light_count + area_count must not exceed %d (MAX_PATH_LIGHTS)" % (who, MAX_PATH_LIGHTS))
     return int(light_count), int(area_count)
@@ -1322,25 +1295,15 @@ def TraceAreaPaths(tlas, rays, keys, n, max_depth, lights, light_count, area, ar
     PunctualLightHits / AreaLightHits / ScatterHits in one call, with its bits.  light_count + area_count <= MAX_PATH_LIGHTS; a
     table whose count is 0 may be None.  With area_count 0 the result has the bits of TracePunctualPaths.  The emitters are not
     geometry: no ray sees them.  Everything else as for TracePunctualPaths.  Returns (radiance, invalid)."""
-    if not all(isinstance(b, Buffer) for b in (tlas, rays, keys)):
-        raise RadianceError("TraceAreaPaths: tlas, rays and keys must be Buffers (CreateBuffer / WrapDeviceMemory)")
-    sb = _shading_struct("TraceAreaPaths", scene_buffers)
-    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0 or isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) \
-            or max_depth < 0:
-        raise RadianceError("TraceAreaPaths: n and max_depth must be non-negative integers")
+    sb, n = _path_arguments("TraceAreaPaths", n, max_depth, scene_buffers, tlas=tlas, rays=rays, keys=keys)
     light_count, area_count = _area_path_counts("TraceAreaPaths", light_count, area_count)
     for what, b, c in (("lights", lights, light_count), ("area", area, area_count)):
         if not (isinstance(b, Buffer) or (b is None and c == 0)):
             raise RadianceError("TraceAreaPaths: %s must be a Buffer (or None with a count of 0)" % what)
-    n = int(n)
-    if radiance is None:
-        radiance = CreateBuffer(None, max(int(radiance_offset) + 16 * n, 1))
-    elif not isinstance(radiance, Buffer):
-        raise RadianceError("TraceAreaPaths: radiance must be a Buffer or None")
+    radiance = _out_buffer("TraceAreaPaths", n, radiance, radiance_offset, "float4", "radiance", False, flags=False)
     invalid = C.c_uint32(0)
-    h = lambda b: b.handle if b is not None else None
-    _check(_lib.lib().rdx_trace_paths_area(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), h(lights),
-                                           int(lights_offset), light_count, h(area), int(area_offset), area_count, C.byref(sb), radiance.handle,
+    _check(_lib.lib().rdx_trace_paths_area(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), _h(lights),
+                                           int(lights_offset), light_count, _h(area), int(area_offset), area_count, C.byref(sb), radiance.handle,
                                            int(radiance_offset), C.byref(invalid)))
     return radiance, int(invalid.value)
 
@@ -1350,24 +1313,21 @@ def TraceAreaPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, area_t, scene
     tensor of PUNCTUAL_LIGHT_DTYPE records or None, area_t a contiguous float32 (A, 16) tensor of AREA_LIGHT_DTYPE records or None,
     L + A <= MAX_PATH_LIGHTS: every record is sampled.  Returns radiance float32 (n, 4): rgb, 0.  The library cannot see torch's
     stream, so the current stream is synchronised first; the call blocks."""
-    import torch
-    r, k = rays_t, keys_t
-    L = _light_table_tensor("TraceAreaPathsTorch", lights_t) if lights_t is not None else 0
-    A = _cuda_tensor("TraceAreaPathsTorch", area_t, (torch.float32,), (None, 16), "area lights") if area_t is not None else 0
+    # the tables are looked at before the rays, so a refusal of a bad table names it
+    L = _cuda_tensor("TraceAreaPathsTorch", lights_t, "light", "lights") if lights_t is not None else 0
+    A = _cuda_tensor("TraceAreaPathsTorch", area_t, "area light", "area lights") if area_t is not None else 0
     L, A = _area_path_counts("TraceAreaPathsTorch", L, A)
-    n = _cuda_tensor("TraceAreaPathsTorch", r, (torch.float32,), (None, 8), "rays")
-    for what, t in (("lights", lights_t), ("area lights", area_t)):
-        if t is not None and t.device != r.device:
+    t = _TorchCall("TraceAreaPathsTorch")
+    t.first(rays_t, "ray", "rays")
+    for what, table in (("lights", lights_t), ("area lights", area_t)):
+        if table is not None and table.device != t.device:
             raise RadianceError("TraceAreaPathsTorch: %s must be on the rays' device" % what)
-    _cuda_tensor("TraceAreaPathsTorch", k, (torch.int32,), (n, 4), "keys", r.device)
-    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or max_depth < 0:
-        raise RadianceError("TraceAreaPathsTorch: max_depth must be a non-negative integer")
-    radiance = torch.empty((n, 4), dtype=torch.float32, device=r.device)
-    torch.cuda.current_stream(r.device).synchronize()
-    if n:
-        wrap = lambda t, rec: WrapDeviceMemory(None, t.data_ptr(), n * rec, keepalive=t)
-        table = lambda t, c: WrapDeviceMemory(None, t.data_ptr(), c * 64, keepalive=t) if c else None      # an empty table has no address to wrap
-        TraceAreaPaths(tlas, wrap(r, 32), wrap(k, 16), n, max_depth, table(lights_t, L), L, table(area_t, A), A, scene_buffers, wrap(radiance, 16))
+    t.also(keys_t, "key", "keys")
+    _count("TraceAreaPathsTorch", max_depth, "max_depth must be a non-negative integer")
+    radiance = t.new("float4")
+    if t.begin():
+        TraceAreaPaths(tlas, t.wrap(rays_t, "ray"), t.wrap(keys_t, "key"), t.n, max_depth, t.wrap(lights_t, "light", L) if L else None, L,
+                       t.wrap(area_t, "area light", A) if A else None, A, scene_buffers, t.wrap(radiance, "float4"))      # an empty table has no address to wrap
     return radiance
 
 
