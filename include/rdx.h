@@ -789,6 +789,10 @@ int         rdx_material_batch(const rdx_hit* hits, const float* ray_dirs_xyz, c
 int         rdx_generate_batch(const uint32_t* pixels, const uint32_t* rand_in3, uint32_t n,
                                float* origins_xyz, float* dirs_xyz);
 int         rdx_pcg3d_batch(const uint32_t* in3, float* out3, uint32_t n);
+/* the frame path's per-bounce ray sort on `capacity` device keys of 15 bits (uint16), the first `live` of them alive: perm[0 .. live)
+ * = their numbers ordered by the key reduced to key_bits (12, 13 or 14) bits; the order inside a reduced key is unspecified */
+int         rdx_debug_sort_keys(rdx_buffer keys, size_t keys_offset, uint32_t live, uint32_t capacity, uint32_t key_bits,
+                                rdx_buffer perm, size_t perm_offset);
 
 /* Scalars of the traversal layout derived from a TLAS blob (csrc/accel_layout.h): what the kernels' LDS is sized from and
  * what picks the engine.  Flags are 0 / 1. */

@@ -216,6 +216,7 @@ SIGNATURES = {
     "rdx_material_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "rdx_generate_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "rdx_pcg3d_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rdx_debug_sort_keys": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
     "rdx_debug_accel_layout": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(rdx_accel_scalars), C.POINTER(C.c_void_p),
                                          C.POINTER(C.c_size_t)]),
     "rdx_debug_accel_layout_update": (C.c_int, [C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_uint32, C.c_int, C.c_int,

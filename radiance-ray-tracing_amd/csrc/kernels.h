@@ -93,14 +93,18 @@ struct PathStreams {
 
 // per-bounce ray sort (option "sort"): counting sort of the m survivors of shade(d) by (origin cell -- the high bits of the Morton
 // code of the origin in a 16^3 grid over the scene box -- then direction octant) into ONE permutation that serves the shadow
-// queries and the next bounce's rays alike (same origin).  No device-scope atomics: per-block LDS histograms, one scan, LDS
-// positions (kernels.hip k_sortg_*).
-constexpr uint32_t SORT_TILE = 4096u;                // counters per scan tile
+// queries and the next bounce's rays alike (same origin).  Two launches: per-block LDS histograms whose counts become offsets
+// inside each key through one returning device atomic per (key, block), then LDS positions (kernels.hip k_sortg_*).
 struct SortBox { float lo[3]; float inv[3]; };      // cell = (p - lo) * inv, clamped to 0..15
-// perm: nMax words; H: ray_sort_tiles_words() words of scratch
+// perm: nMax words; bits: key bits (ray_sort_key_bits()); H: ray_sort_tiles_words() words of scratch, owned by ONE stream's sorts:
+//   [2][16384] total[key], double-buffered: sort number `phase` counts into copy phase & 1 and zeroes the other one for its
+//              successor; the launch flips `phase`.  Whoever allocates H zeroes these ray_sort_zeroed_words() words once
+//   [blocks][16384] offset of block b inside key k (written for the keys the block met, read by the same block)
 void launch_ray_sort_tiles(hipStream_t st, const PathStreams& ps, const uint32_t* mPtr, uint32_t nMax, const SortBox& box, uint32_t* H,
-                           uint32_t* perm, bool largeScene = false);
+                           uint32_t& phase, uint32_t* perm, uint32_t bits);
 uint32_t ray_sort_tiles_words();
+uint32_t ray_sort_zeroed_words();
+uint32_t ray_sort_key_bits(bool largeScene);         // 13, or 14 for the scenes whose records live in HBM
 
 // LDS words one wave of the cooperative / pool engine needs for the given stack needs (traverse_coop.h, traverse_pool.h)
 uint32_t coop_lds_words(uint32_t coopNeed);

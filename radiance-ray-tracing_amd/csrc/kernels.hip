@@ -622,48 +622,30 @@ __device__ __forceinline__ uint32_t sort_cell(const SortBox& B, float x, float y
     const uint32_t cz = (uint32_t)fminf(fmaxf((z - B.lo[2]) * B.inv[2], 0.0f), 15.0f);
     return spread4(cx) | (spread4(cy) << 1) | (spread4(cz) << 2);            // 12-bit Morton code
 }
-// exclusive scan inside tiles of SORT_TILE counters (256 threads x 16 consecutive counters), tile totals to sums[tile]
-__global__ void __launch_bounds__(256)
-k_sort_scan_tiles(uint32_t* __restrict__ bins, uint32_t* __restrict__ sums)
-{
-    static_assert(SORT_TILE == 256u * 16u, "tile shape");
-    __shared__ uint32_t part[256];
-    uint4* p = reinterpret_cast<uint4*>(bins + (size_t)blockIdx.x * SORT_TILE + threadIdx.x * 16u);
-    uint4 v[4];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[k] = p[k]; sum += v[k].x + v[k].y + v[k].z + v[k].w; }
-    const uint32_t t = threadIdx.x;
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 256u; off <<= 1) {
-        const uint32_t x = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint4 o;
-        o.x = run; run += v[k].x; o.y = run; run += v[k].y; o.z = run; run += v[k].z; o.w = run; run += v[k].w;
-        p[k] = o;
-    }
-    if (t == 255u) sums[blockIdx.x] = part[255];
-}
-// Per-bounce ray sort (option "sort" 1), without device-scope atomics.  Counting sort over SORT_GBINS = 4096 keys (the 9 high bits of
-// the origin's Morton cell, direction octant; 10 / 11 / 12 key bits: 55.2 / 54.6 / 54.3 ms on the 10.4 M-triangle scene) in the
-// classic three steps of a radix pass: (A) every block histograms ITS
-// tiles of 4096 consecutive paths in LDS and writes its column of the (key, block) count matrix, (B) one exclusive scan of the
-// matrix in key-major order, (C) every block reloads its scanned column into LDS and hands out positions with LDS atomics
-// while it walks its tiles again.  Two passes over the rays, 4 MB of counters, no global atomic.  (A tile-LOCAL
+// Per-bounce ray sort (option "sort" 1).  Counting sort over at most SORT_GBINS = 16384 keys (the high bits of the origin's Morton
+// cell, direction octant; 10 / 11 / 12 key bits: 55.2 / 54.6 / 54.3 ms on the 10.4 M-triangle scene) in two launches that each stream
+// the 2-byte keys once:
+//   (A) k_sortg_hist: block b counts the keys of ITS slice of the paths (m / blocks consecutive paths, at least SORT_GTILE) in LDS, then
+//       reserves, for every key it met, its count in total[key] with ONE returning device atomic -- what comes back is the block's
+//       offset inside the key, stored in row b of the (block, key) offset table (entries of keys the block did not meet stay unwritten
+//       and are never used);
+//   (B) k_sortg_scatter: every block builds the exclusive scan of total[] itself in LDS (at most 16384 words out of L2: cheaper than a
+//       launch), adds its row of offsets, and hands out positions with LDS atomics while it walks its slice again.
+// No block waits for another: the atomics of (A) return at once in whatever order the blocks arrive, and that order only decides
+// the order of the blocks inside a key, which no result depends on.  total[] exists twice per group: the scatter of one sort zeroes
+// the copy the NEXT sort counts into, and the first is zeroed at allocation, so no memset runs per bounce.  Blocks of 1024 threads
+// share one 64 KB LDS histogram -- two fit a CU's 160 KB, but one per CU measures faster (SORT_GCOLS_LOG2) -- and each lane loads 8
+// keys per 16-byte load, two loads in flight before its LDS atomics start.  (Before: 256 blocks of 256 threads, one 2-byte load per lane at a time, a 4 MB
+// (key, block) count matrix scanned by two more launches in between -- 0.23 TB/s in the histogram pass.)  (A tile-LOCAL
 // sort -- 0.4 ms per frame -- was tried first and gains nothing: what the sort buys is that the ~400 k rays in flight on the
 // chip at any moment come from one region of the scene and meet in L2, not coherence inside a wave.)
 #ifndef SORT_GBITS
 #define SORT_GBITS 13u                 // key bits: 3 of the octant + the high bits - 3 bits of the 12-bit Morton cell (12 / 13 / 14: 22.15 / 22.10 / 22.31 ms Sponza-class, 64.1 / 63.1 / 62.6 ms on the 10.4 M-triangle scene)
 #endif
 #ifndef SORT_GCOLS_LOG2
-#define SORT_GCOLS_LOG2 8u             // columns of the (key, block) count matrix = blocks of the two passes (1024 / 512 / 256 / 128: 22.38 / 22.13 / 22.06 / 22.48 ms, Sponza-class)
+#define SORT_GCOLS_LOG2 8u             // rows of the (block, key) offset table = blocks of the two passes, at most: one per CU.  512, two per CU: 20.97 against 20.94 ms
+                                       // Sponza-class, k_sortg_hist 17.3 against 14.7 us per launch -- twice the rows, more (key, block) atomics at bounce 0 -- the
+                                       // scatter the same (with the 256-thread blocks and the count matrix before: 1024 / 512 / 256 / 128: 22.38 / 22.13 / 22.06 / 22.48 ms)
 #endif
 // The number of key bits is a launch parameter: SORT_GBITS (13) by default, SORT_GBITS_LARGE (14) for the scenes whose
 // records live in HBM (62.6 vs 63.1 ms on the 10.4 M-triangle scene; the Sponza-class scene loses with 14: 22.3 vs 22.1).
@@ -671,72 +653,153 @@ k_sort_scan_tiles(uint32_t* __restrict__ bins, uint32_t* __restrict__ sums)
 #define SORT_GBITS_LARGE 14u
 #endif
 constexpr uint32_t SORT_GBITS_MAX = SORT_GBITS_LARGE > SORT_GBITS ? SORT_GBITS_LARGE : SORT_GBITS;
-constexpr uint32_t SORT_GBINS = 1u << SORT_GBITS_MAX, SORT_GCOLS = 1u << SORT_GCOLS_LOG2, SORT_GTILE = 4096u;
-constexpr uint32_t SORT_GSCAN_TILES = SORT_GBINS * SORT_GCOLS / SORT_TILE;              // scan tiles of 4096 counters (at most)
-static_assert(SORT_GSCAN_TILES <= 1024u, "one thread per scan tile in k_sortg_scan_sums");
+constexpr uint32_t SORT_GBITS_MIN = 12u;               // every thread of the scatter scans at least one uint4 of total[]
+constexpr uint32_t SORT_GBINS = 1u << SORT_GBITS_MAX, SORT_GCOLS = 1u << SORT_GCOLS_LOG2, SORT_GTILE = 8192u;     // SORT_GTILE: paths per block at least
+constexpr uint32_t SORT_GTHREADS = 1024u, SORT_GLOADS = 2u;
 static_assert(SORT_GBITS_MAX <= 14u, "the histogram of a block lives in 64 KB of LDS");
+static_assert(SORT_GBITS >= SORT_GBITS_MIN && SORT_GBITS_LARGE >= SORT_GBITS_MIN, "k_sortg_scatter: bins / 1024 is a multiple of 4");
 // full-resolution key, 15 bits: 12-bit Morton cell << 3 | direction octant (what the shade stage stores)
 __device__ __forceinline__ uint32_t sort_key_of(const SortBox& B, f3 o, f3 d)
 {
     return (sort_cell(B, o.x, o.y, o.z) << 3) | ((d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u));
 }
-// ... reduced to `bits` key bits: the high bits - 3 bits of the cell, the octant
+// ... reduced to `bits` key bits: the high bits - 3 bits of the cell, the octant (bit 15 of a stored key is ignored)
+__device__ __forceinline__ uint32_t sortg_reduce(uint32_t k, uint32_t bits) { return ((((k & 0x7fffu) >> 3) >> (15u - bits)) << 3) | (k & 7u); }
 __device__ __forceinline__ uint32_t sortg_key(const PathStreams& ps, const SortBox& B, uint32_t j, uint32_t bits)
 {
     uint32_t k;
     if (ps.sortKey) k = ps.sortKey[j];                 // written by the shade stage
     else { const float4 ro = ps.nRayO[j], rd = ps.nRayD[j]; k = sort_key_of(B, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z)); }
-    return (((k >> 3) >> (15u - bits)) << 3) | (k & 7u);
+    return sortg_reduce(k, bits);
 }
-__global__ void __launch_bounds__(256)
-k_sortg_hist(PathStreams ps, const uint32_t* __restrict__ mPtr, SortBox B, uint32_t* __restrict__ H, uint32_t bits)
+// the slice [lo, hi) of the m paths that block b counts and scatters: consecutive, lo a multiple of 8 (a 16-byte load of keys), and
+// at least SORT_GTILE paths -- the grid is sized for the capacity, and a block costs its row of the offset table whatever it sorts
+// (64 KB through L2 in the two passes), so late bounces leave the blocks they do not need without a slice
+__device__ __forceinline__ void sortg_slice(uint32_t m, uint32_t& lo, uint32_t& hi)
 {
-    __shared__ uint32_t cnt[SORT_GBINS];
-    const uint32_t m = *mPtr, t = threadIdx.x, cols = gridDim.x, bins = 1u << bits;
-    for (uint32_t k = t; k < bins; k += 256u) cnt[k] = 0u;
-    __syncthreads();
-    for (uint32_t base = blockIdx.x * SORT_GTILE; base < m; base += cols * SORT_GTILE)
-        for (uint32_t i = 0; i < 16u; ++i) {
-            const uint32_t j = base + i * 256u + t;
-            if (j < m) atomicAdd(&cnt[sortg_key(ps, B, j, bits)], 1u);
-        }
-    __syncthreads();
-    for (uint32_t k = t; k < bins; k += 256u) H[k * SORT_GCOLS + blockIdx.x] = cnt[k];       // (columns >= gridDim.x stay zero)
+    const uint32_t per = max(((m + gridDim.x - 1u) / gridDim.x + 7u) & ~7u, SORT_GTILE);
+    lo = min(m, blockIdx.x * per); hi = min(m, lo + per);
 }
-__global__ void __launch_bounds__(1024)
-k_sortg_scan_sums(uint32_t* __restrict__ sums, uint32_t nTiles)
+// f(reduced key of path j, j, run) for every j of [lo, hi), each exactly once and a thread's in rising order.  Stored keys go eight
+// per 16-byte load, SORT_GLOADS loads in flight per lane; a group of eight that crosses hi, keys that are not 16-byte aligned and
+// keys computed from the rays (no stored keys) go one by one.  run > 0: j is the first of `run` consecutive paths of this thread
+// with this key, run == 0: j continues that run -- neighbours in the streams are neighbours on the screen and share cells, so the
+// callers spend one LDS atomic per run, not per path (lanes that meet in a key serialise there)
+template <class F>
+__device__ __forceinline__ void sortg_each(const PathStreams& ps, const SortBox& B, uint32_t lo, uint32_t hi, uint32_t bits, F&& f)
 {
-    __shared__ uint32_t part[1024];
     const uint32_t t = threadIdx.x;
-    const uint32_t v = t < nTiles ? sums[t] : 0u;
-    part[t] = v;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {
-        const uint32_t x = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += x;
-        __syncthreads();
-    }
-    if (t < nTiles) sums[t] = part[t] - v;
+    if (ps.sortKey && !(reinterpret_cast<uintptr_t>(ps.sortKey) & 15u)) {
+        const uint4* kv = reinterpret_cast<const uint4*>(ps.sortKey);
+        for (uint32_t j0 = lo + t * 8u; j0 < hi; j0 += SORT_GTHREADS * 8u * SORT_GLOADS) {
+            uint4 v[SORT_GLOADS];
+#pragma unroll
+            for (uint32_t u = 0; u < SORT_GLOADS; ++u) {
+                const uint32_t j = j0 + u * SORT_GTHREADS * 8u;
+                v[u] = (j < hi && hi - j >= 8u) ? kv[j >> 3] : make_uint4(0u, 0u, 0u, 0u);
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < SORT_GLOADS; ++u) {
+                const uint32_t j = j0 + u * SORT_GTHREADS * 8u;
+                if (j >= hi) break;
+                if (hi - j >= 8u) {
+                    const uint32_t w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+                    uint32_t key[8], len[8];
+#pragma unroll
+                    for (uint32_t e = 0; e < 8u; ++e) key[e] = sortg_reduce((w[e >> 1] >> ((e & 1u) * 16u)) & 0xffffu, bits);
+                    len[7] = 1u;
+#pragma unroll
+                    for (int e = 6; e >= 0; --e) len[e] = key[e] == key[e + 1] ? len[e + 1] + 1u : 1u;
+#pragma unroll
+                    for (uint32_t e = 0; e < 8u; ++e) f(key[e], j + e, (e == 0u || key[e] != key[e - 1u]) ? len[e] : 0u);
+                } else
+                    for (uint32_t e = 0; j + e < hi; ++e) f(sortg_reduce(ps.sortKey[j + e], bits), j + e, 1u);
+            }
+        }
+    } else
+        for (uint32_t j = lo + t; j < hi; j += SORT_GTHREADS) f(sortg_key(ps, B, j, bits), j, 1u);
 }
-__global__ void __launch_bounds__(256)
-k_sortg_scatter(PathStreams ps, const uint32_t* __restrict__ mPtr, SortBox B, const uint32_t* __restrict__ H, const uint32_t* __restrict__ sums,
-                uint32_t* __restrict__ perm, uint32_t bits)
+// (A) total: 1 << bits words, zero on entry; off: row blockIdx.x of the (block, key) offset table, SORT_GBINS words per row
+__global__ void __launch_bounds__(SORT_GTHREADS)
+k_sortg_hist(PathStreams ps, const uint32_t* __restrict__ mPtr, SortBox B, uint32_t* __restrict__ total, uint32_t* __restrict__ off, uint32_t bits)
 {
     __shared__ uint32_t cnt[SORT_GBINS];
-    const uint32_t m = *mPtr, t = threadIdx.x, cols = gridDim.x, bins = 1u << bits;
-    for (uint32_t k = t; k < bins; k += 256u) {
-        const uint32_t at = k * SORT_GCOLS + blockIdx.x;
-        cnt[k] = H[at] + sums[at / SORT_TILE];
-    }
+    const uint32_t m = *mPtr, t = threadIdx.x, bins = 1u << bits;
+    uint32_t lo, hi;
+    sortg_slice(m, lo, hi);
+    if (lo >= hi) return;                              // (the whole block: m == 0, or fewer paths than blocks x 8)
+    for (uint32_t k = t; k < bins; k += SORT_GTHREADS) cnt[k] = 0u;
     __syncthreads();
-    for (uint32_t base = blockIdx.x * SORT_GTILE; base < m; base += cols * SORT_GTILE)
-        for (uint32_t i = 0; i < 16u; ++i) {
-            const uint32_t j = base + i * 256u + t;
-            if (j < m) perm[atomicAdd(&cnt[sortg_key(ps, B, j, bits)], 1u)] = j;      // (the order inside a key is arbitrary: no result depends on it)
-        }
+    sortg_each(ps, B, lo, hi, bits, [&](uint32_t key, uint32_t, uint32_t run) { if (run) atomicAdd(&cnt[key], run); });
+    __syncthreads();
+    uint32_t* mine = off + (size_t)blockIdx.x * SORT_GBINS;
+    // all of a thread's atomics are in flight before the first answer is stored (one after the other they are 8 or 16 round trips to
+    // memory, the whole cost of a small sort); the blocks start at different keys, so that those that finish together do not
+    // queue on the same words
+    uint32_t c[SORT_GBINS / SORT_GTHREADS], at[SORT_GBINS / SORT_GTHREADS];
+#pragma unroll
+    for (uint32_t i = 0; i < SORT_GBINS / SORT_GTHREADS; ++i) {
+        const uint32_t k = (i * SORT_GTHREADS + blockIdx.x * SORT_GTHREADS + t) & (bins - 1u);
+        c[i] = i * SORT_GTHREADS < bins ? cnt[k] : 0u;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < SORT_GBINS / SORT_GTHREADS; ++i) {
+        const uint32_t k = (i * SORT_GTHREADS + blockIdx.x * SORT_GTHREADS + t) & (bins - 1u);
+        at[i] = c[i] ? atomicAdd(&total[k], c[i]) : 0u;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < SORT_GBINS / SORT_GTHREADS; ++i) {
+        const uint32_t k = (i * SORT_GTHREADS + blockIdx.x * SORT_GTHREADS + t) & (bins - 1u);
+        if (c[i]) mine[k] = at[i];
+    }
 }
-
+// (B) totalNext: the SORT_GBINS words the next sort of this group counts into
+__global__ void __launch_bounds__(SORT_GTHREADS)
+k_sortg_scatter(PathStreams ps, const uint32_t* __restrict__ mPtr, SortBox B, const uint32_t* __restrict__ total, uint32_t* __restrict__ totalNext,
+                const uint32_t* __restrict__ off, uint32_t* __restrict__ perm, uint32_t bits)
+{
+    __shared__ uint32_t cnt[SORT_GBINS];
+    __shared__ uint32_t s_wave[SORT_GTHREADS / 64u];
+    const uint32_t m = *mPtr, t = threadIdx.x, bins = 1u << bits;
+    for (uint32_t k = blockIdx.x * SORT_GTHREADS + t; k < SORT_GBINS; k += gridDim.x * SORT_GTHREADS) totalNext[k] = 0u;
+    uint32_t lo, hi;
+    sortg_slice(m, lo, hi);
+    if (lo >= hi) return;
+    // exclusive scan of total[]: thread t owns the bins / 1024 consecutive keys from t * (bins / 1024) on
+    const uint32_t quads = bins / (SORT_GTHREADS * 4u);                   // 2 or 4 (1 with 12 key bits)
+    const uint4* tq = reinterpret_cast<const uint4*>(total) + t * quads;
+    const uint4* oq = reinterpret_cast<const uint4*>(off + (size_t)blockIdx.x * SORT_GBINS) + t * quads;
+    uint4 v[4], o[4];
+    uint32_t sum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q)
+        if (q < quads) { v[q] = tq[q]; o[q] = oq[q]; sum += v[q].x + v[q].y + v[q].z + v[q].w; }
+    uint32_t incl = sum;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t x = __shfl_up(incl, d);
+        if (__lane_id() >= d) incl += x;
+    }
+    if (__lane_id() == 63u) s_wave[t >> 6] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum;
+    for (uint32_t w = 0; w < (t >> 6); ++w) run += s_wave[w];
+    uint4* cq = reinterpret_cast<uint4*>(cnt) + t * quads;
+#pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q)
+        if (q < quads) {
+            uint4 c;
+            c.x = run + o[q].x; run += v[q].x; c.y = run + o[q].y; run += v[q].y; c.z = run + o[q].z; run += v[q].z; c.w = run + o[q].w; run += v[q].w;
+            cq[q] = c;
+        }
+    __syncthreads();
+    uint32_t at = 0;
+    sortg_each(ps, B, lo, hi, bits, [&](uint32_t key, uint32_t j, uint32_t run) {
+        if (run) at = atomicAdd(&cnt[key], run);           // (the order inside a key is arbitrary: no result depends on it)
+        if (at < m) perm[at] = j;                          // (always, when total[] was zero on entry of (A))
+        ++at;
+    });
+}
 // ---------------------------------------------------------------------------------------------
 // shadow: any-hit walk of the deferred shadow query, then hand over to the next bounce
 // ---------------------------------------------------------------------------------------------
@@ -1579,19 +1642,21 @@ void launch_shade(hipStream_t st, const AccelView& av, const SceneArgs& sc, cons
 }
 
 void launch_ray_sort_tiles(hipStream_t st, const PathStreams& ps, const uint32_t* mPtr, uint32_t nMax, const SortBox& box, uint32_t* H,
-                           uint32_t* perm, bool largeScene)
+                           uint32_t& phase, uint32_t* perm, uint32_t bits)
 {
     if (!nMax) return;
-    const uint32_t bits = largeScene ? SORT_GBITS_LARGE : SORT_GBITS, bins = 1u << bits, nTiles = bins * SORT_GCOLS / SORT_TILE;
-    uint32_t* sums = H + SORT_GBINS * SORT_GCOLS;
-    const uint32_t cols = std::min<uint32_t>((nMax + SORT_GTILE - 1u) / SORT_GTILE, SORT_GCOLS);
-    if (cols < SORT_GCOLS) (void)hipMemsetAsync(H, 0, (size_t)bins * SORT_GCOLS * sizeof(uint32_t), st);     // columns no block writes
-    hipLaunchKernelGGL(k_sortg_hist, dim3(cols), dim3(256), 0, st, ps, mPtr, box, H, bits);
-    hipLaunchKernelGGL(k_sort_scan_tiles, dim3(nTiles), dim3(256), 0, st, H, sums);
-    hipLaunchKernelGGL(k_sortg_scan_sums, dim3(1), dim3(1024), 0, st, sums, nTiles);
-    hipLaunchKernelGGL(k_sortg_scatter, dim3(cols), dim3(256), 0, st, ps, mPtr, box, H, sums, perm, bits);
+    bits = std::min(std::max(bits, SORT_GBITS_MIN), SORT_GBITS_MAX);
+    uint32_t* total = H + (phase & 1u) * SORT_GBINS;
+    uint32_t* totalNext = H + ((phase & 1u) ^ 1u) * SORT_GBINS;
+    uint32_t* off = H + 2u * SORT_GBINS;
+    const uint32_t blocks = std::min<uint32_t>((nMax + SORT_GTILE - 1u) / SORT_GTILE, SORT_GCOLS);
+    hipLaunchKernelGGL(k_sortg_hist, dim3(blocks), dim3(SORT_GTHREADS), 0, st, ps, mPtr, box, total, off, bits);
+    hipLaunchKernelGGL(k_sortg_scatter, dim3(blocks), dim3(SORT_GTHREADS), 0, st, ps, mPtr, box, total, totalNext, off, perm, bits);
+    phase ^= 1u;
 }
-uint32_t ray_sort_tiles_words() { return SORT_GBINS * SORT_GCOLS + SORT_GSCAN_TILES; }
+uint32_t ray_sort_tiles_words() { return 2u * SORT_GBINS + SORT_GBINS * SORT_GCOLS; }
+uint32_t ray_sort_zeroed_words() { return 2u * SORT_GBINS; }
+uint32_t ray_sort_key_bits(bool largeScene) { return largeScene ? SORT_GBITS_LARGE : SORT_GBITS; }
 
 void launch_shadow(hipStream_t st, const AccelView& av, const SceneArgs& sc, const PathStreams& ps, const uint32_t* nPtr,
                    uint32_t nMax, bool lastBounce, uint32_t nPixels, uint32_t sampleBase, float tmin, float tmax,

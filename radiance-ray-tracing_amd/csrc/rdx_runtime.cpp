@@ -61,8 +61,8 @@ constexpr int RDX_MAX_DEVICES = 16;
 // 1.5 ms), Sponza-class 24.5 / 24.6 (break-even), sample1 13.3 / 15.4 (its rays are coherent as they come; the sort scrambles the
 // pixel order).
 constexpr uint32_t RDX_SORT_AUTO_MIN_WIDE = 1u << 20;      // option "sort" -1: scenes with at least this many inner BVH nodes sort their rays per bounce ...
-constexpr uint32_t RDX_SORT_AUTO_MIN_WIDE_FULL = 1u << 15; // ... and so do scenes from this size on for chunks of more than sortMinPaths paths (the sort is four more dependent
-                                                           // launches per bounce: small shards lose with it, and so does a scene that sits in L2 anyway)
+constexpr uint32_t RDX_SORT_AUTO_MIN_WIDE_FULL = 1u << 15; // ... and so do scenes from this size on for chunks of more than sortMinPaths paths (the sort is two more dependent
+                                                           // launches per bounce, four when this was measured: small shards lose with it, and so does a scene that sits in L2 anyway)
 struct AccelCache {                // derived traversal layout of one TLAS buffer on one device (accel_layout.h)
     uint64_t version = ~0ull;
     DNode* tnodes = nullptr; DNode* ctnodes = nullptr; DInst* insts = nullptr; DNode* bnodes = nullptr; DTri* tris = nullptr;
@@ -137,7 +137,8 @@ struct Context {
     struct Group {
         PathStreams ps{};
         size_t cap = 0;
-        uint32_t* sortBins = nullptr;       // per-bounce ray sort: histogram scratch (ray_sort_tiles_words()) and the permutation
+        uint32_t* sortBins = nullptr;       // per-bounce ray sort: scratch (ray_sort_tiles_words(): the two total[] copies and the offset table; kernels.h) ...
+        uint32_t sortPhase = 0;             // ... which copy of total[] the next sort of this group counts into (it is zero by then)
         uint32_t* permE = nullptr; size_t permCap = 0;
         unsigned short* sortKey = nullptr;  // per-bounce ray sort: keys of the survivors, written by the shade stage
         size_t stageCap = 0;                // user stage mode: paths the extra streams (shD, shHit, payC ...) hold
@@ -1690,6 +1691,17 @@ static void bounce_switches(uint64_t chunkPaths, BounceArgs& B)
     }
 }
 
+// the sort scratch of a group, allocated on first use: the two copies of total[] start as zeros (stream-ordered before the group's
+// first sort); from then on every sort leaves the copy its successor counts into zeroed (kernels.h)
+static int ensure_sort_bins(Context::Group& G)
+{
+    if (G.sortBins) return 0;
+    HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.sortBins), (size_t)ray_sort_tiles_words() * 4));
+    HIP_OK(hipMemsetAsync(G.sortBins, 0, (size_t)ray_sort_zeroed_words() * 4, G.s0));
+    G.sortPhase = 0;
+    return 0;
+}
+
 // gps[k]: the streams of group k, its gPaths[k] paths generated and their first hits found (G.dCounts[0] = gPaths[k], device side).
 // Nothing is synchronised; on return gps[k] holds the streams as the last bounce left them.
 static int trace_bounces(const BounceArgs& B, PathStreams* gps, const uint32_t* gPaths, int nGroups)
@@ -1720,9 +1732,10 @@ static int trace_bounces(const BounceArgs& B, PathStreams* gps, const uint32_t* 
             ps.permS = nullptr; ps.permE = nullptr;
             if (B.sortOn) {
                 // per-bounce ray sort: the traversal launch below hands its rays out in (octant, Morton cell) order
-                if (!G.sortBins) HIP_OK(hipMalloc(reinterpret_cast<void**>(&G.sortBins), (size_t)ray_sort_tiles_words() * 4));
+                if (ensure_sort_bins(G)) return -1;
                 g_timer.begin(&g.stats.ms_sort, G.s0);
-                launch_ray_sort_tiles(G.s0, ps, G.dCounts + d + 1, n0, B.sortBox, G.sortBins, G.permE, acc(B.tlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE);
+                launch_ray_sort_tiles(G.s0, ps, G.dCounts + d + 1, n0, B.sortBox, G.sortBins, G.sortPhase, G.permE,
+                                      ray_sort_key_bits(acc(B.tlas)->s.nWide >= RDX_SORT_AUTO_MIN_WIDE));
                 g_timer.end(G.s0);
                 ps.permS = G.permE; ps.permE = G.permE;
             }
@@ -2306,6 +2319,29 @@ extern "C" int rdx_query_rays(rdx_buffer tlas, rdx_buffer rays, size_t rays_offs
         return -1;
     if (take_status()) return fail("rdx_query_rays: a traversal wave exceeded its iteration bound and gave up; the batch is incomplete");
     return 0;
+}
+
+// Test seam of the per-bounce ray sort: the frame path's launch (group 0's scratch and phase) on the caller's keys
+extern "C" int rdx_debug_sort_keys(rdx_buffer keys, size_t keys_offset, uint32_t live, uint32_t capacity, uint32_t key_bits, rdx_buffer perm,
+                                   size_t perm_offset)
+{
+    const char* who = "rdx_debug_sort_keys";
+    if (!g.initialized) return fail("rdx_init has not been called");
+    const CallRange R[2] = {{keys, keys_offset, (size_t)capacity * sizeof(uint16_t), "key", 2, true},
+                            {perm, perm_offset, (size_t)capacity * sizeof(uint32_t), "permutation", 4, true}};
+    if (check_call_handles(who, R)) return -1;
+    if (key_bits < 12u || key_bits > 14u) return fail("rdx_debug_sort_keys: key_bits must be 12, 13 or 14, not %u", key_bits);
+    if (live > capacity) return fail("rdx_debug_sort_keys: %u live keys in a capacity of %u", live, capacity);
+    if (capacity > (1u << 30)) return fail("rdx_debug_sort_keys: a capacity of %u keys is more than 2^30", capacity);
+    if (check_call_ranges(who, R, 1, capacity)) return -1;
+    if (!capacity) return 0;
+    Context::Group& G = g.groups[0];
+    if (ensure_sort_bins(G)) return -1;
+    HIP_OK(hipMemcpy(G.dCounts + 1, &live, sizeof live, hipMemcpyHostToDevice));
+    PathStreams ps{};
+    ps.sortKey = at<unsigned short>(keys, keys_offset);
+    return timed_launch(&rdx_trace_stats::ms_sort, {perm}, [&] {
+        launch_ray_sort_tiles(g.stream, ps, G.dCounts + 1, capacity, SortBox{}, G.sortBins, G.sortPhase, at<uint32_t>(perm, perm_offset), key_bits); });
 }
 
 // Surface records of a query's hits (surface.hip)
