@@ -1339,7 +1339,17 @@ static std::string strip_comments(const std::string& t)
     std::string o;
     o.reserve(t.size());
     for (size_t i = 0; i < t.size();) {
-        if (t.compare(i, 2, "//") == 0) { while (i < t.size() && t[i] != '\n') ++i; }
+        if (t.compare(i, 2, "//") == 0) {
+            // to the end of the line -- of the LOGICAL line: a backslash in front of the newline continues the comment, as it does
+            // for the compiler (the newlines stay, for the line numbers)
+            for (; i < t.size(); ++i) {
+                if (t[i] != '\n') continue;
+                size_t b = i;
+                if (b > 0 && t[b - 1] == '\r') --b;
+                if (b > 0 && t[b - 1] == '\\') { o.push_back('\n'); continue; }
+                break;
+            }
+        }
         else if (t.compare(i, 2, "/*") == 0) { const size_t e = t.find("*/", i + 2); const size_t j = e == std::string::npos ? t.size() : e + 2; o.push_back(' '); for (; i < j; ++i) if (t[i] == '\n') o.push_back('\n'); }
         else o.push_back(t[i++]);
     }
@@ -1372,7 +1382,47 @@ static uint64_t fnv1a64_nows(const std::string& t)
 // A program text with the BODIES of its closest-hit / miss stage functions blanked out (the functions sbt.json names for rows
 // without an any-hit shader, and the miss rows): two programs that agree on it differ only inside those functions -- the raygen
 // loop, the payload / scene structs, the helper functions, the any-hit rows and the dispatch tables are the same.
-static void blank_bodies(std::string& t, const std::vector<std::string>& names)
+// What blank_bodies does beyond blanking when it makes the REDUCED text of the eligibility rule (blank_stage_bodies).
+struct ReducedText {
+    bool lasting = false;       // out: a blanked body holds a preprocessor directive that outlives the function
+};
+// A directive that outlives the function it stands in: anything but #include and the conditionals (#if / #ifdef / #ifndef /
+// #elif / #else / #endif) -- #define, #undef, #pragma, #line ..., spelled `#` or with the digraph `%:` -- and the _Pragma
+// operator anywhere in the body.  The text behind such a body no longer means what the same characters mean in the stock program.
+static bool body_has_lasting_directive(const std::string& t, size_t from, size_t to)
+{
+    static const char* const kLocal[] = {"include", "if", "ifdef", "ifndef", "elif", "else", "endif"};
+    auto ident = [](char c) { return std::isalnum((unsigned char)c) || c == '_'; };
+    bool lineStart = true;
+    for (size_t i = from; i < to; ++i) {
+        const char c = t[i];
+        if (c == '\n') { lineStart = true; continue; }
+        if (c == ' ' || c == '\t' || c == '\r') continue;
+        const bool digraph = c == '%' && i + 1 < to && t[i + 1] == ':';
+        if (lineStart && (c == '#' || digraph)) {
+            size_t a = i + (digraph ? 2 : 1);
+            while (a < to && (t[a] == ' ' || t[a] == '\t')) ++a;
+            size_t b = a;
+            while (b < to && ident(t[b])) ++b;
+            const std::string word = t.substr(a, b - a);
+            bool local = word.empty();                         // a null directive
+            for (const char* k : kLocal) if (word == k) local = true;
+            if (!local) return true;
+        }
+        if (t.compare(i, 7, "_Pragma") == 0 && (i == 0 || !ident(t[i - 1])) && (i + 7 >= t.size() || !ident(t[i + 7]))) return true;
+        lineStart = false;
+    }
+    return false;
+}
+// does the line that holds `pos` begin with a preprocessor directive (`#` or `%:` after blanks)?
+static bool on_directive_line(const std::string& t, size_t pos)
+{
+    size_t ls = pos;
+    while (ls > 0 && t[ls - 1] != '\n') --ls;
+    while (ls < pos && (t[ls] == ' ' || t[ls] == '\t')) ++ls;
+    return t[ls] == '#' || (t[ls] == '%' && ls + 1 < t.size() && t[ls + 1] == ':');
+}
+static void blank_bodies(std::string& t, const std::vector<std::string>& names, ReducedText* reduced = nullptr)
 {
     for (const std::string& fn : names) {
         size_t pos = 0;
@@ -1387,10 +1437,23 @@ static void blank_bodies(std::string& t, const std::vector<std::string>& names)
             size_t r = q;
             for (; r < t.size(); ++r) { if (t[r] == '(') ++depth; else if (t[r] == ')') { if (--depth == 0) { ++r; break; } } }
             while (r < t.size() && std::isspace((unsigned char)t[r])) ++r;
+            if (reduced && r < t.size() && t[r] == ';' && !on_directive_line(t, pos) &&
+                std::count(t.begin(), t.begin() + pos, '{') == std::count(t.begin(), t.begin() + pos, '}')) {
+                // the reduced text only: a prototype of a stage function at file scope (a call is inside some body; the replacement
+                // list of a #define is neither) declares what the definition declares anyway; it goes, back to the end of whatever
+                // precedes it, never across a preprocessor line
+                size_t from = pos;
+                while (from > 0 && t[from - 1] != ';' && t[from - 1] != '}' && !(t[from - 1] == '\n' && on_directive_line(t, from - 1))) --from;
+                std::string gap((size_t)std::count(t.begin() + from, t.begin() + r + 1, '\n'), '\n');
+                t.replace(from, r + 1 - from, gap);
+                pos = from + gap.size();
+                continue;
+            }
             if (r >= t.size() || t[r] != '{') { pos = end; continue; }
             int braces = 0;
             size_t e = r;
             for (; e < t.size(); ++e) { if (t[e] == '{') ++braces; else if (t[e] == '}') { if (--braces == 0) { ++e; break; } } }
+            if (reduced && body_has_lasting_directive(t, r, e)) reduced->lasting = true;
             std::string blank = "{";
             blank.append((size_t)std::count(t.begin() + r, t.begin() + e, '\n'), '\n');       // line numbers stay (compiler diagnostics)
             blank += "}";
@@ -1399,7 +1462,10 @@ static void blank_bodies(std::string& t, const std::vector<std::string>& names)
         }
     }
 }
-static std::string blank_stage_bodies(const std::string& text)
+// -> false: the program has no reduced text -- a #define / #undef / #pragma inside a stage function reaches the text behind it,
+// which a reduced text could not show; such a program is not "the stock program outside its stage functions" and runs as the
+// megakernel it is.
+static bool blank_stage_bodies(const std::string& text, std::string& out)
 {
     std::string t = strip_comments(text);
     std::vector<std::string> names;
@@ -1427,12 +1493,20 @@ static std::string blank_stage_bodies(const std::string& text)
         }
         for (const Row* m = miss; m->fn; ++m) names.push_back(m->fn);
     }
-    blank_bodies(t, names);
-    return t;
+    ReducedText reduced;
+    blank_bodies(t, names, &reduced);
+    out = t;
+    return !reduced.lasting;
+}
+// the hash the eligibility rule compares with the stock program's; 0 (no program's) where there is no reduced text
+static uint64_t stage_reduced_hash(const std::string& text)
+{
+    std::string t;
+    return blank_stage_bodies(text, t) ? fnv1a64_nows(t) : 0;
 }
 extern "C" unsigned long long rdx_debug_stage_reduced_hash(const char* code, uint32_t size)
 {
-    return code ? fnv1a64_nows(blank_stage_bodies(std::string(code, size))) : (unsigned long long)RDX_STOCK_REDUCED_HASH;   // null: the stock program's
+    return code ? stage_reduced_hash(std::string(code, size)) : (unsigned long long)RDX_STOCK_REDUCED_HASH;   // null: the stock program's
 }
 
 // Compile-only check of the run-time shader compiler (no device needed; the CPU suite uses it): 0 = the program compiles in
@@ -1513,7 +1587,7 @@ extern "C" rdx_shader rdx_shader_module_create(const char* code, uint32_t size, 
         // 3b. anything else: the program's own raygen, as a megakernel.
         constexpr uint64_t kStockReducedHash = RDX_STOCK_REDUCED_HASH;     // of samples/shader.cl, by tools/stock_shader_hash.py
         //     "user_stages" 2: the caller asserts it for a program written from scratch (the raygen text is then not looked at).
-        const bool stages = g0.opt.userStages == 2 || (g0.opt.userStages == 1 && fnv1a64_nows(blank_stage_bodies(text)) == kStockReducedHash);
+        const bool stages = g0.opt.userStages == 2 || (g0.opt.userStages == 1 && stage_reduced_hash(text) == kStockReducedHash);
         if (stages) {
             // the stage kernel replaces the program's raygen: its body and that of the stock skeleton's camera helper go (dead
             // code there, and their get_global_id(0) has no `sceneData` in scope for the stage-mode macro)

@@ -204,7 +204,12 @@ const char* kStageBody =
     "                color += contribution * payload.color;\n"
     "                contribution *= payload.nextFactor;\n"
     "                end = depth + 1u >= maxDepth;\n"
-    "            } else if (depth == 0u) color = payload.color;\n"
+    "            } else if (depth == 0u) {\n"
+    "                /* nothing hit by the primary ray, or a shader that said so: the background colour -- and the loop goes ON to\n"
+    "                 * depth 1 along payload.nextRay*, where the shaders may answer otherwise (shader.cl:243-253 has no break here) */\n"
+    "                color = payload.color;\n"
+    "                end = depth + 1u >= maxDepth;\n"
+    "            }\n"
     "            if (end) sampleColor[(size_t)(frameID - sampleBase) * nPixels + slot] = (float4)(color, 0.0f);\n"
     "            alive = !end;\n"
     "        }\n"

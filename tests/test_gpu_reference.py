@@ -205,7 +205,8 @@ def test_user_closest_hit_shader_on_the_wavefront_pipeline(mods, cfg, kw):
 
 
 def test_user_stage_functions_the_pipeline_cannot_serve_are_refused(mods):
-    """Stage mode serves ONE nested traceRay per closest-hit shader, and only the stock shadow query (row 2, miss 4, 0.001 / 1000):
+    """Stage mode serves ONE nested traceRay per closest-hit shader, and only the stock shadow query (row 2, 0.001 / 1000; the miss
+    index is the shader's own, tests/test_gpu_user_stage_parity.py):
     a second query, or another kind of query, raises a status bit in the stage kernel and TraceRays fails naming the option that
     runs the program as a megakernel -- no wrong frame is ever returned.  A program whose stage function uses get_global_id()
     outside the scope of `sceneData` does not compile as a stage kernel; asserted eligibility then fails at module creation."""
@@ -227,6 +228,35 @@ def test_user_stage_functions_the_pipeline_cannot_serve_are_refused(mods):
             scenes.DeviceScene(s, shader_text=helper)
     finally:
         rd.SetOption("user_stages", 1)
+    # The stage kernel reads and writes the pool engine's path streams: under another traversal kernel, and in a scene the pool
+    # engine does not walk (instance SBT offsets), TraceRays fails naming the pool engine BEFORE anything is launched --
+    # imageScratch keeps what it held.
+    import user_stage_cases as usc
+    rd.SetOption("user_stages", 2)
+    try:
+        dev = scenes.DeviceScene(s, shader_text=base)
+        dev_sbt = scenes.DeviceScene(usc.make_scene(scenes, "sbt_offset", 96, 54), shader_text=base)
+    finally:
+        rd.SetOption("user_stages", 1)
+    marker = np.full(96 * 54 * 4, 0.25, np.float32)
+
+    def refused(d):
+        d.bind()
+        rd.WriteBuffer(d.plt, d.rdImageScratch, marker.nbytes, marker)
+        with pytest.raises(rd.RadianceError, match="need the pool engine"):
+            rd.TraceRays(d.plt, 0, 0, 0, 96, 54)
+        assert np.array_equal(d.read_scratch().reshape(-1), marker), "a refused frame wrote imageScratch"
+
+    try:
+        for kernel in (0, 1, 2):
+            rd.SetOption("kernel", kernel)
+            refused(dev)
+    finally:
+        rd.SetOption("kernel", 3)
+    refused(dev_sbt)
+    dev.bind()
+    rd.TraceRays(dev.plt, 0, 0, 0, 96, 54)                          # and with the pool engine back the same module renders
+    assert not np.array_equal(dev.read_scratch().reshape(-1), marker)
     # the stock pipeline is unaffected by the failed frames
     dev2 = scenes.DeviceScene(s)
     dev2.render()

@@ -63,3 +63,113 @@ def test_stage_mode_eligibility_rule(lib):
 def test_stock_program_with_an_edited_material_compiles_as_stage_kernel(lib):
     stock = open(REF_SHADER).read().replace("color += albedo * 0.1f;", "color += albedo * 0.25f;").encode()
     assert lib.rdx_debug_jit_compiles(stock, len(stock), b"gfx950", 1) == 0, lib.rdx_last_error().decode()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the eligibility rule against a table of edits of the stock text.  Each edit carries the classification that follows from the
+# rule's stated meaning: eligible iff the program differs from the stock one only INSIDE material / environment / shadowMiss.
+# ---------------------------------------------------------------------------------------------------------------------
+SKY = "payload->color.z = 0.5f;"                      # a statement of `environment`
+MATERIAL_HEAD = "void material(struct Payload* payload, struct HitData* hitData,"
+MATERIAL_PROTO = ("void material(struct Payload* payload, struct HitData* hitData,\n"
+                  "    struct SceneData* sceneData, image2d_array_t imageArray, sampler_t sampler);\n")
+
+
+def _once(text, old, new):
+    assert text.count(old) == 1, (old, text.count(old))
+    return text.replace(old, new)
+
+
+def _after_head(text, head, inserted):
+    """`inserted` as the first statement of the function (or struct) whose text begins with `head`"""
+    i = text.index(head)
+    assert text.find(head, i + 1) == -1, head
+    j = text.index("{", i)
+    return text[:j + 1] + "\n" + inserted + text[j + 1:]
+
+
+ELIGIBLE = {
+    "nested blocks": lambda t: _once(t, SKY, "{ if (payload->hit) { payload->color.z = 0.6f; } else { { payload->color.z = 0.5f; } } }"),
+    "balanced #if": lambda t: _once(t, SKY, "\n#if 1\n    payload->color.z = 0.7f;\n#else\n    payload->color.z = 0.5f;\n#endif\n"),
+    "prototype ahead of the definition": lambda t: _once(t, MATERIAL_HEAD, MATERIAL_PROTO + MATERIAL_HEAD),
+    "material called from environment": lambda t: _once(t, SKY, SKY + "\n    struct HitData none; none.instanceIndex = 0;\n"
+                                                        "    if (payload->color.x < 0.0f) material(payload, &none, sceneData, imageArray, sampler);"),
+    "CRLF line ends": lambda t: _once(t, SKY, "payload->color.z = 0.75f;").replace("\n", "\r\n"),
+}
+NOT_ELIGIBLE = {
+    "edit in shadow": lambda t: _after_head(t, "void shadow(struct Payload* payload, struct HitData* hitData,", "    payload->nextFactor = 0.5f;"),
+    "edit in anyShadow": lambda t: _after_head(t, "void anyShadow(", "    payload->hit = true;"),
+    "edit in getAlbedo": lambda t: _after_head(t, "inline float3 getAlbedo(", "    hitData->distance = 0.0f;"),
+    "edit in generateRay": lambda t: _after_head(t, "void generateRay(", "    float unused = 0.0f;"),
+    "edit in a struct": lambda t: _after_head(t, "struct SceneData\n{", "    int extra;"),
+    "another parameter list": lambda t: _once(t, "void environment(struct Payload* payload,", "void environment(struct Payload* payload, int extra,"),
+    "#define between two functions": lambda t: _once(t, "void shadowMiss(struct Payload* payload,", "#define payload_hit_is 1\nvoid shadowMiss(struct Payload* payload,"),
+    # a directive that outlives the function: the text behind it no longer means what the stock text means, and the reduced
+    # text cannot show it.  Such a program runs as the megakernel it is.
+    "#define inside a blanked body": lambda t: _once(t, SKY, SKY + "\n#define false true\n"),
+    "#undef inside a blanked body": lambda t: _once(t, SKY, SKY + "\n#undef PI\n"),
+    "#pragma inside a blanked body": lambda t: _once(t, SKY, SKY + "\n#pragma OPENCL FP_CONTRACT ON\n"),
+    "%:define (digraph) inside a blanked body": lambda t: _once(t, SKY, SKY + "\n%:define false true\n"),
+    "_Pragma inside a blanked body": lambda t: _once(t, SKY, SKY + "\n    _Pragma(\"OPENCL FP_CONTRACT ON\")\n"),
+    # a prototype is dropped from the reduced text; the replacement list of a macro that looks like one is not a prototype
+    "#define whose replacement looks like a prototype": lambda t: _once(t, "void shadowMiss(struct Payload* payload,", "#define cont material(1);\nvoid shadowMiss(struct Payload* payload,"),
+    "the same, continued over two lines": lambda t: _once(t, "void shadowMiss(struct Payload* payload,", "#define cont \\\n material(1);\nvoid shadowMiss(struct Payload* payload,"),
+}
+# Text the brace counter or the comment stripper can misread.  What is pinned: the calls return (no crash, no read past the
+# text); a text that comes out eligible compiles as a stage kernel; and for the comment that continues over a backslash, that
+# the continued line stays comment.  Equivalence of an eligible text with its megakernel is not asserted here (the GPU parity
+# file does that for its own fixture).  The unterminated comment is no program for a compiler; the stage kernel is compiled
+# from the stripped text, where the comment is gone, so this case pins "no crash, no over-read" and little else.
+SAFE = {
+    "'}' character constant": lambda t: _once(t, SKY, SKY + "\n    const char brace = '}';"),
+    "#if / #else with different brace counts": lambda t: _once(t, SKY, "\n#if 1\n    if (!payload->hit) {\n#else\n    if (!payload->hit) { {\n#endif\n    payload->color.z = 0.5f; }\n"),
+    "unterminated /*": lambda t: t + "\n/* this comment never ends\nvoid material(int x) {",
+    # the compiler reads the second line as comment; so must the text the stage kernel is compiled from
+    "// comment ending in a backslash": lambda t: _once(t, SKY, SKY + "\n    // the next line belongs to this comment \\\n    this is not OpenCL C;\n"),
+}
+
+
+@pytest.fixture(scope="module")
+def stock():
+    if not os.path.exists(REF_SHADER):
+        pytest.skip("/root/reference is absent (GPU box)")
+    return open(REF_SHADER).read()
+
+
+def _hash(lib, s):
+    b = s.encode()
+    return lib.rdx_debug_stage_reduced_hash(b, len(b))
+
+
+def _compiles_as_stage_kernel(lib, s):
+    b = s.encode()
+    return lib.rdx_debug_jit_compiles(b, len(b), b"gfx950", 1) == 0
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="ROCm clang is not installed")
+@pytest.mark.parametrize("name", list(ELIGIBLE))
+def test_edit_inside_a_stage_function_stays_eligible(lib, stock, name):
+    edited = ELIGIBLE[name](stock)
+    assert edited != stock
+    assert _hash(lib, edited) == lib.rdx_debug_stage_reduced_hash(None, 0), name
+    assert _compiles_as_stage_kernel(lib, edited), lib.rdx_last_error().decode()
+
+
+@pytest.mark.parametrize("name", list(NOT_ELIGIBLE))
+def test_edit_outside_the_stage_functions_is_not_eligible(lib, stock, name):
+    edited = NOT_ELIGIBLE[name](stock)
+    assert edited != stock
+    assert _hash(lib, edited) != lib.rdx_debug_stage_reduced_hash(None, 0), name
+
+
+@pytest.mark.skipif(not os.path.exists(CLANG), reason="ROCm clang is not installed")
+@pytest.mark.parametrize("name", list(SAFE))
+def test_text_the_brace_counter_can_misread_is_handled_safely(lib, stock, name):
+    """the calls return; a text that comes out eligible compiles as a stage kernel (from its stripped text); the
+    backslash-continued comment stays comment (its second line is not OpenCL C)"""
+    edited = SAFE[name](stock)
+    assert edited != stock
+    if _hash(lib, edited) == lib.rdx_debug_stage_reduced_hash(None, 0):
+        assert _compiles_as_stage_kernel(lib, edited), lib.rdx_last_error().decode()
+    if name == "// comment ending in a backslash":
+        assert _hash(lib, edited) == lib.rdx_debug_stage_reduced_hash(None, 0), "the continued line was taken for program text"
