@@ -335,6 +335,51 @@ inline uint32_t TraceAreaPaths(Platform*, TopAccelStruct accelStruct, Buffer ray
     return invalid;
 }
 
+// Extension (no reference counterpart; rdx_env_table_size, rdx_env_build): the bytes of the sampling table of a width x height
+// lat-long environment image (0: a size outside the limits), and the table of the float4 image `image` built into `table`.
+inline size_t EnvTableSize(uint32_t width, uint32_t height) { return rdx_env_table_size(width, height); }
+inline void BuildEnvironment(Platform*, Buffer image, uint32_t width, uint32_t height, Buffer table, size_t imageOffset = 0, size_t tableOffset = 0)
+{
+    if (rdx_env_build(image, imageOffset, width, height, table, tableOffset))
+        detail::fatal("BuildEnvironment");
+}
+
+// Extension (no reference counterpart; rdx_env_light_hits): AreaLightHits with the environment (image + table) in the place of the
+// one record: one importance-sampled direction per ray, from pcg3d of `keys` on random stream `stream` or from x, y, z of `randoms`
+// (exactly one of the two is nullptr).  The shadow ray has the stock interval; an environment without light gives zeros.
+inline void EnvLightHits(Platform*, Buffer rays, Buffer materials, uint32_t n, Buffer image, Buffer table, uint32_t width, uint32_t height, Buffer keys,
+                         uint32_t stream, Buffer randoms, Buffer lit, Buffer shadow = nullptr, size_t raysOffset = 0, size_t materialsOffset = 0,
+                         size_t imageOffset = 0, size_t tableOffset = 0, size_t keysOffset = 0, size_t randomsOffset = 0, size_t litOffset = 0,
+                         size_t shadowOffset = 0)
+{
+    if (rdx_env_light_hits(rays, raysOffset, materials, materialsOffset, n, image, imageOffset, table, tableOffset, width, height, keys, keysOffset, stream,
+                           randoms, randomsOffset, lit, litOffset, shadow, shadowOffset))
+        detail::fatal("EnvLightHits");
+}
+
+// Extension (no reference counterpart; rdx_env_lookup): the texel (rgb, 0) the environment shows along the direction of each ray.
+inline void EnvLookup(Platform*, Buffer rays, uint32_t n, Buffer image, Buffer table, uint32_t width, uint32_t height, Buffer radiance,
+                      size_t raysOffset = 0, size_t imageOffset = 0, size_t tableOffset = 0, size_t radianceOffset = 0)
+{
+    if (rdx_env_lookup(rays, raysOffset, n, image, imageOffset, table, tableOffset, width, height, radiance, radianceOffset))
+        detail::fatal("EnvLookup");
+}
+
+// Extension (no reference counterpart; rdx_trace_paths_env): TraceAreaPaths with the environment as one more record after the two
+// tables (random stream areaCount), lightCount + areaCount + 1 <= RDX_MAX_PATH_LIGHTS; a first ray that hits nothing shows the
+// environment.  Returns the number of hits that `scene` does not describe (they count as misses).
+inline uint32_t TraceEnvPaths(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer keys, uint32_t n, uint32_t maxDepth, Buffer lights,
+                              uint32_t lightCount, Buffer area, uint32_t areaCount, Buffer image, Buffer table, uint32_t width, uint32_t height,
+                              const rdx_shading_buffers& scene, Buffer radiance, size_t raysOffset = 0, size_t keysOffset = 0, size_t lightsOffset = 0,
+                              size_t areaOffset = 0, size_t imageOffset = 0, size_t tableOffset = 0, size_t radianceOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_trace_paths_env(accelStruct, rays, raysOffset, keys, keysOffset, n, maxDepth, lights, lightsOffset, lightCount, area, areaOffset, areaCount, image,
+                            imageOffset, table, tableOffset, width, height, &scene, radiance, radianceOffset, &invalid))
+        detail::fatal("TraceEnvPaths");
+    return invalid;
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

@@ -751,7 +751,94 @@ int         rdx_trace_paths_area(rdx_buffer tlas,
                                  rdx_buffer radiance, size_t radiance_offset,     /* out: float4 per path: rgb, w = 0 */
                                  uint32_t* invalid_out);                          /* optional */
 
-/* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_area applies to the byte ranges it is given, on plain
+/* The environment: a lat-long image of width x height float32 RGBA texels in device memory (alpha ignored), importance-sampled at
+ * ONE direction per hit.  Row 0 is the zenith (+y); column x covers the azimuth [2 pi x / W, 2 pi (x + 1) / W); the direction of
+ * (theta, phi) is (sin theta cos phi, cos theta, sin theta sin phi).  1 <= width <= 16384, 1 <= height <= 8192.  No rotation or
+ * intensity (scale or roll the image), one sample per hit, no multiple-importance sampling, no filtering; user closest-hit
+ * programs do not run here; one device.  The reference has no environment light.
+ * rdx_env_table_size(width, height): the bytes of the sampling table, 0 for a size outside the limits.
+ * rdx_env_build writes the table of the image at image_offset into the caller's buffer at table_offset (both multiples of 16), on
+ * the device, in stream order; the call blocks.  The parts are 16-byte aligned (padding is zero), in this order:
+ *   header   64 bytes: uint32 magic 0x56454452, version 1, width, height; float32 wmax, twoPiOverW = (float)(2 pi / W), wOverTwoPi =
+ *            (float)(W / (2 pi)); uint32 0; uint64 total; 24 zero bytes;
+ *   rowCos   float32[H + 1]: (float)cos(pi y / H), computed by the host in double; entry 0 is exactly 1, entry H exactly -1.  Rows
+ *            are bands of cos(theta), so a texel's solid angle is twoPiOverW * (rowCos[y] - rowCos[y + 1]) and the device evaluates
+ *            no transcendental for the table or for E;
+ *   C        uint32[H][W]: the inclusive prefix sums along each row of
+ *            w = max(r, max(g, b)) * (rowCos[y] - rowCos[y + 1]) in float32 (a NaN channel makes the maximum a NaN), taken as 0
+ *                where it is not finite or not positive; wmax = the maximum of w;
+ *            q = 0 where w == 0, else max(1, min(65535, (uint32)(w * (65535.0f / wmax)))): every texel with any light in it can
+ *                be sampled;
+ *   M        uint64[H]: the inclusive prefix sums of the row sums; total = M[H - 1].
+ * Maximum and integer sums do not depend on the order they are taken in: the table's bytes are a function of the image alone.
+ * rdx_env_light_hits is rdx_area_light_hits with the environment in the place of the one record: rays, materials, n, keys |
+ * randoms, stream, lit and shadow are that call's.  The random triple (u, v, z) is pcg3d(key.frameID, key.pixel, key.depth +
+ * ((stream + 1u) << 16)) on the keys route and x, y, z of the caller's float4 on the randoms route; u can be exactly 1.0.  For a
+ * material record with hit == 1, every float32 operation rounded on its own:
+ *   X = min((uint64)((double)u * (double)total), total - 1)  (a caller's u outside [0, 1] or NaN is held to the two ends);
+ *   y = the first row with M[y] > X; lo = y ? M[y - 1] : 0; rowSum = M[y] - lo;
+ *   fy = ((float)(X - lo) + 0.5f) / (float)rowSum;
+ *   Xc = min((uint64)((double)v * (double)rowSum), rowSum - 1); x = the first column with C[y][x] > Xc;
+ *   q = C[y][x] - (x ? C[y][x - 1] : 0); fx = z;
+ *   ct = rowCos[y] + fy * (rowCos[y + 1] - rowCos[y]); st = sqrtf(max(0, 1 - ct * ct)); phi = ((float)x + fx) * twoPiOverW;
+ *   L = (st * cosf(phi), ct, st * sinf(phi)), not normalised again;
+ *   E = image[y][x].rgb * ((((float)total / (float)q) * twoPiOverW) * (rowCos[y] - rowCos[y + 1])): the one-sample estimator under
+ *            the pdf q / (total * the texel's solid angle);
+ *   tmax = 1000.0f, the stock interval, as for a directional light;
+ *   DARK     total == 0; the header's magic, width or height are not the call's; q == 0;
+ *   else     lit and the shadow record as for rdx_area_light_hits.
+ * A dark record and any other value of `hit` give 16 zero bytes in `lit` and 32 in `shadow`.  Every index formed from table
+ * contents is held to [0, H) / [0, W), and both searches are bounded by H and W, not by table contents: a table of garbage gives
+ * unspecified colours, never a read outside the image and table ranges.  Refused, before anything is launched: what
+ * rdx_area_light_hits refuses, with the image and table ranges -- 16 W H bytes and rdx_env_table_size(W, H) bytes at offsets that
+ * are multiples of 16 -- in the place of the area record; a size outside the limits; an output range that overlaps the image or the
+ * table.  n == 0 succeeds and touches nothing.
+ * rdx_env_lookup: radiance[i] = (rgb, 0) of the texel the environment shows along the direction of ray i, with the texel's bits;
+ * zeros for a zero or non-finite direction and for a table whose header is not the call's.  The row is the band of rowCos that
+ * holds normalize(d).y -- the first y with rowCos[y + 1] < it, the sampling bands --, the column min((uint32)(phi * wOverTwoPi),
+ * W - 1) with phi = atan2f(d.z, d.x), plus 6.2831855f where negative.  Nearest texel, no filtering.
+ * rdx_trace_paths_env is rdx_trace_paths_area with the environment as one more record AFTER the light_count punctual and the
+ * area_count area records, sampled via rdx_env_light_hits on the keys route with stream = area_count; light_count + area_count + 1
+ * <= RDX_MAX_PATH_LIGHTS.  A path whose FIRST ray hits nothing shows rdx_env_lookup of that ray in the place of the stock miss
+ * colour; a later miss ends the path and adds nothing: light is counted by next-event estimation alone, so nothing is counted
+ * twice.  radiance[i].rgb is `color` of the README's loop over the per-hit calls, bit for bit.  Everything else, the refusals
+ * included, as for rdx_trace_paths_area, with the image and table ranges added; the radiance range may overlap neither. */
+size_t      rdx_env_table_size(uint32_t width, uint32_t height);
+int         rdx_env_build(rdx_buffer image, size_t image_offset,                  /* float4 per texel, row-major, row 0 = +y */
+                          uint32_t width, uint32_t height,
+                          rdx_buffer table, size_t table_offset);                 /* out: rdx_env_table_size(width, height) bytes */
+int         rdx_env_light_hits(rdx_buffer rays, size_t rays_offset,               /* rdx_ray: only the direction is read */
+                               rdx_buffer materials, size_t materials_offset,     /* rdx_material_record per ray */
+                               uint32_t n,
+                               rdx_buffer image, size_t image_offset,
+                               rdx_buffer table, size_t table_offset,             /* as rdx_env_build wrote it for this image */
+                               uint32_t width, uint32_t height,
+                               rdx_buffer keys, size_t keys_offset,               /* rdx_shade_key per ray, or NULL */
+                               uint32_t stream,                                   /* keys route: 0 .. 0xfffe */
+                               rdx_buffer randoms, size_t randoms_offset,         /* float4 per ray (x, y, z used), or NULL */
+                               rdx_buffer lit, size_t lit_offset,                 /* out float4 per ray: rgb, w = 0 */
+                               rdx_buffer shadow, size_t shadow_offset);          /* optional out: rdx_ray per ray */
+int         rdx_env_lookup(rdx_buffer rays, size_t rays_offset, uint32_t n,       /* rdx_ray: only the direction is read */
+                           rdx_buffer image, size_t image_offset,
+                           rdx_buffer table, size_t table_offset,
+                           uint32_t width, uint32_t height,
+                           rdx_buffer radiance, size_t radiance_offset);          /* out float4 per ray: rgb, w = 0 */
+int         rdx_trace_paths_env(rdx_buffer tlas,
+                                rdx_buffer rays, size_t rays_offset,              /* rdx_ray per path: the first segment, with ITS tmin / tmax */
+                                rdx_buffer keys, size_t keys_offset,              /* rdx_shade_key per path: frameID, pixel (depth, _0 ignored) */
+                                uint32_t n, uint32_t max_depth,                   /* 0 .. 62 */
+                                rdx_buffer lights, size_t lights_offset,          /* the table of rdx_punctual_light records */
+                                uint32_t light_count,
+                                rdx_buffer area, size_t area_offset,              /* the table of rdx_area_light records */
+                                uint32_t area_count,                              /* light_count + area_count + 1 <= RDX_MAX_PATH_LIGHTS */
+                                rdx_buffer image, size_t image_offset,
+                                rdx_buffer table, size_t table_offset,
+                                uint32_t width, uint32_t height,
+                                const rdx_shading_buffers* scene,                 /* slots 4, 5, 7, 8, 9, 10, 11, 12 as for rdx_shade_hits */
+                                rdx_buffer radiance, size_t radiance_offset,      /* out: float4 per path: rgb, w = 0 */
+                                uint32_t* invalid_out);                           /* optional */
+
+/* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_env applies to the byte ranges it is given, on plain
  * numbers (needs no device and no initialised library; no address is dereferenced) -> 0, or -1 with the refusal in
  * rdx_last_error().  A row is one range: `bytes` at `offset` of a buffer of `size` bytes at `address`; `align` (a power of two)
  * is the multiple required of the offset and of the address; present == 0: an optional buffer that was not given, the row is

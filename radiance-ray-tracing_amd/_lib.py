@@ -208,6 +208,16 @@ SIGNATURES = {
     "rdx_trace_paths_area": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                        C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t,
                                        C.POINTER(C.c_uint32)]),
+    "rdx_env_table_size": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rdx_env_build": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "rdx_env_light_hits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_size_t]),
+    "rdx_env_lookup": (C.c_int, [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                 C.c_void_p, C.c_size_t]),
+    "rdx_trace_paths_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                      C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                      C.c_uint32, C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "rdx_debug_check_ranges": (C.c_int, [C.POINTER(rdx_debug_range), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),

@@ -1,17 +1,18 @@
 // light_emit.h -- what one light gives at one shaded point, written ONCE for the per-hit calls (rdx_light_hits,
-// rdx_punctual_light_hits, rdx_area_light_hits) and the per-path calls (path_shade.h), so a path call has the bits of the per-hit
+// rdx_punctual_light_hits, rdx_area_light_hits, rdx_env_light_hits) and the per-path calls (path_shade.h), so a path call has the bits of the per-hit
 // calls by construction: one emit function per kind of light -- (L, E, tmax) seen from `above`, or dark --, one record function
 // from that to the lit colour and the shadow ray, and the body of the three per-hit kernels.  Device code only.
 //
 // The PBR and frame functions are those of stages.h, called as `material` calls them.  The units that include this header are
 // compiled with -ffp-contract=off: every float32 operation is rounded on its own, and d2, the cone's cosine, p, n and g are plain
 // products and sums, NOT dot3 / cross3, which may fuse: numpy float32 restates them (tests/punctual_cases.py `emitted`,
-// tests/area_cases.py `emitted_area`).
+// tests/area_cases.py `emitted_area`, tests/env_cases.py `sampled_env`).
 #pragma once
 #include "kernels.h"
 
 #include "area.h"
 #include "device_math.h"
+#include "env.h"
 #include "stages.h"
 
 namespace rdx {
@@ -96,6 +97,90 @@ __device__ __forceinline__ bool area_emit(const AreaLight* __restrict__ lt, cons
 __device__ __forceinline__ f3 area_random(uint32_t frameID, uint32_t pixel, uint32_t depth, uint32_t stream)
 {
     return pcg3d(frameID, pixel, depth + ((stream + 1u) << 16));
+}
+
+// the environment (include/rdx.h rdx_env_light_hits; env.h for the table) with the random triple (u, v, z): u chooses the row y in
+// M and the place fy inside its band of cos(theta), v the column x in row y of C, z the place fx inside the texel.  E = texel x
+// (total / q) x the texel's solid angle -- the one-sample estimator under the pdf q / (total x solid angle) --, the interval is the
+// stock one, as for a directional light.  Dark: no light in the image (total 0), a header that is not the call's, q == 0.  `env` is
+// the same in every lane, so the header arrives through the scalar cache; the searches are per lane.  Both are bounded by the CALL's
+// H and W and every index stays inside [0, H) / [0, W): a table of garbage gives unspecified colours, never a read outside the
+// image or the table.  u can be exactly 1.0 (pcg3d divides by (float)0xffffffff), hence the two min.
+__device__ __forceinline__ bool env_header_ok(const EnvView& env)
+{
+    const EnvHeader* hd = env.header();
+    return hd->magic == ENV_MAGIC && hd->width == env.W && hd->height == env.H;
+}
+
+// min((uint64)((double)u * (double)sum), sum - 1) for u in [0, 1]; a caller's own random number outside that, or a NaN, is held to
+// the ends before the conversion, which is defined for values inside uint64 alone.  sum == 0 (a table of garbage): 0
+__device__ __forceinline__ uint64_t env_pick(float u, uint64_t sum)
+{
+    const double t = (double)u * (double)sum;
+    if (!(t > 0.0)) return 0ull;
+    if (t >= (double)sum) return sum ? sum - 1ull : 0ull;
+    return (uint64_t)t;
+}
+
+__device__ __forceinline__ bool env_emit(const EnvView& env, float u, float v, float z, f3& L, f3& E, float& tmax)
+{
+    const EnvHeader* hd = env.header();
+    const uint64_t total = hd->total;
+    if (!env_header_ok(env) || total == 0ull) return false;
+    const float twoPiOverW = hd->twoPiOverW;
+    const uint64_t* __restrict__ M = env.M();
+    const uint64_t X = env_pick(u, total);
+    uint32_t lo = 0u, hi = env.H - 1u;           // the first row with M[y] > X
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (M[mid] > X) hi = mid; else lo = mid + 1u;
+    }
+    const uint32_t y = lo;
+    const uint64_t below = y ? M[y - 1u] : 0ull, rowSum = M[y] - below;
+    const float fy = ((float)(X - below) + 0.5f) / (float)rowSum;
+    const uint32_t* __restrict__ Cy = env.C() + (size_t)y * env.W;
+    const uint64_t Xc = env_pick(v, rowSum);
+    lo = 0u; hi = env.W - 1u;                    // the first column with C[y][x] > Xc
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if ((uint64_t)Cy[mid] > Xc) hi = mid; else lo = mid + 1u;
+    }
+    const uint32_t x = lo;
+    const uint32_t q = Cy[x] - (x ? Cy[x - 1u] : 0u);
+    if (q == 0u) return false;
+    const float* __restrict__ rowCos = env.rowCos();
+    const float c0 = rowCos[y], c1 = rowCos[y + 1u];
+    const float ct = c0 + fy * (c1 - c0);
+    const float st = sqrtf(cl_max(0.0f, 1.0f - ct * ct));
+    const float phi = ((float)x + z) * twoPiOverW;
+    L = mk3(st * cosf(phi), ct, st * sinf(phi));
+    const float4 texel = env.image[(size_t)y * env.W + x];
+    const float s = (((float)total / (float)q) * twoPiOverW) * (c0 - c1);
+    E = mk3(texel.x * s, texel.y * s, texel.z * s);
+    tmax = 1000.0f;
+    return true;
+}
+
+// the texel the environment shows along d (rdx_env_lookup, and the depth-0 miss of rdx_trace_paths_env): the row is the band of
+// rowCos that holds normalize3(d).y -- the sampling bands --, the column that of atan2f(d.z, d.x); nearest texel, its bits
+__device__ __forceinline__ float4 env_lookup(const EnvView& env, const f3& d)
+{
+    const float4 none = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float inf = __builtin_inff();
+    if (d.x == 0.0f && d.y == 0.0f && d.z == 0.0f) return none;
+    if (!(fabsf(d.x) < inf) || !(fabsf(d.y) < inf) || !(fabsf(d.z) < inf) || !env_header_ok(env)) return none;
+    const float c = normalize3(d).y;
+    const float* __restrict__ rowCos = env.rowCos();
+    uint32_t lo = 0u, hi = env.H - 1u;           // the first row whose lower edge lies below c
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (rowCos[mid + 1u] < c) hi = mid; else lo = mid + 1u;
+    }
+    float phi = atan2f(d.z, d.x);
+    if (phi < 0.0f) phi = phi + 6.2831855f;
+    const uint32_t x = min((uint32_t)(phi * env.header()->wOverTwoPi), env.W - 1u);
+    const float4 texel = env.image[(size_t)lo * env.W + x];
+    return make_float4(texel.x, texel.y, texel.z, 0.0f);
 }
 
 // ---- record ----

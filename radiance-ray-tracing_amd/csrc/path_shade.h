@@ -1,12 +1,12 @@
 // path_shade.h -- the shade kernel of one bounce of the path calls (rdx_trace_paths_lights, rdx_trace_paths_punctual,
-// rdx_trace_paths_area), written ONCE as a function template over the bounce's light source:
+// rdx_trace_paths_area, rdx_trace_paths_env), written ONCE as a function template over the bounce's light source:
 //
 //   closest-hit query -> path_shade<Source> -> any-hit query of live x Source::count() shadow rays -> k_lights_fold (light_paths.hip)
 //
 // It is what rdx_resolve_hits + rdx_resolve_materials + one per-hit light call per light + rdx_scatter_hits compute for a live
 // ray, in one pass: the hit is gathered ONCE (hit_material.h), the tangent frame of the normal is built ONCE and serves every light
-// (light_emit.h) and the sample.  k_lights_shade, k_punctual_shade and k_area_shade (light_paths.hip, punctual.hip, area.hip) are
-// one-line callers with the sources below.  Device code only.
+// (light_emit.h) and the sample.  k_lights_shade, k_punctual_shade, k_area_shade and k_env_shade (light_paths.hip, punctual.hip,
+// area.hip, env.hip) are one-line callers with the sources below.  Device code only.
 #pragma once
 #include "kernels.h"
 
@@ -18,12 +18,15 @@ namespace rdx {
 
 constexpr uint32_t PATH_SHADE_BLOCK = 256;
 
-// ---- the light sources: count() lights, and emit(j, above, id, depth, L, E, tmax) = the emit function (light_emit.h) of light j.
+// ---- the light sources: count() lights, emit(j, above, id, depth, L, E, tmax) = the emit function (light_emit.h) of light j, and
+// miss(rd) = what a path whose FIRST ray, of direction rd, hits nothing shows: the stock miss colour (stages.h `environment`).
 // Every table is the same address in every lane and the loop counter is uniform, so a record's words arrive through the scalar
 // cache and the branch between two tables is uniform.  The tables are the one thing the caller's records can point a kernel at,
 // and the host has checked their records into their buffers. ----
 
 // the scene buffer's DirLight array: k_light_hits for light j
+__device__ __forceinline__ float4 stock_miss() { return make_float4(0.2f, 0.2f, 0.5f, 0.0f); }
+
 struct DirLightSource {
     const DirLight* __restrict__ lights;
     uint32_t nLights;
@@ -32,6 +35,7 @@ struct DirLightSource {
     {
         return dir_emit(lights + j, L, E, tmax);
     }
+    __device__ __forceinline__ float4 miss(const float4&) const { return stock_miss(); }
 };
 
 // a caller's punctual table: k_punctual_light_hits for record j
@@ -43,6 +47,7 @@ struct PunctualSource {
     {
         return punctual_emit(lights + j, above, L, E, tmax);
     }
+    __device__ __forceinline__ float4 miss(const float4&) const { return stock_miss(); }
 };
 
 // a punctual table, then an area table: after the punctual records, k_area_light_hits for area record a = j - nLights on the keys
@@ -60,6 +65,27 @@ struct PunctualAreaSource {
         const f3 rnd = area_random(id.y, id.z, depth, a);
         return area_emit(area + a, above, rnd.x, rnd.y, L, E, tmax);
     }
+    __device__ __forceinline__ float4 miss(const float4&) const { return stock_miss(); }
+};
+
+// a punctual table, an area table, then the environment as record nLights + nArea: k_env_light_hits on the keys route with
+// stream = nArea and the path's own (frame, pixel, depth).  A first ray that hits nothing shows the environment's texel
+struct PunctualAreaEnvSource {
+    const PunctualLight* __restrict__ lights;
+    uint32_t nLights;
+    const AreaLight* __restrict__ area;
+    uint32_t nArea;
+    EnvView env;
+    __device__ __forceinline__ uint32_t count() const { return nLights + nArea + 1u; }
+    __device__ __forceinline__ bool emit(uint32_t j, const f3& above, const uint4& id, uint32_t depth, f3& L, f3& E, float& tmax) const
+    {
+        if (j < nLights) return punctual_emit(lights + j, above, L, E, tmax);
+        const uint32_t a = j - nLights;
+        const f3 rnd = area_random(id.y, id.z, depth, a);
+        if (a < nArea) return area_emit(area + a, above, rnd.x, rnd.y, L, E, tmax);
+        return env_emit(env, rnd.x, rnd.y, rnd.z, L, E, tmax);
+    }
+    __device__ __forceinline__ float4 miss(const float4& rd) const { return env_lookup(env, mk3(rd.x, rd.y, rd.z)); }
 };
 
 // One live ray per lane.  A hit that fails gather_hit is a miss and is counted -- one ballot per wave, one atomic by its first
@@ -93,8 +119,12 @@ __device__ __forceinline__ void path_shade(const DInst* __restrict__ insts, cons
             alive = gather_hit(sc, slotOf, nInst, hb, g);
             bad = !alive;
         }
-        // a path's colour starts at zero; a miss at depth 0 shows the stock miss colour (stages.h `environment`)
-        if (depth == 0u) io.radiance[i] = alive ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : make_float4(0.2f, 0.2f, 0.5f, 0.0f);
+        // a path's colour starts at zero; a miss at depth 0 shows what the source shows there
+        if (depth == 0u) {
+            float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (!alive) first = source.miss(rd);
+            io.radiance[i] = first;
+        }
     }
     // wave64 ballots: every lane of the wave is here (no thread has returned)
     const unsigned long long mb = __ballot(bad);

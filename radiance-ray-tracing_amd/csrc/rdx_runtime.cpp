@@ -35,6 +35,7 @@
 #include RDX_SBT_HEADER
 #include "accel_layout.h"
 #include "area.h"
+#include "env.h"
 #include "bvh_build.h"
 #include "device_math.h"
 #include "kernels.h"
@@ -3051,6 +3052,138 @@ extern "C" int rdx_trace_paths_area(rdx_buffer tlas, rdx_buffer rays, size_t ray
                                  uint32_t* invalid) {
                                  launch_area_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, table, light_count, areaTable, area_count, io, live, d, sampleNext, cursor,
                                                    invalid); });
+}
+
+// ---- the environment: a lat-long image and the sampling table rdx_env_build derives from it (include/rdx.h; env.h, env.hip) ----
+namespace {
+int env_size_refused(const char* who, uint32_t width, uint32_t height)
+{
+    if (env_table_size(width, height)) return 0;
+    return fail("%s: an environment of %u x %u texels is outside the supported 1 .. %u x 1 .. %u", who, width, height, ENV_MAX_WIDTH, ENV_MAX_HEIGHT);
+}
+size_t env_image_bytes(uint32_t width, uint32_t height) { return (size_t)width * height * 4 * sizeof(float); }
+EnvView env_view(rdx_buffer image, size_t image_offset, rdx_buffer table, size_t table_offset, uint32_t width, uint32_t height)
+{
+    return EnvView{at<const float4>(image, image_offset), at<const char>(table, table_offset), width, height};
+}
+} // namespace
+
+extern "C" size_t rdx_env_table_size(uint32_t width, uint32_t height) { return env_table_size(width, height); }
+
+// The header and rowCos are computed here (cosines in double) and uploaded, the padding of the parts is zeroed, and the three
+// kernels follow in stream order: nothing comes back to the host before the table is complete
+extern "C" int rdx_env_build(rdx_buffer image, size_t image_offset, uint32_t width, uint32_t height, rdx_buffer table, size_t table_offset)
+{
+    const char* who = "rdx_env_build";
+    if (!g.initialized) return fail("rdx_env_build: rdx_init has not been called");
+    if (env_size_refused(who, width, height)) return -1;
+    const CallRange R[2] = {{image, image_offset, env_image_bytes(width, height), "environment-image", 16, true},
+                            {table, table_offset, env_table_size(width, height), "environment-table", 16, true}};
+    if (check_call_handles(who, R)) return -1;
+    if (check_call_ranges(who, R, 1, 1)) return -1;
+    std::vector<char> head(env_c_offset(height), 0);
+    EnvHeader hd{};
+    hd.magic = ENV_MAGIC; hd.version = ENV_VERSION; hd.width = width; hd.height = height;
+    const double pi = 3.14159265358979323846;
+    hd.twoPiOverW = (float)(2.0 * pi / (double)width);
+    hd.wOverTwoPi = (float)((double)width / (2.0 * pi));
+    std::memcpy(head.data(), &hd, sizeof hd);
+    float* rowCos = reinterpret_cast<float*>(head.data() + env_rowcos_offset());
+    for (uint32_t y = 0; y <= height; ++y) rowCos[y] = (float)std::cos(pi * (double)y / (double)height);
+    rowCos[0] = 1.0f; rowCos[height] = -1.0f;
+    char* dTable = at<char>(table, table_offset);
+    const size_t cEnd = env_c_offset(height) + (size_t)width * height * sizeof(uint32_t), mEnd = env_m_offset(width, height) + (size_t)height * sizeof(uint64_t);
+    return timed_launch(&rdx_trace_stats::ms_shade, {table}, [&] {
+        HIP_IGN(hipMemcpyAsync(dTable, head.data(), head.size(), hipMemcpyHostToDevice, g.stream));
+        if (env_m_offset(width, height) > cEnd) HIP_IGN(hipMemsetAsync(dTable + cEnd, 0, env_m_offset(width, height) - cEnd, g.stream));
+        if (env_table_size(width, height) > mEnd) HIP_IGN(hipMemsetAsync(dTable + mEnd, 0, env_table_size(width, height) - mEnd, g.stream));
+        launch_env_build(g.stream, at<const float4>(image, image_offset), dTable, width, height); });
+}
+
+// rdx_area_light_hits with the environment in the place of the one record (env.hip): light_hits around env_emit
+extern "C" int rdx_env_light_hits(rdx_buffer rays, size_t rays_offset, rdx_buffer materials, size_t materials_offset, uint32_t n, rdx_buffer image,
+                                  size_t image_offset, rdx_buffer table, size_t table_offset, uint32_t width, uint32_t height, rdx_buffer keys,
+                                  size_t keys_offset, uint32_t stream, rdx_buffer randoms, size_t randoms_offset, rdx_buffer lit, size_t lit_offset,
+                                  rdx_buffer shadow, size_t shadow_offset)
+{
+    const char* who = "rdx_env_light_hits";
+    if (!g.initialized) return fail("rdx_env_light_hits: rdx_init has not been called");
+    if (env_size_refused(who, width, height)) return -1;
+    // the first six are read, the others written
+    const CallRange R[8] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true},
+                            {materials, materials_offset, (size_t)n * sizeof(rdx_material_record), "material-record", 16, true},
+                            {image, image_offset, env_image_bytes(width, height), "environment-image", 16, true},
+                            {table, table_offset, env_table_size(width, height), "environment-table", 16, true},
+                            {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, false}, {randoms, randoms_offset, (size_t)n * 4 * sizeof(float), "randoms", 16, false},
+                            {lit, lit_offset, (size_t)n * 4 * sizeof(float), "lit", 16, true}, {shadow, shadow_offset, (size_t)n * sizeof(rdx_ray), "shadow-ray", 16, false}};
+    if (check_call_handles(who, R)) return -1;
+    if (!keys && !randoms) return fail("rdx_env_light_hits: neither keys nor randoms given: one of the two is required");
+    if (keys && randoms) return fail("rdx_env_light_hits: both keys and randoms given: only one of the two is allowed");
+    if (stream > 0xfffeu) return fail("rdx_env_light_hits: stream %u exceeds the supported maximum of 65534", stream);
+    if (check_call_ranges(who, R, 6, n)) return -1;
+    if (!n) return 0;
+    return timed_launch(&rdx_trace_stats::ms_shade, {lit, shadow}, [&] {
+        launch_env_light_hits(g.stream, at<const float4>(rays, rays_offset), at<const float4>(materials, materials_offset), n,
+                              env_view(image, image_offset, table, table_offset, width, height), at<const uint4>(keys, keys_offset), stream,
+                              at<const float4>(randoms, randoms_offset), at<float4>(lit, lit_offset), at<float4>(shadow, shadow_offset)); });
+}
+
+// the texel the environment shows along each ray's direction (env.hip): env_lookup per ray
+extern "C" int rdx_env_lookup(rdx_buffer rays, size_t rays_offset, uint32_t n, rdx_buffer image, size_t image_offset, rdx_buffer table, size_t table_offset,
+                              uint32_t width, uint32_t height, rdx_buffer radiance, size_t radiance_offset)
+{
+    const char* who = "rdx_env_lookup";
+    if (!g.initialized) return fail("rdx_env_lookup: rdx_init has not been called");
+    if (env_size_refused(who, width, height)) return -1;
+    const CallRange R[4] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true},
+                            {image, image_offset, env_image_bytes(width, height), "environment-image", 16, true},
+                            {table, table_offset, env_table_size(width, height), "environment-table", 16, true},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
+    if (check_call_handles(who, R)) return -1;
+    if (check_call_ranges(who, R, 3, n)) return -1;
+    if (!n) return 0;
+    return timed_launch(&rdx_trace_stats::ms_shade, {radiance}, [&] {
+        launch_env_lookup(g.stream, at<const float4>(rays, rays_offset), n, env_view(image, image_offset, table, table_offset, width, height),
+                          at<float4>(radiance, radiance_offset)); });
+}
+
+// rdx_trace_paths_area with the environment as one more record after the two tables (include/rdx.h; env.hip): the checks, then
+// trace_light_paths with k_env_shade over light_count + area_count + 1 records
+extern "C" int rdx_trace_paths_env(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n, uint32_t max_depth,
+                                   rdx_buffer lights, size_t lights_offset, uint32_t light_count, rdx_buffer area, size_t area_offset, uint32_t area_count,
+                                   rdx_buffer image, size_t image_offset, rdx_buffer table, size_t table_offset, uint32_t width, uint32_t height,
+                                   const rdx_shading_buffers* scene, rdx_buffer radiance, size_t radiance_offset, uint32_t* invalid_out)
+{
+    const char* who = "rdx_trace_paths_env";
+    if (!g.initialized) return fail("rdx_trace_paths_env: rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_env: invalid TLAS handle");
+    if (light_count >= MAX_PATH_LIGHTS || area_count >= MAX_PATH_LIGHTS || light_count + area_count + 1 > MAX_PATH_LIGHTS)
+        return fail("rdx_trace_paths_env: light_count %u + area_count %u + the environment exceeds the %u records a path samples (RDX_MAX_PATH_LIGHTS)", light_count,
+                    area_count, MAX_PATH_LIGHTS);
+    if (env_size_refused(who, width, height)) return -1;
+    const CallRange R[8] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
+                            {lights, lights_offset, (size_t)light_count * sizeof(PunctualLight), "light-table", 16, light_count != 0},
+                            {area, area_offset, (size_t)area_count * sizeof(AreaLight), "area-light-table", 16, area_count != 0},
+                            {image, image_offset, env_image_bytes(width, height), "environment-image", 16, true},
+                            {table, table_offset, env_table_size(width, height), "environment-table", 16, true},
+                            {scene ? scene->scene : nullptr, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, false},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths_env: depth %u exceeds the supported maximum of 62", max_depth);
+    if (check_call_ranges(who, R, 7, n, {invalid_out}, shading_aligned(scene))) return -1;
+    if (!n) return 0;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
+    // device addresses: read by the kernels of every call.  A table of no records is never read
+    const PunctualLight* lightTable = light_count ? at<const PunctualLight>(lights, lights_offset) : nullptr;
+    const AreaLight* areaTable = area_count ? at<const AreaLight>(area, area_offset) : nullptr;
+    const EnvView env = env_view(image, image_offset, table, table_offset, width, height);
+    return trace_light_paths(who, tlas, rays, rays_offset, keys, keys_offset, n, max_depth, light_count + area_count + 1, sc, radiance, radiance_offset, invalid_out,
+                             [&](hipStream_t st, const AccelCache& ac, const LightPathStreams& io, uint32_t live, uint32_t d, bool sampleNext, uint32_t* cursor,
+                                 uint32_t* invalid) {
+                                 launch_env_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, lightTable, light_count, areaTable, area_count, env, io, live, d, sampleNext,
+                                                  cursor, invalid); });
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,
