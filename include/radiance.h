@@ -380,6 +380,20 @@ inline uint32_t TraceEnvPaths(Platform*, TopAccelStruct accelStruct, Buffer rays
     return invalid;
 }
 
+// Extension (no reference counterpart; rdx_denoise_work_size, rdx_denoise): the frame's denoiser -- an edge-avoiding a-trous filter
+// over the width x height float4 colours in `color`, guided by the rdx_material_record / rdx_surface records of the same pixels'
+// primary hits; the result goes to `out` (float4 per pixel, w kept) and, tone-mapped as Accumulate does it, to `image` (RGBA8, may
+// be nullptr).  `work` holds DenoiseWorkSize(width, height) bytes (0: a size outside the limits) of no lasting meaning.
+inline size_t DenoiseWorkSize(uint32_t width, uint32_t height) { return rdx_denoise_work_size(width, height); }
+inline void Denoise(Platform*, Buffer color, Buffer materials, Buffer surfaces, uint32_t width, uint32_t height, const rdx_denoise_settings& settings,
+                    Buffer work, Buffer out, Image image = nullptr, size_t colorOffset = 0, size_t materialsOffset = 0, size_t surfacesOffset = 0,
+                    size_t workOffset = 0, size_t outOffset = 0, size_t imageOffset = 0)
+{
+    if (rdx_denoise(color, colorOffset, materials, materialsOffset, surfaces, surfacesOffset, width, height, &settings, work, workOffset, out, outOffset, image,
+                    imageOffset))
+        detail::fatal("Denoise");
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

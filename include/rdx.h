@@ -838,6 +838,60 @@ int         rdx_trace_paths_env(rdx_buffer tlas,
                                 rdx_buffer radiance, size_t radiance_offset,      /* out: float4 per path: rgb, w = 0 */
                                 uint32_t* invalid_out);                           /* optional */
 
+/* The frame's denoiser, on the device: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a width x height image
+ * of float4 colours -- what rdx_trace_paths and its kin write for the rays of rdx_generate_rays, pixel p = y * width + x -- guided
+ * by the rdx_material_record and the rdx_surface of the same pixels' primary hits (records the caller filled in are equally
+ * allowed).  valid(p) = materials[p].hit == 1 && surfaces[p].hit == 1; n = materials[p].normal, a = materials[p].albedo, P =
+ * surfaces[p].position.  Every float32 operation below is rounded on its own; dot is fma(z, z', fma(y, y', x x')).
+ * Prepare: den_k = DEMODULATE ? fmaxf(a_k, 0.015625f) : 1 (a NaN albedo gives 0.015625); i_0(p)_k = valid ? color[p]_k / den_k :
+ * color[p]_k.
+ * Pass j = 0 .. passes - 1, s = 1 << j, h = {1/16, 1/4, 3/8, 1/4, 1/16}: an invalid p keeps its iterate.  For a valid p, sum = 0,
+ * sumw = 0, and for dy = -2 .. 2, inside that dx = -2 .. 2, q = (x + dx s, y + dy s), skipped when outside the image or not valid:
+ *     k  = h[dy + 2] * h[dx + 2]
+ *     wn = fmaxf(dot(n(p), n(q)), 0), squared normal_squarings times
+ *     wz = sigma_position == 0 ? 1 : fmaxf(1 - fabsf(dot(n(p), P(q) - P(p))) / (sigma_position * (float)s), 0)
+ *     l(c) = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b of the current iterate; x = fabsf(l(p) - l(q)) / (sigma_colour * 2^-j)
+ *     wc = sigma_colour == 0 ? 1 : 1 / (1 + x * x)
+ *     w  = ((k * wn) * wz) * wc; the tap is skipped unless w > 0 and the three components of i_j(q) are finite
+ *     sum_k = sum_k + i_j(q)_k * w; sumw = sumw + w
+ * i_{j+1}(p) = sumw > 0 ? sum / sumw (one division per component) : i_j(p).
+ * Finish: out[p].rgb = valid ? i_passes(p)_k * den_k : color[p].rgb; out[p].w = color[p].w, its bits kept; image[p] (optional,
+ * RGBA8) is the tone map of rdx_accumulate on out[p].rgb, with RDX_DENOISE_DEBUG as its debug bit.  passes == 0 is prepare and
+ * finish alone.  A pixel's result depends on this order of taps only, not on how the work is cut into launches and blocks.
+ * `work` is rdx_denoise_work_size(width, height) bytes of the caller's (0 for a size outside 1 .. 16384 x 1 .. 16384 or above
+ * 2^26 pixels; at most 64 bytes per pixel); its contents before and after a call are unspecified.  Nothing is staged and nothing
+ * is allocated per call; the call blocks and runs on logical device 0 in multi-device mode.  rdx_get_trace_stats().ms_accumulate
+ * is the kernel time of the call.  Refused, before anything is launched: an uninitialised library; a NULL or unknown handle among
+ * color / materials / surfaces / work / out, an unknown `image`; `settings` NULL, passes > 8, normal_squarings > 7, a sigma that
+ * is negative, infinite or a NaN, non-zero padding, unknown flag bits; a size outside the limits; an offset that is not a
+ * multiple of 16 (4 for `image`); a range that does not hold width x height records (16 per pixel for color / out, 64 for
+ * materials / surfaces, 4 for image, the work size); `work`, `out` or `image` overlapping an input range or each other; wrapped
+ * memory that is misaligned.  width == 0 or height == 0 succeeds and touches nothing.
+ * Not covered: temporal accumulation, a variance guide, guides beyond the primary hit (a reflection is filtered as the surface it
+ * appears on); sigma_position is in the caller's world units. */
+#define RDX_DENOISE_DEMODULATE 1u   /* divide by the clamped albedo before the passes, multiply it back after them */
+#define RDX_DENOISE_DEBUG      2u   /* the tone map's RTProp.debug: no ACES, no gamma */
+typedef struct rdx_denoise_settings {      /* 32 B */
+    uint32_t passes;             /* 0 .. 8: pass j uses step 1 << j; 0 copies */
+    uint32_t normal_squarings;   /* 0 .. 7: normal weight = max(n.n', 0) squared this many times (5 -> power 32) */
+    float    sigma_position;     /* world units of plane distance at step 1; 0 = term off; otherwise finite and > 0 */
+    float    sigma_colour;       /* luminance units at pass 0, halved every pass; 0 = term off; otherwise finite and > 0 */
+    uint32_t flags;              /* bit 0 RDX_DENOISE_DEMODULATE, bit 1 RDX_DENOISE_DEBUG (tone map: RTProp.debug) */
+    uint32_t _0[3];              /* must be 0 */
+} rdx_denoise_settings;
+size_t      rdx_denoise_work_size(uint32_t width, uint32_t height);
+int         rdx_denoise(rdx_buffer color, size_t color_offset,           /* float4 per pixel, row-major, rgb + w */
+                        rdx_buffer materials, size_t materials_offset,   /* rdx_material_record per pixel */
+                        rdx_buffer surfaces, size_t surfaces_offset,     /* rdx_surface per pixel */
+                        uint32_t width, uint32_t height, const rdx_denoise_settings* settings,
+                        rdx_buffer work, size_t work_offset,             /* rdx_denoise_work_size bytes; contents before and after unspecified */
+                        rdx_buffer out, size_t out_offset,               /* float4 per pixel */
+                        rdx_buffer image, size_t image_offset);          /* optional RGBA8 per pixel */
+/* Test and measurement seam: bit j of `mask` (j = 0, 1: steps 1 and 2) makes that pass of every later rdx_denoise take its taps from
+ * an LDS tile of the block's pixels and their halo, a clear bit straight from memory.  Both forms give the same bits; the default
+ * is 3, the faster form of both steps. */
+void        rdx_debug_denoise_tiled(uint32_t mask);
+
 /* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_env applies to the byte ranges it is given, on plain
  * numbers (needs no device and no initialised library; no address is dereferenced) -> 0, or -1 with the refusal in
  * rdx_last_error().  A row is one range: `bytes` at `offset` of a buffer of `size` bytes at `address`; `align` (a power of two)

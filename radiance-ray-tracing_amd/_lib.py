@@ -114,6 +114,11 @@ class rdx_scatter(C.Structure):
     _fields_ = [("nextFactor", C.c_float * 3), ("slot", C.c_uint32)]
 
 
+class rdx_denoise_settings(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_position", C.c_float), ("sigma_colour", C.c_float),
+                ("flags", C.c_uint32), ("_0", C.c_uint32 * 3)]
+
+
 class rdx_shading_buffers(C.Structure):
     _fields_ = [("scene", C.c_void_p), ("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p),
                 ("material", C.c_void_p), ("textureArray", C.c_void_p), ("sampler", C.c_void_p)]
@@ -218,6 +223,10 @@ SIGNATURES = {
     "rdx_trace_paths_env": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
                                       C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
                                       C.c_uint32, C.POINTER(rdx_shading_buffers), C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "rdx_denoise_work_size": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rdx_denoise": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(rdx_denoise_settings),
+                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rdx_debug_denoise_tiled": (None, [C.c_uint32]),
     "rdx_debug_check_ranges": (C.c_int, [C.POINTER(rdx_debug_range), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),

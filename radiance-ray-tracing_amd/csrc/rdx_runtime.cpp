@@ -37,6 +37,7 @@
 #include "area.h"
 #include "env.h"
 #include "bvh_build.h"
+#include "denoise.h"
 #include "device_math.h"
 #include "kernels.h"
 #include "light_paths.h"
@@ -3184,6 +3185,56 @@ extern "C" int rdx_trace_paths_env(rdx_buffer tlas, rdx_buffer rays, size_t rays
                                  uint32_t* invalid) {
                                  launch_env_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, lightTable, light_count, areaTable, area_count, env, io, live, d, sampleNext,
                                                   cursor, invalid); });
+}
+
+// ---- the edge-avoiding a-trous filter over a frame's colours (denoise.hip) ---------------------------------------------
+namespace {
+uint32_t g_denoiseTiled = 3;        // rdx_debug_denoise_tiled: steps 1 and 2 from the LDS tile, the faster form of both
+}
+
+extern "C" size_t rdx_denoise_work_size(uint32_t width, uint32_t height) { return denoise_work_size(width, height); }
+
+// Test and measurement seam: bit j set = pass j (j < 2: steps 1 and 2) of every later rdx_denoise takes its taps from an LDS tile,
+// clear = straight from memory.  Both forms give the same bits; the default, 3, is what was measured faster
+extern "C" void rdx_debug_denoise_tiled(uint32_t mask) { g_denoiseTiled = mask & 3u; }
+
+extern "C" int rdx_denoise(rdx_buffer color, size_t color_offset, rdx_buffer materials, size_t materials_offset, rdx_buffer surfaces, size_t surfaces_offset,
+                           uint32_t width, uint32_t height, const rdx_denoise_settings* settings, rdx_buffer work, size_t work_offset, rdx_buffer out,
+                           size_t out_offset, rdx_buffer image, size_t image_offset)
+{
+    const char* who = "rdx_denoise";
+    if (!g.initialized) return fail("rdx_denoise: rdx_init has not been called");
+    static_assert(sizeof(rdx_denoise_settings) == 32 && sizeof(rdx_material_record) == 64 && sizeof(rdx_surface) == 64, "the records of rdx_denoise");
+    const bool empty = !width || !height;
+    const size_t npix = empty ? 0 : (size_t)width * height;
+    // a size outside the limits is refused below, before the table is consulted: until then the byte counts only have to exist
+    const size_t rows = npix <= DENOISE_MAX_PIXELS ? npix : 0;
+    const CallRange R[6] = {{color, color_offset, rows * sizeof(float4), "colour", 16, true},
+                            {materials, materials_offset, rows * sizeof(rdx_material_record), "material-record", 16, true},
+                            {surfaces, surfaces_offset, rows * sizeof(rdx_surface), "surface-record", 16, true},
+                            {work, work_offset, empty ? 0 : denoise_work_size(width, height), "work", 16, true},
+                            {out, out_offset, rows * sizeof(float4), "output", 16, true}, {image, image_offset, rows * 4, "image", 4, false}};
+    if (check_call_handles(who, R)) return -1;
+    if (!settings) return fail("rdx_denoise: no settings");
+    if (settings->passes > DENOISE_MAX_PASSES) return fail("rdx_denoise: %u passes exceed the supported maximum of %u", settings->passes, DENOISE_MAX_PASSES);
+    if (settings->normal_squarings > DENOISE_MAX_SQUARINGS)
+        return fail("rdx_denoise: normal_squarings %u exceeds the supported maximum of %u", settings->normal_squarings, DENOISE_MAX_SQUARINGS);
+    if (!(settings->sigma_position >= 0.0f && settings->sigma_position < HUGE_VALF))
+        return fail("rdx_denoise: sigma_position must be 0 (the term is off) or finite and positive, not %g", (double)settings->sigma_position);
+    if (!(settings->sigma_colour >= 0.0f && settings->sigma_colour < HUGE_VALF))
+        return fail("rdx_denoise: sigma_colour must be 0 (the term is off) or finite and positive, not %g", (double)settings->sigma_colour);
+    if (settings->flags & ~(RDX_DENOISE_DEMODULATE | RDX_DENOISE_DEBUG))
+        return fail("rdx_denoise: unknown flags 0x%x (bit 0 = demodulate, bit 1 = debug)", settings->flags);
+    if (settings->_0[0] | settings->_0[1] | settings->_0[2]) return fail("rdx_denoise: the padding of the settings must be 0");
+    if (!empty && !denoise_work_size(width, height))
+        return fail("rdx_denoise: an image of %u x %u pixels is outside the supported 1 .. %u x 1 .. %u and 2^26 pixels", width, height, DENOISE_MAX_DIM,
+                    DENOISE_MAX_DIM);
+    if (check_call_ranges(who, R, 3, (uint32_t)npix)) return -1;
+    if (empty) return 0;
+    const DenoiseArgs a{width, height, settings->passes, settings->normal_squarings, settings->flags, settings->sigma_position, settings->sigma_colour, g_denoiseTiled};
+    return timed_launch(&rdx_trace_stats::ms_accumulate, {work, out, image}, [&] {
+        launch_denoise(g.stream, a, at<const float4>(color, color_offset), at<const float4>(materials, materials_offset), at<const float4>(surfaces, surfaces_offset),
+                       at<float4>(work, work_offset), at<float4>(out, out_offset), at<uchar4>(image, image_offset)); });
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,
