@@ -394,6 +394,30 @@ inline void Denoise(Platform*, Buffer color, Buffer materials, Buffer surfaces, 
         detail::fatal("Denoise");
 }
 
+// Extension (no reference counterpart; rdx_camera_view, rdx_temporal_history_size, rdx_temporal_accumulate): temporal accumulation --
+// CameraView writes the rdx_view of the PhysicalCamera in `camera` (as GenerateRays reads it) to `view`; TemporalAccumulate carries
+// `historyIn` (may be nullptr: a history starts) through `previousView` (nullptr: the camera did not move) to the camera of `view`,
+// folds the width x height float4 colours in `color` into it and writes `historyOut`: TemporalHistorySize(width, height) bytes, four
+// planes of one float4 per pixel, of which plane 0 -- at historyOutOffset -- is what Denoise takes as `color`.  `previousPositions`
+// (float4 per pixel, may be nullptr) says where each pixel's surface point was one frame ago; `image` (RGBA8, may be nullptr) is
+// plane 0 tone-mapped as Accumulate does it.
+inline void CameraView(Platform*, Buffer camera, Buffer view, size_t viewOffset = 0)
+{
+    if (rdx_camera_view(camera, view, viewOffset)) detail::fatal("CameraView");
+}
+inline size_t TemporalHistorySize(uint32_t width, uint32_t height) { return rdx_temporal_history_size(width, height); }
+inline void TemporalAccumulate(Platform*, Buffer color, Buffer materials, Buffer surfaces, Buffer view, uint32_t width, uint32_t height,
+                               const rdx_temporal_settings& settings, Buffer historyIn, Buffer historyOut, Buffer previousView = nullptr,
+                               Buffer previousPositions = nullptr, Image image = nullptr, size_t colorOffset = 0, size_t materialsOffset = 0,
+                               size_t surfacesOffset = 0, size_t viewOffset = 0, size_t historyInOffset = 0, size_t historyOutOffset = 0,
+                               size_t previousViewOffset = 0, size_t previousPositionsOffset = 0, size_t imageOffset = 0)
+{
+    if (rdx_temporal_accumulate(color, colorOffset, materials, materialsOffset, surfaces, surfacesOffset, previousPositions, previousPositionsOffset, view,
+                                viewOffset, previousView, previousViewOffset, width, height, &settings, historyIn, historyInOffset, historyOut,
+                                historyOutOffset, image, imageOffset))
+        detail::fatal("TemporalAccumulate");
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

@@ -867,7 +867,8 @@ int         rdx_trace_paths_env(rdx_buffer tlas,
  * multiple of 16 (4 for `image`); a range that does not hold width x height records (16 per pixel for color / out, 64 for
  * materials / surfaces, 4 for image, the work size); `work`, `out` or `image` overlapping an input range or each other; wrapped
  * memory that is misaligned.  width == 0 or height == 0 succeeds and touches nothing.
- * Not covered: temporal accumulation, a variance guide, guides beyond the primary hit (a reflection is filtered as the surface it
+ * Not covered: a variance guide (rdx_temporal_accumulate below accumulates over frames and estimates the variance; the passes
+ * here do not read it yet), guides beyond the primary hit (a reflection is filtered as the surface it
  * appears on); sigma_position is in the caller's world units. */
 #define RDX_DENOISE_DEMODULATE 1u   /* divide by the clamped albedo before the passes, multiply it back after them */
 #define RDX_DENOISE_DEBUG      2u   /* the tone map's RTProp.debug: no ACES, no gamma */
@@ -891,6 +892,104 @@ int         rdx_denoise(rdx_buffer color, size_t color_offset,           /* floa
  * an LDS tile of the block's pixels and their halo, a clear bit straight from memory.  Both forms give the same bits; the default
  * is 3, the faster form of both steps. */
 void        rdx_debug_denoise_tiled(uint32_t mask);
+
+/* Temporal accumulation, on the device: the temporal half of SVGF (Schied et al. 2017).  A frame's history is carried to the current
+ * camera through the previous view, its taps are tested against the history's own guide, and colour and the first two luminance
+ * moments are folded into exponential means with a per-pixel variance estimate.  Every float32 operation below is rounded on its
+ * own; dot is fma(z, z', fma(y, y', x x')); divisions are IEEE divisions; no transcendental is evaluated per pixel.
+ *
+ * rdx_camera_view writes the rdx_view of `camera`, the PhysicalCamera buffer exactly as rdx_generate_rays reads it (its current
+ * contents, on the device).  With c* = cosf, s* = sinf of wx, wy, wz (the OCML functions of rdx_generate_rays) and the row-major
+ *     RotX = {1, 0, 0;  0, cx, -sx;  0, sx, cx}   RotY = {cy, 0, sy;  0, 1, 0;  -sy, 0, cy}   RotZ = {cz, -sz, 0;  sz, cz, 0;  0, 0, 1}
+ * M = RotX (RotY RotZ): first T = RotY RotZ, then M = RotX T, every element of a product (a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j.
+ * right, up and back are the columns 0, 1, 2 of M (the camera looks along -back); kx = focalLength / sensorWidth; ky =
+ * focalLength / (sensorWidth * (heightPixel / widthPixel)).  The record is plain data: a caller with a camera of their own fills
+ * it directly.  Refused: an uninitialised library; a NULL or unknown handle; a camera buffer below 48 bytes; view_offset no
+ * multiple of 16; a view range that does not hold 64 bytes or overlaps the camera.  rdx_get_trace_stats().ms_generate is its time.
+ * The sample-space position of a world point Q under a view V:
+ *     v  = Q - V.eye
+ *     dz = -dot(V.back, v);                     Q is in front of the camera iff dz > 0
+ *     u  = V.width * 0.5f + (V.width * V.kx) * (dot(V.right, v) / dz)
+ *     t  = V.height * 0.5f - (V.height * V.ky) * (dot(V.up, v) / dz)
+ * the inverse of the ray of rdx_generate_rays for fStop == 0: the point origin + s direction of the ray of pixel (x, y) with jitter
+ * rnd lands at u = x + rnd.x, t = y + rnd.y up to rounding.  The thin lens (fStop != 0) is NOT inverted: its rays start on the
+ * lens, and a point off the focal plane projects to the centre of its circle of confusion.
+ *
+ * rdx_temporal_accumulate, per pixel p = y * width + x.  valid(p) = materials[p].hit == 1 && surfaces[p].hit == 1 (the rule of
+ * rdx_denoise); n = materials[p].normal, mi = materials[p].materialIndex, P = surfaces[p].position, c = color[p].rgb.
+ * A history is four planes of width x height float4, rdx_temporal_history_size(width, height) = 64 width height bytes (0 for a
+ * size outside 1 .. 16384 x 1 .. 16384 or above 2^26 pixels):
+ *     plane 0  c'.rgb | w: the bits of color[p].w        (rdx_denoise takes it as `color` at the history's offset, without a copy)
+ *     plane 1  m1 | m2 | variance | N                    (N: the history length, a uint32)
+ *     plane 2  n.xyz | mi
+ *     plane 3  P.xyz | valid                             (1u or 0u)
+ * 1. An invalid p writes color[p]'s bits to plane 0, zeros and N = 0 to plane 1, n | mi and P | 0 to planes 2 and 3, and is no
+ *    one's tap, now or in the next frame.
+ * 2. Q = previous_positions ? previous_positions[p].xyz : P: where this surface point was one frame ago.
+ * 3. du = u(previous_view, Q) - u(view, P); dt = t(previous_view, Q) - t(view, P); the history position is hx = (float)x + du, hy =
+ *    (float)y + dt in texel units.  Sign convention: a camera that moved by one pixel's width along +right finds pixel (x, y)'s
+ *    history at (x + 1, y).  Subtracting the current view's own projection removes the sub-pixel jitter; with bit-equal views and
+ *    Q = P the motion is exactly +0 and the history position exactly the pixel.
+ * 4. x0 = floorf(hx), fx = hx - x0, wx = {1 - fx, fx}; likewise y0, fy, wy.  Taps (x0 + i, y0 + j), j = 0, 1 outer, i = 0, 1 inner,
+ *    weight w = wx[i] * wy[j].  A tap q counts iff it lies inside the image, history_in is given, q's valid == 1 and N >= 1, q's mi
+ *    equals mi, dot(n, n(q)) >= normal_cos_min, position_tolerance == 0 or fabsf(dot(n, P(q) - Q)) <= position_tolerance, w > 0
+ *    and the three components of q's colour are finite (a comparison with a NaN fails).  For a counted tap sum_k = sum_k + h(q)_k * w,
+ *    s1 = s1 + m1(q) * w, s2 = s2 + m2(q) * w, sumw = sumw + w, Nh = min(Nh, N(q)).  dz <= 0 under either view, or a du or dt that
+ *    is not finite: no tap counts.
+ * 5. l = (0.2126f * c.r + 0.7152f * c.g) + 0.0722f * c.b.  With sumw > 0: h = sum / sumw, m1h = s1 / sumw, m2h = s2 / sumw (one
+ *    division each); N' = min(Nh + 1, max_history) (no wrap); a = fmaxf(1.0f / (float)N', alpha_min), am = fmaxf(1.0f / (float)N',
+ *    alpha_moments_min); c'_k = h_k + (c_k - h_k) * a; m1' = m1h + (l - m1h) * am; m2' = m2h + (l * l - m2h) * am.
+ *    Without: N' = 1, c' = c, m1' = l, m2' = l * l.
+ *    A c with a component that is not finite: with history c' = h, m1' = m1h, m2' = m2h, N' = Nh (the history is kept as it is);
+ *    without, c' = c's bits, m1' = m2' = 0 and N' = 0, so that it is no one's tap.
+ * 6. variance = fmaxf(m2' - m1' * m1', 0) where N' >= variance_min_history.  Elsewhere, in a second launch over the new history:
+ *    s1 = s2 = sumw = 0, and for dy = -3 .. 3, inside that dx = -3 .. 3, q = (x + dx, y + dy) inside the image with N'(q) >= 1 and
+ *    mi(q) == mi: w = fmaxf(dot(n, n(q)), 0), skipped unless w > 0 and w, m1'(q), m2'(q) are finite; s1 = s1 + m1'(q) * w; s2 = s2 +
+ *    m2'(q) * w; sumw = sumw + w.  M1 = sumw > 0 ? s1 / sumw : m1', M2 likewise; variance = fmaxf(M2 - M1 * M1, 0) *
+ *    ((float)variance_min_history / (float)max(N', 1)): SVGF's boost for young pixels.
+ * 7. image[p] (optional, RGBA8) is the tone map of rdx_accumulate on plane 0's rgb, with RDX_TEMPORAL_DEBUG as its debug bit.
+ * previous_view NULL is `view`; history_in NULL starts a history (N' = 1 on every valid pixel).  Nothing is staged and nothing is
+ * allocated per call; the call blocks and runs on logical device 0 in multi-device mode.  rdx_get_trace_stats().ms_accumulate is
+ * the kernel time of the call.  Refused, before anything is launched: an uninitialised library; a NULL or unknown handle among
+ * color / materials / surfaces / view / history_out, an unknown one among the optional four; `settings` NULL, max_history outside
+ * 1 .. 65535, alpha_min or alpha_moments_min outside [0, 1] or a NaN, a normal_cos_min that is not finite, a position_tolerance
+ * that is negative, infinite or a NaN, variance_min_history above 255, unknown flag bits, non-zero padding; a size outside the
+ * limits; an offset that is not a multiple of 16 (4 for `image`); a range that does not hold its records (16 bytes per pixel for
+ * color / previous_positions, 64 for materials / surfaces, 64 for a view, the history size, 4 per pixel for image); history_out or
+ * image overlapping any input -- history_in included -- or each other; wrapped memory that is misaligned.  width == 0 or height == 0
+ * succeeds and touches nothing.
+ * Not covered: the variance guide inside rdx_denoise's passes (plane 1 is its input), a wider search when all four taps fail,
+ * albedo demodulation of the history (a caller may pass demodulated colours), the thin lens, anything beyond the primary hit. */
+#define RDX_TEMPORAL_DEBUG 1u       /* the tone map's RTProp.debug: no ACES, no gamma */
+typedef struct rdx_view {                  /* 64 B: four float4 */
+    float eye[3],   widthPixel;
+    float right[3], heightPixel;
+    float up[3],    kx;
+    float back[3],  ky;
+} rdx_view;
+typedef struct rdx_temporal_settings {     /* 32 B */
+    uint32_t max_history;            /* 1 .. 65535: N saturates here, so alpha never falls below 1 / max_history */
+    float    alpha_min;              /* 0 .. 1: the least weight of the current colour */
+    float    alpha_moments_min;      /* 0 .. 1: the same for the two luminance moments */
+    float    normal_cos_min;         /* finite: a tap counts if dot(n, n') >= this */
+    float    position_tolerance;     /* world units of plane distance; 0 = term off; otherwise finite and > 0 */
+    uint32_t variance_min_history;   /* 0 .. 255: below this N the variance is the 7 x 7 spatial estimate (SVGF: 4); 0 = never */
+    uint32_t flags;                  /* bit 0 RDX_TEMPORAL_DEBUG */
+    uint32_t _0;                     /* must be 0 */
+} rdx_temporal_settings;
+int         rdx_camera_view(rdx_buffer camera,                                  /* PhysicalCamera, as for rdx_generate_rays */
+                            rdx_buffer view, size_t view_offset);               /* out: one rdx_view */
+size_t      rdx_temporal_history_size(uint32_t width, uint32_t height);
+int         rdx_temporal_accumulate(rdx_buffer color, size_t color_offset,                         /* float4 per pixel, row-major, rgb + w */
+                                    rdx_buffer materials, size_t materials_offset,                 /* rdx_material_record per pixel */
+                                    rdx_buffer surfaces, size_t surfaces_offset,                   /* rdx_surface per pixel */
+                                    rdx_buffer previous_positions, size_t previous_positions_offset,   /* optional float4 per pixel */
+                                    rdx_buffer view, size_t view_offset,                           /* rdx_view */
+                                    rdx_buffer previous_view, size_t previous_view_offset,         /* optional rdx_view; NULL = view */
+                                    uint32_t width, uint32_t height, const rdx_temporal_settings* settings,
+                                    rdx_buffer history_in, size_t history_in_offset,               /* optional: the previous frame's history_out */
+                                    rdx_buffer history_out, size_t history_out_offset,             /* rdx_temporal_history_size bytes */
+                                    rdx_buffer image, size_t image_offset);                        /* optional RGBA8 per pixel */
 
 /* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_env applies to the byte ranges it is given, on plain
  * numbers (needs no device and no initialised library; no address is dereferenced) -> 0, or -1 with the refusal in

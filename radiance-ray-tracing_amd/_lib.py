@@ -119,6 +119,16 @@ class rdx_denoise_settings(C.Structure):
                 ("flags", C.c_uint32), ("_0", C.c_uint32 * 3)]
 
 
+class rdx_view(C.Structure):
+    _fields_ = [("eye", C.c_float * 3), ("widthPixel", C.c_float), ("right", C.c_float * 3), ("heightPixel", C.c_float),
+                ("up", C.c_float * 3), ("kx", C.c_float), ("back", C.c_float * 3), ("ky", C.c_float)]
+
+
+class rdx_temporal_settings(C.Structure):
+    _fields_ = [("max_history", C.c_uint32), ("alpha_min", C.c_float), ("alpha_moments_min", C.c_float), ("normal_cos_min", C.c_float),
+                ("position_tolerance", C.c_float), ("variance_min_history", C.c_uint32), ("flags", C.c_uint32), ("_0", C.c_uint32)]
+
+
 class rdx_shading_buffers(C.Structure):
     _fields_ = [("scene", C.c_void_p), ("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p),
                 ("material", C.c_void_p), ("textureArray", C.c_void_p), ("sampler", C.c_void_p)]
@@ -227,6 +237,11 @@ SIGNATURES = {
     "rdx_denoise": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(rdx_denoise_settings),
                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "rdx_debug_denoise_tiled": (None, [C.c_uint32]),
+    "rdx_camera_view": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "rdx_temporal_history_size": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rdx_temporal_accumulate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(rdx_temporal_settings), C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "rdx_debug_check_ranges": (C.c_int, [C.POINTER(rdx_debug_range), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),

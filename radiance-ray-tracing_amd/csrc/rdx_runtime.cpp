@@ -38,6 +38,7 @@
 #include "env.h"
 #include "bvh_build.h"
 #include "denoise.h"
+#include "temporal.h"
 #include "device_math.h"
 #include "kernels.h"
 #include "light_paths.h"
@@ -3235,6 +3236,77 @@ extern "C" int rdx_denoise(rdx_buffer color, size_t color_offset, rdx_buffer mat
     return timed_launch(&rdx_trace_stats::ms_accumulate, {work, out, image}, [&] {
         launch_denoise(g.stream, a, at<const float4>(color, color_offset), at<const float4>(materials, materials_offset), at<const float4>(surfaces, surfaces_offset),
                        at<float4>(work, work_offset), at<float4>(out, out_offset), at<uchar4>(image, image_offset)); });
+}
+
+// ---- temporal accumulation: a frame's history reprojected through the previous view (temporal.hip) -------------------
+extern "C" size_t rdx_temporal_history_size(uint32_t width, uint32_t height) { return temporal_history_size(width, height); }
+
+extern "C" int rdx_camera_view(rdx_buffer camera, rdx_buffer view, size_t view_offset)
+{
+    const char* who = "rdx_camera_view";
+    if (!g.initialized) return fail("rdx_camera_view: rdx_init has not been called");
+    static_assert(sizeof(rdx_view) == 64, "four float4 per view");
+    const CallRange R[2] = {{camera, 0, sizeof(PhysicalCamera), "camera", 4, true}, {view, view_offset, sizeof(rdx_view), "view", 16, true}};
+    if (check_call_handles(who, R)) return -1;
+    if (camera->size < sizeof(PhysicalCamera))
+        return fail("rdx_camera_view: the camera buffer (%zu bytes) does not hold a PhysicalCamera (%zu bytes)", camera->size, sizeof(PhysicalCamera));
+    if (check_call_ranges(who, R, 1, 1)) return -1;
+    return timed_launch(&rdx_trace_stats::ms_generate, {view}, [&] {
+        launch_camera_view(g.stream, at<const PhysicalCamera>(camera), at<float4>(view, view_offset)); });
+}
+
+extern "C" int rdx_temporal_accumulate(rdx_buffer color, size_t color_offset, rdx_buffer materials, size_t materials_offset, rdx_buffer surfaces,
+                                       size_t surfaces_offset, rdx_buffer previous_positions, size_t previous_positions_offset, rdx_buffer view,
+                                       size_t view_offset, rdx_buffer previous_view, size_t previous_view_offset, uint32_t width, uint32_t height,
+                                       const rdx_temporal_settings* settings, rdx_buffer history_in, size_t history_in_offset, rdx_buffer history_out,
+                                       size_t history_out_offset, rdx_buffer image, size_t image_offset)
+{
+    const char* who = "rdx_temporal_accumulate";
+    if (!g.initialized) return fail("rdx_temporal_accumulate: rdx_init has not been called");
+    static_assert(sizeof(rdx_temporal_settings) == 32 && sizeof(rdx_view) == 64, "the records of rdx_temporal_accumulate");
+    const bool empty = !width || !height;
+    const size_t npix = empty ? 0 : (size_t)width * height;
+    // a size outside the limits is refused below, before the table is consulted: until then the byte counts only have to exist
+    const size_t rows = npix <= TEMPORAL_MAX_PIXELS ? npix : 0;
+    const size_t history = empty ? 0 : temporal_history_size(width, height);
+    const CallRange R[9] = {{color, color_offset, rows * sizeof(float4), "colour", 16, true},
+                            {materials, materials_offset, rows * sizeof(rdx_material_record), "material-record", 16, true},
+                            {surfaces, surfaces_offset, rows * sizeof(rdx_surface), "surface-record", 16, true},
+                            {previous_positions, previous_positions_offset, rows * sizeof(float4), "previous-position", 16, false},
+                            {view, view_offset, empty ? 0 : sizeof(rdx_view), "view", 16, true},
+                            {previous_view, previous_view_offset, empty ? 0 : sizeof(rdx_view), "previous-view", 16, false},
+                            {history_in, history_in_offset, history, "history-in", 16, false},
+                            {history_out, history_out_offset, history, "history-out", 16, true},
+                            {image, image_offset, rows * 4, "image", 4, false}};
+    if (check_call_handles(who, R)) return -1;
+    if (!settings) return fail("rdx_temporal_accumulate: no settings");
+    const rdx_temporal_settings& s = *settings;
+    if (s.max_history < 1u || s.max_history > TEMPORAL_MAX_HISTORY)
+        return fail("rdx_temporal_accumulate: max_history %u is outside 1 .. %u", s.max_history, TEMPORAL_MAX_HISTORY);
+    if (!(s.alpha_min >= 0.0f && s.alpha_min <= 1.0f)) return fail("rdx_temporal_accumulate: alpha_min must lie in [0, 1], not %g", (double)s.alpha_min);
+    if (!(s.alpha_moments_min >= 0.0f && s.alpha_moments_min <= 1.0f))
+        return fail("rdx_temporal_accumulate: alpha_moments_min must lie in [0, 1], not %g", (double)s.alpha_moments_min);
+    if (!(std::fabs(s.normal_cos_min) < HUGE_VALF)) return fail("rdx_temporal_accumulate: normal_cos_min must be finite, not %g", (double)s.normal_cos_min);
+    if (!(s.position_tolerance >= 0.0f && s.position_tolerance < HUGE_VALF))
+        return fail("rdx_temporal_accumulate: position_tolerance must be 0 (the term is off) or finite and positive, not %g", (double)s.position_tolerance);
+    if (s.variance_min_history > TEMPORAL_MAX_VARIANCE_HISTORY)
+        return fail("rdx_temporal_accumulate: variance_min_history %u exceeds the supported maximum of %u", s.variance_min_history, TEMPORAL_MAX_VARIANCE_HISTORY);
+    if (s.flags & ~RDX_TEMPORAL_DEBUG) return fail("rdx_temporal_accumulate: unknown flags 0x%x (bit 0 = debug)", s.flags);
+    if (s._0) return fail("rdx_temporal_accumulate: the padding of the settings must be 0");
+    if (!empty && !history)
+        return fail("rdx_temporal_accumulate: an image of %u x %u pixels is outside the supported 1 .. %u x 1 .. %u and 2^26 pixels", width, height,
+                    TEMPORAL_MAX_DIM, TEMPORAL_MAX_DIM);
+    if (check_call_ranges(who, R, 7, (uint32_t)npix)) return -1;
+    if (empty) return 0;
+    TemporalArgs a{width, height, s.max_history, s.variance_min_history, s.flags & TEMPORAL_DEBUG, s.alpha_min, s.alpha_moments_min, s.normal_cos_min,
+                   s.position_tolerance};
+    if (s.position_tolerance != 0.0f) a.flags |= TEMPORAL_POSITION;
+    const float4* v = at<const float4>(view, view_offset);
+    return timed_launch(&rdx_trace_stats::ms_accumulate, {history_out, image}, [&] {
+        launch_temporal_accumulate(g.stream, a, at<const float4>(color, color_offset), at<const float4>(materials, materials_offset),
+                                   at<const float4>(surfaces, surfaces_offset), at<const float4>(previous_positions, previous_positions_offset), v,
+                                   previous_view ? at<const float4>(previous_view, previous_view_offset) : v, at<const float4>(history_in, history_in_offset),
+                                   at<float4>(history_out, history_out_offset), at<uchar4>(image, image_offset)); });
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,
