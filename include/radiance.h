@@ -418,6 +418,24 @@ inline void TemporalAccumulate(Platform*, Buffer color, Buffer materials, Buffer
         detail::fatal("TemporalAccumulate");
 }
 
+// Extension (no reference counterpart; rdx_svgf_work_size, rdx_svgf_filter): the variance-guided a-trous filter of SVGF -- Denoise's
+// passes with a luminance weight in units of the local standard deviation.  `color` and `moments` are typically planes 0 and 1 of a
+// history TemporalAccumulate wrote: the same Buffer at colorOffset = the history's offset and momentsOffset = that + 16 width height.
+// The result goes to `out` (float4 per pixel, w kept), the filtered variance to `varianceOut` (one float per pixel, may be nullptr),
+// the iterate after settings.feedback_pass passes to `feedback` (float4 per pixel; given iff feedback_pass != 0: what the caller
+// copies into plane 0 for the next frame) and, tone-mapped as Accumulate does it, to `image` (RGBA8, may be nullptr).  `work` holds
+// SvgfWorkSize(width, height) bytes (0: a size outside the limits) of no lasting meaning.
+inline size_t SvgfWorkSize(uint32_t width, uint32_t height) { return rdx_svgf_work_size(width, height); }
+inline void SvgfFilter(Platform*, Buffer color, Buffer moments, Buffer materials, Buffer surfaces, uint32_t width, uint32_t height,
+                       const rdx_svgf_settings& settings, Buffer work, Buffer out, Buffer varianceOut = nullptr, Buffer feedback = nullptr, Image image = nullptr,
+                       size_t colorOffset = 0, size_t momentsOffset = 0, size_t materialsOffset = 0, size_t surfacesOffset = 0, size_t workOffset = 0,
+                       size_t outOffset = 0, size_t varianceOutOffset = 0, size_t feedbackOffset = 0, size_t imageOffset = 0)
+{
+    if (rdx_svgf_filter(color, colorOffset, moments, momentsOffset, materials, materialsOffset, surfaces, surfacesOffset, width, height, &settings, work,
+                        workOffset, out, outOffset, varianceOut, varianceOutOffset, feedback, feedbackOffset, image, imageOffset))
+        detail::fatal("SvgfFilter");
+}
+
 // ---- resources ----------------------------------------------------------------------------------------
 inline Buffer CreateBuffer(Platform*, unsigned int size) { return detail::need(rdx_buffer_create(size), "CreateBuffer"); }
 inline Image CreateImage(Platform*, unsigned int width, unsigned int height) { return detail::need(rdx_buffer_create((size_t)width * height * CHANNEL), "CreateImage"); }

@@ -867,9 +867,9 @@ int         rdx_trace_paths_env(rdx_buffer tlas,
  * multiple of 16 (4 for `image`); a range that does not hold width x height records (16 per pixel for color / out, 64 for
  * materials / surfaces, 4 for image, the work size); `work`, `out` or `image` overlapping an input range or each other; wrapped
  * memory that is misaligned.  width == 0 or height == 0 succeeds and touches nothing.
- * Not covered: a variance guide (rdx_temporal_accumulate below accumulates over frames and estimates the variance; the passes
- * here do not read it yet), guides beyond the primary hit (a reflection is filtered as the surface it
- * appears on); sigma_position is in the caller's world units. */
+ * Not covered: a variance guide (rdx_temporal_accumulate below accumulates over frames and estimates the variance;
+ * rdx_svgf_filter further below is this filter with that variance as its guide), guides beyond the primary hit (a reflection is
+ * filtered as the surface it appears on); sigma_position is in the caller's world units. */
 #define RDX_DENOISE_DEMODULATE 1u   /* divide by the clamped albedo before the passes, multiply it back after them */
 #define RDX_DENOISE_DEBUG      2u   /* the tone map's RTProp.debug: no ACES, no gamma */
 typedef struct rdx_denoise_settings {      /* 32 B */
@@ -958,7 +958,7 @@ void        rdx_debug_denoise_tiled(uint32_t mask);
  * color / previous_positions, 64 for materials / surfaces, 64 for a view, the history size, 4 per pixel for image); history_out or
  * image overlapping any input -- history_in included -- or each other; wrapped memory that is misaligned.  width == 0 or height == 0
  * succeeds and touches nothing.
- * Not covered: the variance guide inside rdx_denoise's passes (plane 1 is its input), a wider search when all four taps fail,
+ * Not covered: the variance guide inside rdx_denoise's passes (rdx_svgf_filter below reads plane 1), a wider search when all four taps fail,
  * albedo demodulation of the history (a caller may pass demodulated colours), the thin lens, anything beyond the primary hit. */
 #define RDX_TEMPORAL_DEBUG 1u       /* the tone map's RTProp.debug: no ACES, no gamma */
 typedef struct rdx_view {                  /* 64 B: four float4 */
@@ -990,6 +990,81 @@ int         rdx_temporal_accumulate(rdx_buffer color, size_t color_offset,      
                                     rdx_buffer history_in, size_t history_in_offset,               /* optional: the previous frame's history_out */
                                     rdx_buffer history_out, size_t history_out_offset,             /* rdx_temporal_history_size bytes */
                                     rdx_buffer image, size_t image_offset);                        /* optional RGBA8 per pixel */
+
+/* The variance-guided a-trous filter of SVGF (Schied et al. 2017), on the device: the passes of rdx_denoise with a luminance weight
+ * that is normalised by the local standard deviation -- wide where the estimate is noisy, narrow where a history has converged --
+ * and with the variance filtered along by the squared weights.  `color` is typically plane 0 of a history of
+ * rdx_temporal_accumulate and `moments` its plane 1, both taken at the history's offsets without a copy; of moments[p] only .z, the
+ * variance, is read.  Every float32 operation below is rounded on its own; dot is fma(z, z', fma(y, y', x x')); divisions are IEEE
+ * divisions and sqrtf is the correctly rounded one; no transcendental is evaluated per pixel.
+ * valid, n, a, P, den_k, l(c), h, k, wn and wz are those of rdx_denoise, word for word.
+ * Prepare: ld = DEMODULATE ? l(den) : 1 (the luminance formula on the three den_k); i_0(p)_k = valid ? color[p]_k / den_k :
+ * color[p]_k; vz = moments[p].z;
+ *     v_0(p) = (valid && vz > 0 && vz < inf) ? vz / (ld * ld) : 0
+ * so that a NaN, a negative or an infinite variance counts as 0.
+ * Pass j = 0 .. passes - 1, s = 1 << j: an invalid p keeps i_j(p) and v_j(p).  For a valid p, first the 3 x 3 prefilter of the
+ * variance, always at distance 1 whatever s is: g = {1/4, 1/2, 1/4}, gs = 0, gw = 0, and for dy = -1 .. 1, inside that dx = -1 .. 1,
+ * q = (x + dx, y + dy), skipped when outside the image or not valid (the centre always counts):
+ *     gs = gs + (g[dy + 1] * g[dx + 1]) * v_j(q); gw = gw + g[dy + 1] * g[dx + 1]
+ *     gv = gs / gw; sd = sqrtf(gv); dl = sigma_luminance * sd + epsilon
+ * (with sigma_luminance == 0 nothing reads dl).  Then sum = 0, sv = 0, sumw = 0 and the 25 taps in the order of rdx_denoise, dy =
+ * -2 .. 2, inside that dx = -2 .. 2, q = (x + dx s, y + dy s), skipped when outside the image or not valid, k, wn and wz unchanged:
+ *     x  = fabsf(l(i_j(p)) - l(i_j(q))) / dl
+ *     wc = sigma_luminance == 0 ? 1 : 1 / (1 + x * x)
+ *     w  = ((k * wn) * wz) * wc; the tap is skipped unless w > 0, the three components of i_j(q) are finite and v_j(q) is finite
+ *     sum_k = sum_k + i_j(q)_k * w; sv = sv + v_j(q) * (w * w); sumw = sumw + w
+ * With sumw > 0: i_{j+1}(p) = sum / sumw (one division per component) and v_{j+1}(p) = sv / (sumw * sumw); otherwise both are kept.
+ * (With sigma_luminance == 0 this is rdx_denoise with sigma_colour == 0 but for the test of v_j(q): where w * w or sumw * sumw leaves
+ * float32's range while sum / sumw does not -- a caller's normal near 3e38, a sumw below 2^-75 -- v becomes inf or a NaN and the
+ * pixel is no one's tap from then on.)
+ * Feedback: after pass feedback_pass - 1, feedback[p].rgb = valid ? i_{feedback_pass}(p)_k * den_k : color[p].rgb, and .w is the
+ * bits of color[p].w: the colours SVGF carries into the next frame's history (feedback_pass 1).  It is a range of its own; the
+ * caller copies it into plane 0.
+ * Finish: out[p].rgb = valid ? i_passes(p)_k * den_k : color[p].rgb; out[p].w = color[p].w, its bits kept; variance_out[p] = valid ?
+ * v_passes(p) * (ld * ld) : 0; image[p] (optional, RGBA8) is the tone map of rdx_accumulate on out[p].rgb, with RDX_DENOISE_DEBUG
+ * as its debug bit.  passes == 0 is prepare and finish alone.  A pixel's result depends on this order of taps only, not on how the
+ * work is cut into launches and blocks.
+ * `work` is rdx_svgf_work_size(width, height) bytes of the caller's (the limits of rdx_denoise_work_size; at most 64 bytes per
+ * pixel); its contents before and after a call are unspecified.  Nothing is staged and nothing is allocated per call; the call
+ * blocks and runs on logical device 0 in multi-device mode.  rdx_get_trace_stats().ms_accumulate is the kernel time of the call.
+ * Refused, before anything is launched: an uninitialised library; a NULL or unknown handle among color / moments / materials /
+ * surfaces / work / out, an unknown one among variance_out / feedback / image; `settings` NULL, passes > 8, normal_squarings > 7,
+ * a sigma_position or sigma_luminance that is negative, infinite or a NaN, an epsilon that is not finite or not > 0, feedback_pass >
+ * passes, `feedback` given with feedback_pass == 0 or missing with feedback_pass != 0, unknown flag bits, non-zero padding; a size
+ * outside the limits; an offset that is not a multiple of 16 (4 for `image` and `variance_out`); a range that does not hold width x
+ * height records (16 per pixel for color / moments / out / feedback, 64 for materials / surfaces, 4 for variance_out / image, the
+ * work size); `work`, `out`, `variance_out`, `feedback` or `image` overlapping an input range or each other; wrapped memory that is
+ * misaligned.  width == 0 or height == 0 succeeds and touches nothing.
+ * Dividing the variance by ld * ld is an approximation: a history holds modulated colours, so its variance is that of albedo times
+ * irradiance, and only where the albedo is constant across the frames and taps behind it is variance / ld^2 the variance of l(i).
+ * Not covered: a firefly clamp; the exp kernel of the paper (wc is the rational 1 / (1 + x^2), which needs no transcendental);
+ * writing the feedback into the history (it is a separate range the caller copies); demodulated histories; guides beyond the
+ * primary hit. */
+typedef struct rdx_svgf_settings {         /* 32 B */
+    uint32_t passes;             /* 0 .. 8: pass j uses step 1 << j */
+    uint32_t normal_squarings;   /* 0 .. 7, as rdx_denoise */
+    float    sigma_position;     /* as rdx_denoise; 0 = term off */
+    float    sigma_luminance;    /* in standard deviations (SVGF: 4); 0 = term off; otherwise finite and > 0 */
+    float    epsilon;            /* finite and > 0: added to sigma_luminance * sd */
+    uint32_t feedback_pass;      /* 0 = no feedback; otherwise 1 .. passes: `feedback` receives the iterate after that many passes (SVGF: 1) */
+    uint32_t flags;              /* RDX_DENOISE_DEMODULATE | RDX_DENOISE_DEBUG, the same bits */
+    uint32_t _0;                 /* must be 0 */
+} rdx_svgf_settings;
+size_t      rdx_svgf_work_size(uint32_t width, uint32_t height);
+int         rdx_svgf_filter(rdx_buffer color, size_t color_offset,               /* float4 per pixel, row-major, rgb + w */
+                            rdx_buffer moments, size_t moments_offset,           /* float4 per pixel: .z = the luminance variance */
+                            rdx_buffer materials, size_t materials_offset,       /* rdx_material_record per pixel */
+                            rdx_buffer surfaces, size_t surfaces_offset,         /* rdx_surface per pixel */
+                            uint32_t width, uint32_t height, const rdx_svgf_settings* settings,
+                            rdx_buffer work, size_t work_offset,                 /* rdx_svgf_work_size bytes; contents before and after unspecified */
+                            rdx_buffer out, size_t out_offset,                   /* float4 per pixel */
+                            rdx_buffer variance_out, size_t variance_out_offset, /* optional: one float per pixel */
+                            rdx_buffer feedback, size_t feedback_offset,         /* optional float4 per pixel; given iff feedback_pass != 0 */
+                            rdx_buffer image, size_t image_offset);              /* optional RGBA8 per pixel */
+/* Test and measurement seam: bit j of `mask` (j = 0, 1: steps 1 and 2) makes that pass of every later rdx_svgf_filter take its taps
+ * from an LDS tile of the block's pixels and their halo, a clear bit straight from memory.  Both forms give the same bits; the
+ * default is 3. */
+void        rdx_debug_svgf_tiled(uint32_t mask);
 
 /* Test seam: the one rule every call from rdx_query_rays to rdx_trace_paths_env applies to the byte ranges it is given, on plain
  * numbers (needs no device and no initialised library; no address is dereferenced) -> 0, or -1 with the refusal in

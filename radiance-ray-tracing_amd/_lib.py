@@ -70,6 +70,11 @@ class rdx_surface_buffers(C.Structure):
     _fields_ = [("meshInfo", C.c_void_p), ("index", C.c_void_p), ("uv", C.c_void_p), ("normal", C.c_void_p)]
 
 
+class rdx_svgf_settings(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("normal_squarings", C.c_uint32), ("sigma_position", C.c_float), ("sigma_luminance", C.c_float),
+                ("epsilon", C.c_float), ("feedback_pass", C.c_uint32), ("flags", C.c_uint32), ("_0", C.c_uint32)]
+
+
 class rdx_debug_range(C.Structure):
     _fields_ = [("address", C.c_uint64), ("size", C.c_uint64), ("offset", C.c_uint64), ("bytes", C.c_uint64), ("align", C.c_uint32),
                 ("present", C.c_uint32)]
@@ -242,6 +247,11 @@ SIGNATURES = {
     "rdx_temporal_accumulate": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(rdx_temporal_settings), C.c_void_p, C.c_size_t,
                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "rdx_svgf_work_size": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "rdx_svgf_filter": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                  C.POINTER(rdx_svgf_settings), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                  C.c_void_p, C.c_size_t]),
+    "rdx_debug_svgf_tiled": (None, [C.c_uint32]),
     "rdx_debug_check_ranges": (C.c_int, [C.POINTER(rdx_debug_range), C.POINTER(C.c_char_p), C.c_uint32, C.c_uint32, C.c_uint32]),
     "rdx_debug_shade_in_bounds": (C.c_int, [C.POINTER(rdx_mesh_info), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                             C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(rdx_material), C.c_uint32, C.c_int, C.c_uint32]),

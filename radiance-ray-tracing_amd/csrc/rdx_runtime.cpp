@@ -38,6 +38,7 @@
 #include "env.h"
 #include "bvh_build.h"
 #include "denoise.h"
+#include "svgf.h"
 #include "temporal.h"
 #include "device_math.h"
 #include "kernels.h"
@@ -3307,6 +3308,68 @@ extern "C" int rdx_temporal_accumulate(rdx_buffer color, size_t color_offset, rd
                                    at<const float4>(surfaces, surfaces_offset), at<const float4>(previous_positions, previous_positions_offset), v,
                                    previous_view ? at<const float4>(previous_view, previous_view_offset) : v, at<const float4>(history_in, history_in_offset),
                                    at<float4>(history_out, history_out_offset), at<uchar4>(image, image_offset)); });
+}
+
+// ---- the variance-guided a-trous filter of SVGF over a history's colours and variance (svgf.hip) -----------------------
+namespace {
+uint32_t g_svgfTiled = 3;           // rdx_debug_svgf_tiled: which of steps 1 and 2 take the LDS tile
+}
+
+extern "C" size_t rdx_svgf_work_size(uint32_t width, uint32_t height) { return svgf_work_size(width, height); }
+
+// Test and measurement seam: bit j set = pass j (j < 2: steps 1 and 2) of every later rdx_svgf_filter takes its taps from an LDS
+// tile, clear = straight from memory.  Both forms give the same bits
+extern "C" void rdx_debug_svgf_tiled(uint32_t mask) { g_svgfTiled = mask & 3u; }
+
+extern "C" int rdx_svgf_filter(rdx_buffer color, size_t color_offset, rdx_buffer moments, size_t moments_offset, rdx_buffer materials, size_t materials_offset,
+                               rdx_buffer surfaces, size_t surfaces_offset, uint32_t width, uint32_t height, const rdx_svgf_settings* settings, rdx_buffer work,
+                               size_t work_offset, rdx_buffer out, size_t out_offset, rdx_buffer variance_out, size_t variance_out_offset, rdx_buffer feedback,
+                               size_t feedback_offset, rdx_buffer image, size_t image_offset)
+{
+    const char* who = "rdx_svgf_filter";
+    if (!g.initialized) return fail("rdx_svgf_filter: rdx_init has not been called");
+    static_assert(sizeof(rdx_svgf_settings) == 32 && sizeof(rdx_material_record) == 64 && sizeof(rdx_surface) == 64, "the records of rdx_svgf_filter");
+    const bool empty = !width || !height;
+    const size_t npix = empty ? 0 : (size_t)width * height;
+    // a size outside the limits is refused below, before the table is consulted: until then the byte counts only have to exist
+    const size_t rows = npix <= DENOISE_MAX_PIXELS ? npix : 0;
+    const CallRange R[9] = {{color, color_offset, rows * sizeof(float4), "colour", 16, true},
+                            {moments, moments_offset, rows * sizeof(float4), "moments", 16, true},
+                            {materials, materials_offset, rows * sizeof(rdx_material_record), "material-record", 16, true},
+                            {surfaces, surfaces_offset, rows * sizeof(rdx_surface), "surface-record", 16, true},
+                            {work, work_offset, empty ? 0 : svgf_work_size(width, height), "work", 16, true},
+                            {out, out_offset, rows * sizeof(float4), "output", 16, true},
+                            {variance_out, variance_out_offset, rows * sizeof(float), "variance", 4, false},
+                            {feedback, feedback_offset, rows * sizeof(float4), "feedback", 16, false},
+                            {image, image_offset, rows * 4, "image", 4, false}};
+    if (check_call_handles(who, R)) return -1;
+    if (!settings) return fail("rdx_svgf_filter: no settings");
+    const rdx_svgf_settings& s = *settings;
+    if (s.passes > DENOISE_MAX_PASSES) return fail("rdx_svgf_filter: %u passes exceed the supported maximum of %u", s.passes, DENOISE_MAX_PASSES);
+    if (s.normal_squarings > DENOISE_MAX_SQUARINGS)
+        return fail("rdx_svgf_filter: normal_squarings %u exceeds the supported maximum of %u", s.normal_squarings, DENOISE_MAX_SQUARINGS);
+    if (!(s.sigma_position >= 0.0f && s.sigma_position < HUGE_VALF))
+        return fail("rdx_svgf_filter: sigma_position must be 0 (the term is off) or finite and positive, not %g", (double)s.sigma_position);
+    if (!(s.sigma_luminance >= 0.0f && s.sigma_luminance < HUGE_VALF))
+        return fail("rdx_svgf_filter: sigma_luminance must be 0 (the term is off) or finite and positive, not %g", (double)s.sigma_luminance);
+    if (!(s.epsilon > 0.0f && s.epsilon < HUGE_VALF)) return fail("rdx_svgf_filter: epsilon must be finite and positive, not %g", (double)s.epsilon);
+    if (s.feedback_pass > s.passes) return fail("rdx_svgf_filter: feedback_pass %u exceeds the %u passes", s.feedback_pass, s.passes);
+    if (feedback && !s.feedback_pass) return fail("rdx_svgf_filter: a feedback buffer was given, but feedback_pass is 0");
+    if (!feedback && s.feedback_pass) return fail("rdx_svgf_filter: feedback_pass is %u, but no feedback buffer was given", s.feedback_pass);
+    if (s.flags & ~(RDX_DENOISE_DEMODULATE | RDX_DENOISE_DEBUG))
+        return fail("rdx_svgf_filter: unknown flags 0x%x (bit 0 = demodulate, bit 1 = debug)", s.flags);
+    if (s._0) return fail("rdx_svgf_filter: the padding of the settings must be 0");
+    if (!empty && !svgf_work_size(width, height))
+        return fail("rdx_svgf_filter: an image of %u x %u pixels is outside the supported 1 .. %u x 1 .. %u and 2^26 pixels", width, height, DENOISE_MAX_DIM,
+                    DENOISE_MAX_DIM);
+    if (check_call_ranges(who, R, 4, (uint32_t)npix)) return -1;
+    if (empty) return 0;
+    const SvgfArgs a{width, height, s.passes, s.normal_squarings, s.flags, s.sigma_position, s.sigma_luminance, s.epsilon, s.feedback_pass, g_svgfTiled};
+    return timed_launch(&rdx_trace_stats::ms_accumulate, {work, out, variance_out, feedback, image}, [&] {
+        launch_svgf_filter(g.stream, a, at<const float4>(color, color_offset), at<const float4>(moments, moments_offset),
+                           at<const float4>(materials, materials_offset), at<const float4>(surfaces, surfaces_offset), at<float4>(work, work_offset),
+                           at<float4>(out, out_offset), at<float>(variance_out, variance_out_offset), at<float4>(feedback, feedback_offset),
+                           at<uchar4>(image, image_offset)); });
 }
 
 extern "C" int rdx_material_batch(const rdx_hit* hits, const float* dirs, const uint32_t* pixels, const uint32_t* frames,
