@@ -380,6 +380,34 @@ inline uint32_t TraceEnvPaths(Platform*, TopAccelStruct accelStruct, Buffer rays
     return invalid;
 }
 
+// Extension (no reference counterpart; rdx_env_mis_weights): the balance-heuristic weight of the scatter sample against the
+// environment's for the directions of the n rdx_ray records of `dirs` (EnvLightHits' shadow rays, ScatterHits' next rays), seen from
+// record src[k] (src nullptr: k, and nrecords == n) of the nrecords rays / materials; keys or randoms as given to ScatterHits (at
+// most one; both nullptr: the environment's own direction).  One rdx_env_mis_weight per direction to `out`.
+inline void EnvMisWeights(Platform*, Buffer rays, Buffer materials, Buffer dirs, uint32_t n, Buffer src, uint32_t nrecords, Buffer keys, Buffer randoms,
+                          Buffer image, Buffer table, uint32_t width, uint32_t height, Buffer out, size_t raysOffset = 0, size_t materialsOffset = 0,
+                          size_t dirsOffset = 0, size_t srcOffset = 0, size_t keysOffset = 0, size_t randomsOffset = 0, size_t imageOffset = 0,
+                          size_t tableOffset = 0, size_t outOffset = 0)
+{
+    if (rdx_env_mis_weights(rays, raysOffset, materials, materialsOffset, dirs, dirsOffset, n, src, srcOffset, nrecords, keys, keysOffset, randoms,
+                            randomsOffset, image, imageOffset, table, tableOffset, width, height, out, outOffset))
+        detail::fatal("EnvMisWeights");
+}
+
+// Extension (no reference counterpart; rdx_trace_paths_env_mis): TraceEnvPaths with the environment and the scatter sample weighted
+// against each other: a bounce ray that leaves the scene shows the environment, so mirrors and glass see the sky.
+inline uint32_t TraceEnvMisPaths(Platform*, TopAccelStruct accelStruct, Buffer rays, Buffer keys, uint32_t n, uint32_t maxDepth, Buffer lights,
+                                 uint32_t lightCount, Buffer area, uint32_t areaCount, Buffer image, Buffer table, uint32_t width, uint32_t height,
+                                 const rdx_shading_buffers& scene, Buffer radiance, size_t raysOffset = 0, size_t keysOffset = 0, size_t lightsOffset = 0,
+                                 size_t areaOffset = 0, size_t imageOffset = 0, size_t tableOffset = 0, size_t radianceOffset = 0)
+{
+    uint32_t invalid = 0;
+    if (rdx_trace_paths_env_mis(accelStruct, rays, raysOffset, keys, keysOffset, n, maxDepth, lights, lightsOffset, lightCount, area, areaOffset, areaCount,
+                                image, imageOffset, table, tableOffset, width, height, &scene, radiance, radianceOffset, &invalid))
+        detail::fatal("TraceEnvMisPaths");
+    return invalid;
+}
+
 // Extension (no reference counterpart; rdx_denoise_work_size, rdx_denoise): the frame's denoiser -- an edge-avoiding a-trous filter
 // over the width x height float4 colours in `color`, guided by the rdx_material_record / rdx_surface records of the same pixels'
 // primary hits; the result goes to `out` (float4 per pixel, w kept) and, tone-mapped as Accumulate does it, to `image` (RGBA8, may

@@ -838,6 +838,81 @@ int         rdx_trace_paths_env(rdx_buffer tlas,
                                 rdx_buffer radiance, size_t radiance_offset,      /* out: float4 per path: rgb, w = 0 */
                                 uint32_t* invalid_out);                           /* optional */
 
+/* Multiple-importance sampling of the environment: the direction rdx_env_light_hits draws from the table and the direction
+ * rdx_scatter_hits draws from the material are weighted against each other by the balance heuristic, so that a bounce ray that
+ * leaves the scene is SEEN: a mirror and a pane of glass show the sky, and a glossy surface under a broad sky converges sooner.
+ * Punctual and area records are not geometry and stay pure next-event estimation; area emitters stay invisible.
+ * At a hit with material record (N, albedo, metallic, roughness r, transmission, ior) and V = normalize(-ray direction), every
+ * float32 operation rounded on its own, dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)), normalize as in the reference:
+ *   lobe(rnd)     of a scatter sample, from the random triple rdx_scatter_hits drew it with: TRANSMISSION (2) if rnd.z < 0.5f &&
+ *                 2.0f * rnd.z < transmission, else DIFFUSE (0) if rnd.z < 0.5f, else SPECULAR (1); NONE (3) for a direction the
+ *                 environment's table gave;
+ *   pdf_scatter(L) NoL = dot(N, L); 0 unless NoL > 0, else H = normalize(V + L); NoH = clamp(dot(N, H), 0, 1); VoH = clamp(dot(V, H), 0,
+ *                 1); a2 = (r * r) * (r * r); den = NoH * NoH * (a2 - 1.0f) + 1.0f; D = a2 / (3.14159265359f * den * den);
+ *                 pSpec = D * NoH / (4.0f * VoH); pDiff = min(NoL, 1.0f) / 3.14159265359f; t = clamp(transmission, 0, 1);
+ *                 pdf_scatter = 0.5f * pSpec + (0.5f * (1.0f - t)) * pDiff: the density with which the two reflective lobes together
+ *                 produce L;
+ *   pdf_env(d)    0 where rdx_env_lookup shows nothing (a zero or non-finite d, a header that is not the call's) and where total == 0;
+ *                 else, with the row y and the column x of rdx_env_lookup, q = C[y][x] - (x ? C[y][x - 1] : 0) and
+ *                 pdf_env = ((float)q / (float)total) / (twoPiOverW * (rowCos[y] - rowCos[y + 1])): the density with which
+ *                 rdx_env_light_hits produces d;
+ *   w_scatter     1.0f if the lobe is TRANSMISSION, if it is SPECULAR and (r * r) * (r * r) == 0.0f, if !(NoL > 0), if pdf_scatter or
+ *                 pdf_env is not finite, or if !(pdf_scatter + pdf_env > 0); else pdf_scatter / (pdf_scatter + pdf_env).
+ *   The environment's weight is 1.0f - w_scatter.
+ * rdx_env_mis_weights evaluates this for n directions: direction k is dirs[k].direction -- a `shadow` range of rdx_env_light_hits
+ * or a `next` range of rdx_scatter_hits, as those calls write them -- seen from ray / material record s = src ? src[k] : k (the
+ * `src` of rdx_scatter_hits; without it nrecords must equal n).  keys or randoms are the nrecords rows rdx_scatter_hits was given
+ * and give the lobe of record s; with neither, the lobe is NONE.  out[k] is an rdx_env_mis_weight.  16 zero bytes for s >=
+ * nrecords, a record whose hit is not 1, a direction of zeros and a row whose tmax is 0 (a dark shadow row, a dead next row).  The
+ * kernel gathers through src alone, held to nrecords, and every table index is held to the call's W and H.  Refused, before
+ * anything is launched: invalid handles; offsets that are not multiples of 16 (of 4 for src); a range outside its buffer; `out` overlapping any
+ * input; both keys and randoms; nrecords != n without src; a size outside the limits.  n == 0 succeeds and touches nothing.
+ * rdx_trace_paths_env_mis is rdx_trace_paths_env, same arguments and refusals, with three changes to the README's loop:
+ *   the environment's lit of a hit is scaled, lit.rgb * (1.0f - w_scatter(its shadow direction, lobe NONE)), each channel, at
+ *   every depth but the last (depth + 1 < max_depth);
+ *   w = w_scatter(the next direction, the sample's lobe) is kept with the path after rdx_scatter_hits;
+ *   a live ray of depth >= 1 without a valid hit -- a miss, or a hit the scene buffers do not describe -- adds
+ *   color += weight * (rdx_env_lookup(ray).rgb * w), weight being the path's after the previous fold.
+ * Depth 0 is unchanged (a first miss shows the texel).  The last depth samples no next ray, so no scatter sample would carry the
+ * share w_scatter of its hit: there the environment's lit counts in full, as in rdx_trace_paths_env, and the truncated path
+ * estimates the same integral as that call's wherever every lobe can be sampled both ways.  Both reflective lobes share
+ * w_scatter(L) over the upper hemisphere, so their weighted sum and the weighted next-event term add up to the unweighted BRDF;
+ * transmission and the r == 0 mirror are counted by the scatter sample alone.  A transmission sample's total-internal-reflection
+ * fallback direction is weighted 1 like the rest of its lobe.  radiance[i].rgb is `color` of that loop, bit for bit. */
+#define RDX_LOBE_DIFFUSE 0u
+#define RDX_LOBE_SPECULAR 1u
+#define RDX_LOBE_TRANSMISSION 2u
+#define RDX_LOBE_NONE 3u
+typedef struct rdx_env_mis_weight {
+    float    w_scatter, pdf_scatter, pdf_env;
+    uint32_t lobe;
+} rdx_env_mis_weight;
+int         rdx_env_mis_weights(rdx_buffer rays, size_t rays_offset,              /* rdx_ray per record: the direction is read -> V */
+                                rdx_buffer materials, size_t materials_offset,    /* rdx_material_record per record */
+                                rdx_buffer dirs, size_t dirs_offset, uint32_t n,  /* rdx_ray per direction: the direction and tmax are read */
+                                rdx_buffer src, size_t src_offset,                /* optional uint32 per direction: its record; NULL: k */
+                                uint32_t nrecords,                                /* rows of rays / materials / keys / randoms */
+                                rdx_buffer keys, size_t keys_offset,              /* rdx_shade_key per record, or NULL */
+                                rdx_buffer randoms, size_t randoms_offset,        /* float4 per record (z used), or NULL; both NULL: lobe NONE */
+                                rdx_buffer image, size_t image_offset,
+                                rdx_buffer table, size_t table_offset,
+                                uint32_t width, uint32_t height,
+                                rdx_buffer out, size_t out_offset);               /* out: rdx_env_mis_weight per direction */
+int         rdx_trace_paths_env_mis(rdx_buffer tlas,
+                                    rdx_buffer rays, size_t rays_offset,          /* as rdx_trace_paths_env, every argument */
+                                    rdx_buffer keys, size_t keys_offset,
+                                    uint32_t n, uint32_t max_depth,
+                                    rdx_buffer lights, size_t lights_offset,
+                                    uint32_t light_count,
+                                    rdx_buffer area, size_t area_offset,
+                                    uint32_t area_count,
+                                    rdx_buffer image, size_t image_offset,
+                                    rdx_buffer table, size_t table_offset,
+                                    uint32_t width, uint32_t height,
+                                    const rdx_shading_buffers* scene,
+                                    rdx_buffer radiance, size_t radiance_offset,
+                                    uint32_t* invalid_out);
+
 /* The frame's denoiser, on the device: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a width x height image
  * of float4 colours -- what rdx_trace_paths and its kin write for the rays of rdx_generate_rays, pixel p = y * width + x -- guided
  * by the rdx_material_record and the rdx_surface of the same pixels' primary hits (records the caller filled in are equally

@@ -17,8 +17,8 @@ LIB = os.path.join(HERE, "librdx.so")
 EXTRA = os.environ.get("RDX_DEFINES", "").split()
 if os.environ.get("RDX_LIB_NAME"):
     LIB = os.path.join(HERE, os.environ["RDX_LIB_NAME"])
-SOURCES = ["kernels.hip", "tlas_update.hip", "surface.hip", "shade.hip", "material.hip", "scatter.hip", "light_paths.hip", "punctual.hip", "area.hip", "env.hip", "denoise.hip", "temporal.hip", "svgf.hip", "raygen.hip", "paths.hip", "rdx_runtime.cpp", "accel_layout.cpp", "bvh_build.cpp", "scene_obj.cpp", "user_shader.cpp"]
-HEADERS = ["kernels.h", "accel_layout.h", "stages.h", "texture.h", "device_math.h", "rdx_types.h", "surface.h", "shade.h", "material_eval.h", "hit_material.h", "light_emit.h", "path_shade.h", "scatter.h", "light_paths.h", "punctual.h", "area.h", "env.h", "denoise.h", "temporal.h", "svgf.h", "raygen.h", "raygen_device.h", "paths.h", "bvh_build.h", "sbt_generated.h", "traverse_coop.h", "traverse_pool.h", "user_shader.h",
+SOURCES = ["kernels.hip", "tlas_update.hip", "surface.hip", "shade.hip", "material.hip", "scatter.hip", "light_paths.hip", "punctual.hip", "area.hip", "env.hip", "env_mis.hip", "denoise.hip", "temporal.hip", "svgf.hip", "raygen.hip", "paths.hip", "rdx_runtime.cpp", "accel_layout.cpp", "bvh_build.cpp", "scene_obj.cpp", "user_shader.cpp"]
+HEADERS = ["kernels.h", "accel_layout.h", "stages.h", "texture.h", "device_math.h", "rdx_types.h", "surface.h", "shade.h", "material_eval.h", "hit_material.h", "light_emit.h", "path_shade.h", "scatter.h", "light_paths.h", "punctual.h", "area.h", "env.h", "env_mis.h", "denoise.h", "temporal.h", "svgf.h", "raygen.h", "raygen_device.h", "paths.h", "bvh_build.h", "sbt_generated.h", "traverse_coop.h", "traverse_pool.h", "user_shader.h",
            os.path.join("..", "..", "include", "rdx.h")]
 # device bitcode for user programs: one file for every library name (it depends on texture.h only)
 TEX_BC = os.path.join(HERE, "user_texture.bc")

@@ -23,6 +23,8 @@ constexpr uint32_t ENV_MAGIC = 0x56454452u;        // "RDEV"
 constexpr uint32_t ENV_VERSION = 1u;
 constexpr uint32_t ENV_MAX_WIDTH = 16384u, ENV_MAX_HEIGHT = 8192u;
 constexpr uint32_t ENV_QMAX = 65535u;              // a texel's largest quantised weight: a row sums to less than 2^30
+// the lobe a scatter sample was drawn from (rdx_env_mis_weights); NONE: a direction the environment's table gave
+constexpr uint32_t LOBE_DIFFUSE = 0u, LOBE_SPECULAR = 1u, LOBE_TRANSMISSION = 2u, LOBE_NONE = 3u;
 
 struct EnvHeader {
     uint32_t magic, version, width, height;
@@ -79,6 +81,19 @@ void launch_env_lookup(hipStream_t st, const float4* rays, uint32_t n, const Env
 void launch_env_shade(hipStream_t st, const DInst* insts, const uint32_t* slotOf, uint32_t nInst, const ShadeScene& sc, const PunctualLight* lights,
                       uint32_t nLights, const AreaLight* area, uint32_t nArea, const EnvView& env, const LightPathStreams& io, uint32_t n, uint32_t depth,
                       bool sampleNext, uint32_t* live, uint32_t* invalid);
+
+// ---- multiple-importance sampling of the environment against the scatter sample (env_mis.hip; the estimator is env_mis.h) ----
+// rdx_env_mis_weights: direction k = dirs[2k + 1] seen from ray / material record s = src ? src[k] : k, a record of zeros for s >=
+// nrecords; the lobe from keys[s] or randoms[s], NONE where both are null; out[k] = (w, pdf_scatter, pdf_env, lobe)
+void launch_env_mis_weights(hipStream_t st, const float4* rays, const float4* materials, const float4* dirs, uint32_t n, const uint32_t* src,
+                            uint32_t nrecords, const uint4* keys, const float4* randoms, const EnvView& env, uint4* out);
+// k_env_mis_shade: launch_env_shade with the environment's record weighted by 1 - w of its direction, w of the sampled direction in
+// foldF.w, and the weighted texel of a live ray of depth > 0 without a valid hit added to radiance[path]
+void launch_env_mis_shade(hipStream_t st, const DInst* insts, const uint32_t* slotOf, uint32_t nInst, const ShadeScene& sc, const PunctualLight* lights,
+                          uint32_t nLights, const AreaLight* area, uint32_t nArea, const EnvView& env, const LightPathStreams& io, uint32_t n,
+                          uint32_t depth, bool sampleNext, uint32_t* live, uint32_t* invalid);
+// k_env_mis_fold: launch_lights_fold (light_paths.h) with foldF.w handed on in nWeight.w, the next live ray's weight word
+void launch_env_mis_fold(hipStream_t st, const float4* any, uint32_t nLights, const LightPathStreams& io, uint32_t live);
 #endif
 
 } // namespace rdx

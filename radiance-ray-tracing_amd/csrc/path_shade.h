@@ -93,10 +93,20 @@ struct PunctualAreaEnvSource {
 // consecutive live rays stay together and in order: a lane's record is the block's base from ONE atomic on *live per BLOCK, plus
 // the survivors of the block's earlier waves, plus the lane's rank in its wave's ballot.  Survivor k writes the records k * count()
 // + j of its lights, ray-major.  20 bytes of LDS: the block's four survivor counts and its base.
-template <class Source>
+//
+// Mis is what rdx_trace_paths_env_mis adds (env_mis.hip EnvMis): the LAST record of the source is the environment and
+// is weighted by 1 - skyWeight of its direction wherever a next ray is sampled, scatterWeight of the sampled direction travels in
+// foldF.w -- the fold hands it on in nWeight.w, where this kernel finds it as w.w at the next depth --, and a live ray of depth > 0
+// without a valid hit adds weight * (source.miss(rd) * w.w) to its path's colour.  NoMis is every other call's: `on` is a
+// compile-time false and nothing of this is in their code.
+struct NoMis {
+    static constexpr bool on = false;
+};
+
+template <class Source, class Mis = NoMis>
 __device__ __forceinline__ void path_shade(const DInst* __restrict__ insts, const uint32_t* __restrict__ slotOf, uint32_t nInst, const ShadeScene& sc,
                                            const Source& source, const LightPathStreams& io, uint32_t n, uint32_t depth, uint32_t sampleNext,
-                                           uint32_t* __restrict__ live, uint32_t* __restrict__ invalid)
+                                           uint32_t* __restrict__ live, uint32_t* __restrict__ invalid, const Mis& mis = Mis{})
 {
     const uint32_t i = blockIdx.x * PATH_SHADE_BLOCK + threadIdx.x;
     bool alive = false, bad = false;
@@ -124,6 +134,16 @@ __device__ __forceinline__ void path_shade(const DInst* __restrict__ insts, cons
             float4 first = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (!alive) first = source.miss(rd);
             io.radiance[i] = first;
+        }
+        if constexpr (Mis::on) {
+            // the scatter sample that found the environment.  A path has one live ray and the fold of depth - 1 precedes this launch in
+            // stream order: a plain load and store
+            if (depth != 0u && !alive) {
+                const float4 sky = source.miss(rd);
+                const float4 c = io.radiance[id.x];
+                const f3 color = mk3(c.x, c.y, c.z) + mk3(w.x, w.y, w.z) * (mk3(sky.x, sky.y, sky.z) * w.w);
+                io.radiance[id.x] = make_float4(color.x, color.y, color.z, 0.0f);
+            }
         }
     }
     // wave64 ballots: every lane of the wave is here (no thread has returned)
@@ -165,6 +185,14 @@ __device__ __forceinline__ void path_shade(const DInst* __restrict__ insts, cons
         const bool lit = source.emit(j, mat.above, id, depth, L, E, tmax);
         float4 c, s0, s1;
         light_record(lit, p, L, E, tmax, c, s0, s1);
+        if constexpr (Mis::on) {
+            // a uniform branch on j and the depth: the weight is evaluated for the environment's record alone, and only where a next
+            // ray is sampled -- at the last depth no scatter sample carries the other share, and the record counts in full
+            if (j + 1u == nAll && sampleNext && lit) {
+                const float ws = 1.0f - mis.skyWeight(p, L);
+                c = make_float4(c.x * ws, c.y * ws, c.z * ws, 0.0f);
+            }
+        }
         const size_t r = first + j;
         io.lit[r] = c;
         io.shadow[2 * r] = s0;
@@ -173,9 +201,11 @@ __device__ __forceinline__ void path_shade(const DInst* __restrict__ insts, cons
 
     // ---- k_scatter_hits with the key (frameID, pixel, depth) ----
     f3 nf = mk3(0.f, 0.f, 0.f);
+    float wNext = 0.0f;
     if (sampleNext) {
         const f3 rnd = pcg3d(id.y, id.z, depth);
         const f3 nd = sample_brdf_transm(p.FN, p.V, mat.N, mat.albedo, mat.metallic, mat.roughness, mat.transmission, mat.ior, rnd, nf);
+        if constexpr (Mis::on) wNext = mis.scatterWeight(p, nd, rnd);
         const f3 origin = dot3(nd, mat.N) < 0 ? mat.below : mat.above;      // getHitPosition(hitData, -+faceN)
         io.nRays[2 * k] = make_float4(origin.x, origin.y, origin.z, 0.001f);
         io.nRays[2 * k + 1] = make_float4(nd.x, nd.y, nd.z, 1000.0f);
@@ -183,7 +213,7 @@ __device__ __forceinline__ void path_shade(const DInst* __restrict__ insts, cons
     const f3 ambient = mat.albedo * 0.1f;
     io.nIds[k] = id;
     io.nWeight[k] = w;
-    io.foldF[k] = make_float4(nf.x, nf.y, nf.z, 0.0f);
+    io.foldF[k] = make_float4(nf.x, nf.y, nf.z, wNext);
     io.foldA[k] = make_float4(ambient.x, ambient.y, ambient.z, 0.0f);
 }
 

@@ -2798,11 +2798,14 @@ extern "C" int rdx_trace_paths(rdx_buffer tlas, rdx_buffer rays, size_t rays_off
 // launch_query_rays sizes its grid on the host, so ONE word -- the survivors of the depth -- is read back per bounce; nothing else
 // passes through the host.  The chunk's streams are one allocation that grows on first use and is reused: 192 + 80 L bytes per path
 // (DESIGN 4.15, 4.16).
+// `fold` is the call's fold kernel beside its shade kernel: k_lights_fold for all but rdx_trace_paths_env_mis, whose own hands the
+// weight's fourth word on (env_mis.hip).
 namespace {
+using FoldLaunch = void (*)(hipStream_t, const float4*, uint32_t, const LightPathStreams&, uint32_t);
 template <class ShadeLaunch>
 int trace_light_paths(const char* who, rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n,
                       uint32_t max_depth, uint32_t L, const ShadeScene& sc, rdx_buffer radiance, size_t radiance_offset, uint32_t* invalid_out,
-                      ShadeLaunch&& shade)
+                      ShadeLaunch&& shade, FoldLaunch fold = launch_lights_fold)
 {
     const AccelCache& ac = *acc(tlas);
     // a chunk's shadow rays are one launch_query_rays range, whose count is 32 bits; beyond the five lights of a SceneProperties a
@@ -2891,7 +2894,7 @@ int trace_light_paths(const char* who, rdx_buffer tlas, rdx_buffer rays, size_t 
                 g.stats.launches_shadow++;
             }
             g_timer.begin(&g.stats.ms_shade, G.s0);
-            launch_lights_fold(G.s0, sAny, L, io, survivors);
+            fold(G.s0, sAny, L, io, survivors);
             g_timer.end(G.s0);
             g.bounceCounts[d + 1] += survivors;
             if (d == 0) g.stats.rays_primary += liveRays; else g.stats.rays_bounce += liveRays;
@@ -3187,6 +3190,78 @@ extern "C" int rdx_trace_paths_env(rdx_buffer tlas, rdx_buffer rays, size_t rays
                                  uint32_t* invalid) {
                                  launch_env_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, lightTable, light_count, areaTable, area_count, env, io, live, d, sampleNext,
                                                   cursor, invalid); });
+}
+
+// The weight of the scatter sample against the environment's for n directions (include/rdx.h; env_mis.hip).  As rdx_env_light_hits:
+// no TLAS and no scene streams, so the checks are those of the ranges alone.  rays, materials, keys and randoms hold nrecords rows,
+// dirs, src and out n
+extern "C" int rdx_env_mis_weights(rdx_buffer rays, size_t rays_offset, rdx_buffer materials, size_t materials_offset, rdx_buffer dirs, size_t dirs_offset,
+                                   uint32_t n, rdx_buffer src, size_t src_offset, uint32_t nrecords, rdx_buffer keys, size_t keys_offset, rdx_buffer randoms,
+                                   size_t randoms_offset, rdx_buffer image, size_t image_offset, rdx_buffer table, size_t table_offset, uint32_t width,
+                                   uint32_t height, rdx_buffer out, size_t out_offset)
+{
+    const char* who = "rdx_env_mis_weights";
+    if (!g.initialized) return fail("rdx_env_mis_weights: rdx_init has not been called");
+    if (env_size_refused(who, width, height)) return -1;
+    static_assert(sizeof(rdx_env_mis_weight) == 16 && RDX_LOBE_NONE == LOBE_NONE && RDX_LOBE_TRANSMISSION == LOBE_TRANSMISSION, "weight record");
+    // the first eight are read, the last written
+    const CallRange R[9] = {{rays, rays_offset, (size_t)nrecords * sizeof(rdx_ray), "ray", 16, true},
+                            {materials, materials_offset, (size_t)nrecords * sizeof(rdx_material_record), "material-record", 16, true},
+                            {dirs, dirs_offset, (size_t)n * sizeof(rdx_ray), "direction", 16, true},
+                            {src, src_offset, (size_t)n * sizeof(uint32_t), "src", 4, false},
+                            {image, image_offset, env_image_bytes(width, height), "environment-image", 16, true},
+                            {table, table_offset, env_table_size(width, height), "environment-table", 16, true},
+                            {keys, keys_offset, (size_t)nrecords * sizeof(rdx_shade_key), "key", 16, false},
+                            {randoms, randoms_offset, (size_t)nrecords * 4 * sizeof(float), "randoms", 16, false},
+                            {out, out_offset, (size_t)n * sizeof(rdx_env_mis_weight), "weight", 16, true}};
+    if (check_call_handles(who, R)) return -1;
+    if (keys && randoms) return fail("rdx_env_mis_weights: both keys and randoms given: at most one of the two is allowed");
+    if (!src && nrecords != n) return fail("rdx_env_mis_weights: without src direction k belongs to record k: nrecords %u must equal n %u", nrecords, n);
+    if (check_call_ranges(who, R, 8, n)) return -1;
+    if (!n) return 0;
+    return timed_launch(&rdx_trace_stats::ms_shade, {out}, [&] {
+        launch_env_mis_weights(g.stream, at<const float4>(rays, rays_offset), at<const float4>(materials, materials_offset), at<const float4>(dirs, dirs_offset), n,
+                               at<const uint32_t>(src, src_offset), nrecords, at<const uint4>(keys, keys_offset), at<const float4>(randoms, randoms_offset),
+                               env_view(image, image_offset, table, table_offset, width, height), at<uint4>(out, out_offset)); });
+}
+
+// rdx_trace_paths_env with the environment and the scatter sample weighted against each other (include/rdx.h; env_mis.hip): the
+// checks of rdx_trace_paths_env, then trace_light_paths with k_env_mis_shade and k_env_mis_fold
+extern "C" int rdx_trace_paths_env_mis(rdx_buffer tlas, rdx_buffer rays, size_t rays_offset, rdx_buffer keys, size_t keys_offset, uint32_t n, uint32_t max_depth,
+                                       rdx_buffer lights, size_t lights_offset, uint32_t light_count, rdx_buffer area, size_t area_offset, uint32_t area_count,
+                                       rdx_buffer image, size_t image_offset, rdx_buffer table, size_t table_offset, uint32_t width, uint32_t height,
+                                       const rdx_shading_buffers* scene, rdx_buffer radiance, size_t radiance_offset, uint32_t* invalid_out)
+{
+    const char* who = "rdx_trace_paths_env_mis";
+    if (!g.initialized) return fail("rdx_trace_paths_env_mis: rdx_init has not been called");
+    if (!tlas || !known_buffer(tlas)) return fail("rdx_trace_paths_env_mis: invalid TLAS handle");
+    if (light_count >= MAX_PATH_LIGHTS || area_count >= MAX_PATH_LIGHTS || light_count + area_count + 1 > MAX_PATH_LIGHTS)
+        return fail("rdx_trace_paths_env_mis: light_count %u + area_count %u + the environment exceeds the %u records a path samples (RDX_MAX_PATH_LIGHTS)",
+                    light_count, area_count, MAX_PATH_LIGHTS);
+    if (env_size_refused(who, width, height)) return -1;
+    const CallRange R[8] = {{rays, rays_offset, (size_t)n * sizeof(rdx_ray), "ray", 16, true}, {keys, keys_offset, (size_t)n * sizeof(rdx_shade_key), "key", 16, true},
+                            {lights, lights_offset, (size_t)light_count * sizeof(PunctualLight), "light-table", 16, light_count != 0},
+                            {area, area_offset, (size_t)area_count * sizeof(AreaLight), "area-light-table", 16, area_count != 0},
+                            {image, image_offset, env_image_bytes(width, height), "environment-image", 16, true},
+                            {table, table_offset, env_table_size(width, height), "environment-table", 16, true},
+                            {scene ? scene->scene : nullptr, 0, sizeof(SceneProperties), "scene (SceneProperties)", 4, false},
+                            {radiance, radiance_offset, (size_t)n * sizeof(float4), "radiance", 16, true}};
+    uint32_t samplerBits = 0;
+    if (check_call_handles(who, R) || check_shading_handles(who, scene, samplerBits)) return -1;
+    if (max_depth > 62) return fail("rdx_trace_paths_env_mis: depth %u exceeds the supported maximum of 62", max_depth);
+    if (check_call_ranges(who, R, 7, n, {invalid_out}, shading_aligned(scene))) return -1;
+    if (!n) return 0;
+    ShadeScene sc;
+    if (shade_scene(who, scene, samplerBits, sc) || derive_accel(tlas)) return -1;
+    const PunctualLight* lightTable = light_count ? at<const PunctualLight>(lights, lights_offset) : nullptr;
+    const AreaLight* areaTable = area_count ? at<const AreaLight>(area, area_offset) : nullptr;
+    const EnvView env = env_view(image, image_offset, table, table_offset, width, height);
+    return trace_light_paths(who, tlas, rays, rays_offset, keys, keys_offset, n, max_depth, light_count + area_count + 1, sc, radiance, radiance_offset, invalid_out,
+                             [&](hipStream_t st, const AccelCache& ac, const LightPathStreams& io, uint32_t live, uint32_t d, bool sampleNext, uint32_t* cursor,
+                                 uint32_t* invalid) {
+                                 launch_env_mis_shade(st, ac.insts, ac.slotOf, ac.s.nInst, sc, lightTable, light_count, areaTable, area_count, env, io, live, d,
+                                                      sampleNext, cursor, invalid); },
+                             launch_env_mis_fold);
 }
 
 // ---- the edge-avoiding a-trous filter over a frame's colours (denoise.hip) ---------------------------------------------

@@ -8,7 +8,11 @@ image lights the scene, importance-sampled at one direction per hit.  Built on r
 The image is (height, width, 4) float32, row 0 the zenith (+y), column x the azimuth [2 pi x / W, 2 pi (x + 1) / W); the direction
 of (theta, phi) is (sin theta cos phi, cos theta, sin theta sin phi).  An Environment is the image, the sampling table that
 rdx_env_build derives from it on the device, and their size.  Rotation and intensity are the image's: roll or scale it and build
-again."""
+again.
+
+TraceEnvPaths counts the sky by next-event estimation alone.  EnvMisWeights / TraceEnvMisPaths (rdx_env_mis_weights,
+rdx_trace_paths_env_mis) weight the sky's sample and the scatter sample against each other, so that a bounce ray
+that leaves the scene shows the sky: mirrors reflect it and glass lets it through."""
 import ctypes as C
 
 import numpy as np
@@ -203,17 +207,24 @@ def TraceEnvPaths(tlas, rays, keys, n, max_depth, lights, light_count, area, are
     light_count + area_count + 1 <= MAX_PATH_LIGHTS; a table whose count is 0 may be None.  A path whose first ray hits nothing shows
     EnvLookup of that ray; a later miss ends the path and adds nothing (next-event estimation only, so nothing is counted twice).
     Everything else as for rd.TraceAreaPaths.  Returns (radiance, invalid)."""
-    sb, n = rd._path_arguments("TraceEnvPaths", n, max_depth, scene_buffers, tlas=tlas, rays=rays, keys=keys)
-    light_count, area_count = _path_counts("TraceEnvPaths", light_count, area_count)
+    return _trace_env_paths("TraceEnvPaths", "rdx_trace_paths_env", tlas, rays, keys, n, max_depth, lights, light_count, area, area_count, environment,
+                            scene_buffers, radiance, rays_offset, keys_offset, lights_offset, area_offset, radiance_offset)
+
+
+def _trace_env_paths(who, symbol, tlas, rays, keys, n, max_depth, lights, light_count, area, area_count, environment, scene_buffers, radiance, rays_offset,
+                     keys_offset, lights_offset, area_offset, radiance_offset):
+    """the Buffer route of TraceEnvPaths and TraceEnvMisPaths: the library's call `symbol`"""
+    sb, n = rd._path_arguments(who, n, max_depth, scene_buffers, tlas=tlas, rays=rays, keys=keys)
+    light_count, area_count = _path_counts(who, light_count, area_count)
     for what, b, c in (("lights", lights, light_count), ("area", area, area_count)):
         if not (isinstance(b, Buffer) or (b is None and c == 0)):
-            raise RadianceError("TraceEnvPaths: %s must be a Buffer (or None with a count of 0)" % what)
-    e = _environment("TraceEnvPaths", environment)
-    radiance = rd._out_buffer("TraceEnvPaths", n, radiance, radiance_offset, "float4", "radiance", False, flags=False)
+            raise RadianceError("%s: %s must be a Buffer (or None with a count of 0)" % (who, what))
+    e = _environment(who, environment)
+    radiance = rd._out_buffer(who, n, radiance, radiance_offset, "float4", "radiance", False, flags=False)
     invalid = C.c_uint32(0)
-    _check(_lib.lib().rdx_trace_paths_env(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), _h(lights),
-                                          int(lights_offset), light_count, _h(area), int(area_offset), area_count, *e, C.byref(sb), radiance.handle,
-                                          int(radiance_offset), C.byref(invalid)))
+    _check(getattr(_lib.lib(), symbol)(tlas.handle, rays.handle, int(rays_offset), keys.handle, int(keys_offset), n, int(max_depth), _h(lights),
+                                       int(lights_offset), light_count, _h(area), int(area_offset), area_count, *e, C.byref(sb), radiance.handle,
+                                       int(radiance_offset), C.byref(invalid)))
     return radiance, int(invalid.value)
 
 
@@ -221,7 +232,11 @@ def TraceEnvPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, area_t, enviro
     """Extension: TraceEnvPaths on CUDA tensors -- rays, keys, lights_t and area_t as for rd.TraceAreaPathsTorch (either table may be
     None), L + A + 1 <= MAX_PATH_LIGHTS.  Returns radiance float32 (n, 4): rgb, 0.  The library cannot see torch's stream, so the
     current stream is synchronised first; the call blocks."""
-    who = "TraceEnvPathsTorch"
+    return _trace_env_paths_torch("TraceEnvPathsTorch", TraceEnvPaths, tlas, rays_t, keys_t, max_depth, lights_t, area_t, environment, scene_buffers)
+
+
+def _trace_env_paths_torch(who, call, tlas, rays_t, keys_t, max_depth, lights_t, area_t, environment, scene_buffers):
+    """the torch route of TraceEnvPaths and TraceEnvMisPaths: `call` on the wrapped tensors"""
     L = rd._cuda_tensor(who, lights_t, "light", "lights") if lights_t is not None else 0
     A = rd._cuda_tensor(who, area_t, "area light", "area lights") if area_t is not None else 0
     L, A = _path_counts(who, L, A)
@@ -235,9 +250,82 @@ def TraceEnvPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, area_t, enviro
     rd._count(who, max_depth, "max_depth must be a non-negative integer")
     radiance = t.new("float4")
     if t.begin():
-        TraceEnvPaths(tlas, t.wrap(rays_t, "ray"), t.wrap(keys_t, "key"), t.n, max_depth, t.wrap(lights_t, "light", L) if L else None, L,
-                      t.wrap(area_t, "area light", A) if A else None, A, environment, scene_buffers, t.wrap(radiance, "float4"))
+        call(tlas, t.wrap(rays_t, "ray"), t.wrap(keys_t, "key"), t.n, max_depth, t.wrap(lights_t, "light", L) if L else None, L,
+             t.wrap(area_t, "area light", A) if A else None, A, environment, scene_buffers, t.wrap(radiance, "float4"))
     return radiance
+
+
+# ---- multiple-importance sampling of the environment against the scatter sample (rdx_env_mis_weights, rdx_trace_paths_env_mis) ----
+LOBE_DIFFUSE, LOBE_SPECULAR, LOBE_TRANSMISSION, LOBE_NONE = 0, 1, 2, 3
+MIS_WEIGHT_DTYPE = np.dtype([("w_scatter", "<f4"), ("pdf_scatter", "<f4"), ("pdf_env", "<f4"), ("lobe", "<u4")])
+assert MIS_WEIGHT_DTYPE.itemsize == 16
+
+
+def EnvMisWeights(rays, materials, dirs, n, environment, keys=None, randoms=None, src=None, nrecords=None, out=None, rays_offset=0, materials_offset=0,
+                  dirs_offset=0, keys_offset=0, randoms_offset=0, src_offset=0, out_offset=0):
+    """Extension: the balance-heuristic weight of the scatter sample against the environment's sample for `n` directions: the
+    `direction` of the RAY_DTYPE records of `dirs` -- the shadow rays EnvLightHits wrote, or the next rays rd.ScatterHits wrote --
+    seen from the ray and the material record they belong to: record k, or, `src` given (ScatterHits' src), record src[k] of the
+    `nrecords` records of rays / materials (default n).  keys or randoms are what ScatterHits was given (at most one) and tell the
+    lobe the direction was drawn from; with neither the direction is the environment's own (LOBE_NONE).  One MIS_WEIGHT_DTYPE record
+    per direction to `out` (a Buffer, or None: created): w_scatter, pdf_scatter, pdf_env, lobe; the environment's weight is
+    1 - w_scatter.  Zeros for a record whose hit is not 1, a src[k] >= nrecords and a row that accepts nothing.  Returns out."""
+    rd._buffers("EnvMisWeights", rays=rays, materials=materials, dirs=dirs)
+    e = _environment("EnvMisWeights", environment)
+    hk, hr, hs = (rd._optional_buffer("EnvMisWeights", b, what) for b, what in ((keys, "keys"), (randoms, "randoms"), (src, "src")))
+    if keys is not None and randoms is not None:
+        raise RadianceError("EnvMisWeights: both keys and randoms given: at most one of the two is allowed")
+    n = rd._count("EnvMisWeights", n, "n must be a non-negative integer", 0xffffffff)
+    nrecords = n if nrecords is None else rd._count("EnvMisWeights", nrecords, "nrecords must be a non-negative integer", 0xffffffff)
+    if src is None and nrecords != n:
+        raise RadianceError("EnvMisWeights: without src direction k belongs to record k: nrecords must equal n")
+    out = rd._out_buffer("EnvMisWeights", n, out, out_offset, "float4", "out", False, flags=False)
+    _check(_lib.lib().rdx_env_mis_weights(rays.handle, int(rays_offset), materials.handle, int(materials_offset), dirs.handle, int(dirs_offset), n, hs,
+                                          int(src_offset), nrecords, hk, int(keys_offset), hr, int(randoms_offset), *e, out.handle, int(out_offset)))
+    return out
+
+
+def EnvMisWeightsTorch(rays_t, materials_t, dirs_t, environment, keys=None, randoms=None, src=None):
+    """Extension: EnvMisWeights on CUDA tensors -- dirs_t a contiguous float32 (n, 8) tensor of rays; rays_t and materials_t the
+    (nrecords, 8) and (nrecords, 16) tensors they belong to, nrecords == n unless src, a contiguous int32 (n,) tensor, is given; at
+    most one of keys (int32 (nrecords, 4)) and randoms (float32 (nrecords, 4)).  Returns float32 (n, 4): w_scatter, pdf_scatter,
+    pdf_env and the bits of the lobe (view as int32).  The library cannot see torch's stream, so the current stream is synchronised
+    first; the call blocks."""
+    who = "EnvMisWeightsTorch"
+    t = rd._TorchCall(who)
+    _environment(who, environment)
+    t.first(dirs_t, "ray", "dirs", owner="dirs")
+    if src is not None:
+        t.also(src, "src", "src", owner="dirs")
+    nrecords = rd._cuda_tensor(who, rays_t, "ray", "rays", None if src is not None else t.n, t.device, "dirs")
+    rd._cuda_tensor(who, materials_t, "material", "materials", nrecords, t.device, "dirs")
+    if keys is not None and randoms is not None:
+        raise RadianceError("%s: at most one of keys and randoms may be given" % who)
+    if keys is not None:
+        rd._cuda_tensor(who, keys, "key", "keys", nrecords, t.device, "dirs")
+    if randoms is not None:
+        rd._cuda_tensor(who, randoms, "float4", "randoms", nrecords, t.device, "dirs")
+    out = t.new("float4")
+    if t.begin():
+        EnvMisWeights(t.wrap(rays_t, "ray", nrecords), t.wrap(materials_t, "material", nrecords), t.wrap(dirs_t, "ray"), t.n, environment,
+                      t.wrap(keys, "key", nrecords), t.wrap(randoms, "float4", nrecords), t.wrap(src, "src"), nrecords, t.wrap(out, "float4"))
+    return out
+
+
+def TraceEnvMisPaths(tlas, rays, keys, n, max_depth, lights, light_count, area, area_count, environment, scene_buffers, radiance=None, rays_offset=0,
+                     keys_offset=0, lights_offset=0, area_offset=0, radiance_offset=0):
+    """Extension: TraceEnvPaths with the environment and the scatter sample weighted against each other (EnvMisWeights): the
+    environment's term of every hit is scaled by 1 - w_scatter of its direction, and a bounce ray that leaves the scene adds the
+    texel EnvLookup shows along it times the w_scatter of the sample that drew it -- so a mirror and glass show the sky, and a glossy
+    surface under a broad sky converges sooner.  Punctual and area records are unchanged.  The loop over the per-hit calls with these
+    three lines in one call, with its bits.  Arguments and result as for TraceEnvPaths."""
+    return _trace_env_paths("TraceEnvMisPaths", "rdx_trace_paths_env_mis", tlas, rays, keys, n, max_depth, lights, light_count, area, area_count, environment,
+                            scene_buffers, radiance, rays_offset, keys_offset, lights_offset, area_offset, radiance_offset)
+
+
+def TraceEnvMisPathsTorch(tlas, rays_t, keys_t, max_depth, lights_t, area_t, environment, scene_buffers):
+    """Extension: TraceEnvMisPaths on CUDA tensors, as TraceEnvPathsTorch.  Returns radiance float32 (n, 4): rgb, 0."""
+    return _trace_env_paths_torch("TraceEnvMisPathsTorch", TraceEnvMisPaths, tlas, rays_t, keys_t, max_depth, lights_t, area_t, environment, scene_buffers)
 
 
 def ProceduralSky(width, height, sun_direction=(0.3, 0.8, 0.52), sun_radiance=(4000.0, 3600.0, 3000.0), sun_angle=0.02, zenith=(0.25, 0.45, 1.0),
